@@ -9,20 +9,22 @@ the tensor's global parameters (sharded min/max scan + one 8-byte MIN all-reduce
 grows -> STRONG scaling; value = the tensor's fp32 GiB x K / max-over-ranks time.  Steps rotate over 24 distinct buffer sets (3.3 GB per GPU at
 every N: the 256 MiB Infinity Cache holds none of it, outputs included), so the number is an HBM number.
 
-This file: the timed region, `roofline`, the self-check against the checker, `cpu_baseline` (tools/bench_cpu_baseline.py, rank 0 at N = 1).
-Everything else -- graph replay, the other operators, configs 3-5, all-reduce schedules, weak scaling -- is tools/bench_extras.py, imported only
-when extras are on and unable to cost the line.  N = 1: on by default.  N > 1 (round 6): the default is the line, its N = 1 reference point and
-config 5 (the one path with a collective) -- nothing that has never run between two GPUs stands near the first scaling run; `--extras` adds the
-rest (a watchdog prints the headline with whatever has finished, and the peer-to-peer child job starts only AFTER the line is out).
-`--no-extras` prints the bare headline in a few seconds.
+A plain run is lean: set up, warm up, time EXACTLY K steps (one window; `--windows` adds more), write the outputs of the last timed step if
+`--dump-outputs DIR` is given, print the line.  Everything else runs only with `--full`: the self-check against the checker
+(`shard_bit_exact`), `cpu_baseline` (tools/bench_cpu_baseline.py, rank 0 at N = 1) and the side measurements of tools/bench_extras.py (graph
+replay, the other operators, configs 3-5, all-reduce schedules, weak scaling), imported only then and unable to cost the line.  N = 1 with
+`--full`: all of them.  N > 1 with `--full`: the line, its N = 1 reference point and config 5 (the one path with a collective); `--extras` adds
+the rest (a watchdog prints the headline with whatever has finished, and the peer-to-peer child job starts only AFTER the line is out).
+`--no-extras` / `--no-cpu-baseline` leave those legs out of a `--full` run.
 
-Launch: python bench.py [--gpus N]     (N > 1 without a launcher environment: bench.py starts its own N ranks through torch.distributed.run)
+Launch: python bench.py [--gpus N] [--full]     (N > 1 without a launcher environment: bench.py starts its own N ranks through torch.distributed.run)
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
-Prints ONE JSON line on rank 0; `ranks_seen`, `shard_bit_exact` and (N > 1) `n1_reference` let the line validate itself.
+Prints ONE JSON line on rank 0; `ranks_seen` and, with `--full`, `shard_bit_exact` and (N > 1) `n1_reference` let the line validate itself.
 """
 import argparse
 import json
 import os
+import socket
 import sys
 import threading
 import time
@@ -51,18 +53,26 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--numel", type=int, default=NUMEL)
-    ap.add_argument("--windows", type=int, default=25, help="timed windows of --steps steps each; `value` is the median window")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each; `value` is the median window (default: one window, K timed steps)")
     ap.add_argument("--sets", type=int, default=24, help="distinct buffer sets rotated through at N=1 (24 x 136 MB = 3.3 GB); N>1 keeps the same bytes per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="the bare contract line: no side measurements, no CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32/float64): a fixed, seeded sample of the uint8 "
+                         "output, its indices, the histogram of the whole output and (scale, zero_point)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the self-check against the checker, the CPU baseline and the side measurements (tools/bench_extras.py)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without side measurements and CPU baseline")
     ap.add_argument("--extras", action="store_true", default=os.environ.get("PIQUANT_BENCH_EXTRAS") == "1",
-                    help="N > 1: ALL side measurements (all-reduce schedules, hipGraph replay, weak scaling, the peer-to-peer child job); the default for N > 1 is the "
-                         "contract line, its N = 1 reference point and config 5 (sharded compute_quant_params with its 8-byte RCCL all-reduce) only")
+                    help="N > 1 with --full: ALL side measurements (all-reduce schedules, hipGraph replay, weak scaling, the peer-to-peer child job); --full alone "
+                         "for N > 1 is the contract line, its N = 1 reference point and config 5 (sharded compute_quant_params with its 8-byte RCCL all-reduce) only")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline time budget")
     # test plumbing: the N > 1 control flow on a box with ONE GPU (all ranks on cuda:0, gloo instead of RCCL, which refuses two ranks on one device)
     ap.add_argument("--backend", default="nccl", help=argparse.SUPPRESS)
     ap.add_argument("--share-gpu", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.windows < 1:
+        ap.error("--steps and --windows must be >= 1, --warmup >= 0")
+    return args
 
 
 def time_loop(fn, steps, stream, base=0):
@@ -93,6 +103,55 @@ def shard_check(x_dev, out_dev, scale, zp):
         return None
 
 
+DUMP_SAMPLE = 1 << 21         # --dump-outputs: elements of the output sampled (seeded) beyond its first and last 4096
+DUMP_SEED = 20_240_601
+
+
+def dump_outputs(path, out_dev, b0, e0, n_total, scale, zp, rank, world, use_dist):
+    """--dump-outputs: what the last timed step computed, as a caller of the path receives it -- the uint8 output of ONE logical tensor (each rank
+    holds the shard [b0, e0)) -- in float32 / float64 .npy files of about 24 MB: a fixed, seeded sample of the output with its indices, the
+    histogram of the whole output, and the (scale, zero_point) it was quantized with.  Rank 0 writes them."""
+    rng = np.random.default_rng(DUMP_SEED)
+    if n_total <= DUMP_SAMPLE:
+        idx = np.arange(n_total, dtype=np.int64)
+    else:
+        edge = np.concatenate([np.arange(4096), np.arange(n_total - 4096, n_total)])
+        idx = np.unique(np.concatenate([edge, rng.integers(0, n_total, DUMP_SAMPLE)]))
+    mine = idx[(idx >= b0) & (idx < e0)] - b0
+    vals = out_dev[torch.from_numpy(mine).to(out_dev.device)].cpu().numpy()
+    hist = torch.bincount(out_dev.long(), minlength=256).cpu().numpy()
+    parts = [(vals, hist)]
+    if use_dist:
+        parts = [None] * world
+        dist.all_gather_object(parts, (vals, hist))
+    if rank != 0:
+        return
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "quantized.npy", np.concatenate([v for v, _ in parts]).astype(np.float32))      # shards are contiguous in rank order
+    np.save(d / "quantized_index.npy", idx.astype(np.float64))
+    np.save(d / "quantized_histogram.npy", np.sum([h for _, h in parts], axis=0).astype(np.float64))
+    np.save(d / "quant_params.npy", np.array([scale, zp], dtype=np.float64))
+
+
+def wait_for_exit(pids, limit_s):
+    """True once none of the local `pids` is alive any more (gone, or a zombie that has closed its files) -- False after limit_s seconds."""
+    t_end = time.monotonic() + limit_s
+    while True:
+        alive = []
+        for pid in pids:
+            try:
+                if Path(f"/proc/{pid}/stat").read_text().rsplit(")", 1)[1].split()[0] != "Z":
+                    alive.append(pid)
+            except (OSError, IndexError):
+                pass
+        if not alive:
+            return True
+        if time.monotonic() > t_end:
+            return False
+        time.sleep(0.05)
+
+
 def device_identity(dev):
     props = torch.cuda.get_device_properties(dev)
     ident = getattr(props, "uuid", None)
@@ -109,7 +168,6 @@ def median(sorted_values):
 def launch_own_ranks(args):
     """`python bench.py --gpus N` with N > 1 and no launcher environment: start the N ranks here -- the same torch.distributed.run command the
     driver uses, rendezvous on 127.0.0.1 and a port that is free right now -- and pass their exit code on."""
-    import socket
     import subprocess
 
     if not args.share_gpu and args.gpus > torch.cuda.device_count():      # loud and at once: RCCL with two ranks on one device does not fail, it hangs
@@ -183,7 +241,7 @@ def main():
     scale, zp = (piquant.torch if world == 1 else pqd).compute_quant_params(xs[0], dtype=torch.quint8)
     torch.cuda.synchronize()
     rearm()
-    want_cpu = rank == 0 and world == 1 and not (args.no_cpu_baseline or args.no_extras)
+    want_cpu = args.full and rank == 0 and world == 1 and not (args.no_cpu_baseline or args.no_extras)
     xs0_host = xs[0].cpu().numpy() if want_cpu else None
     ptr_in, ptr_out = [t.data_ptr() for t in xs], [t.data_ptr() for t in outs]
 
@@ -202,8 +260,10 @@ def main():
     if use_dist:
         dist.barrier()     # the first collective sets the communicator up (hundreds of ms with RCCL): here, not next to the timed region
     with torch.cuda.stream(stream):
-        for i in range(PREWARM + args.warmup):
+        for i in range(PREWARM):
             step(i)
+        if args.warmup:      # the W warmup steps run through the timing code itself (result discarded): the first timed window starts warm
+            time_loop(step, args.warmup, stream, base=PREWARM)
         torch.cuda.synchronize()
         # The timed region: WINDOWS consecutive windows of EXACTLY K steps, every window bracketed by barrier + torch.cuda.synchronize() on both
         # sides (time_loop synchronizes at its start and end).  One window is what the contract describes; K = 20 steps are 0.45 ms of work, and
@@ -219,9 +279,11 @@ def main():
         if use_dist:
             dist.barrier()
 
-    # Self-validation, outside the timed region and before any side measurement reuses the buffers: every rank compares the bytes the timed
-    # calls left in output buffer 0 with the checker run on ITS shard of tensor 0, and says which device it ran on.
-    mine = {"rank": rank, "shard": [b0, e0], "bit_exact": shard_check(xs[0], outs[0], scale, zp), "device": device_identity(dev)}
+    if args.dump_outputs:      # the last timed step's output, before anything else touches the buffers
+        dump_outputs(args.dump_outputs, outs[(args.windows * args.steps - 1) % nsets], b0, e0, n_total, scale, zp, rank, world, use_dist)
+    # --full: self-validation, outside the timed region and before any side measurement reuses the buffers: every rank compares the bytes the
+    # timed calls left in output buffer 0 with the checker run on ITS shard of tensor 0.  Every run: which device each rank ran on.
+    mine = {"rank": rank, "shard": [b0, e0], "bit_exact": shard_check(xs[0], outs[0], scale, zp) if args.full else None, "device": device_identity(dev)}
     per_rank = [mine]
     t = torch.tensor([walls, evs], dtype=torch.float64, device=dev)
     if use_dist:
@@ -259,10 +321,6 @@ def main():
             "avg_launch_us": round(kernel_s * 1e6, 3), "timing": "HIP events on the launch stream around the K timed launches / K, median of the timed windows",
             "rotation": f"{nsets} buffer sets = {nsets * ALGO_BYTES_PER_ELEM * n / 1e9:.2f} GB per GPU: cold, outputs included",
         },
-        "shard_bit_exact": [r["bit_exact"] for r in per_rank],
-        "self_check": {"what": "output bytes of buffer set 0 after the timed region == the checker (oracle/: C restatement of the reference arithmetic, pinned against "
-                               "the reference's own kernels in tests/) on each rank's shard_range of tensor 0; null = checker not available on this box",
-                       "shards": [r["shard"] for r in per_rank], "all_bit_exact": all(r["bit_exact"] is True for r in per_rank)},
         "ranks_seen": {"world_size": dist.get_world_size() if use_dist else 1, "backend": (dist.get_backend() if use_dist else None),
                        "launcher": ("bench.py's own torch.distributed.run" if os.environ.get("PIQUANT_BENCH_SELF_LAUNCHED") else "external") if use_dist else None,
                        "devices": [r["device"] for r in per_rank], "distinct_devices": len({r["device"] for r in per_rank})},
@@ -272,6 +330,11 @@ def main():
                                        "dominated by its fixed ~2.4 us dispatch ramp/drain (DESIGN.md section 4), so the per-GPU fraction falls with N")
         result["roofline"]["aggregate_GB/s"] = round(ALGO_BYTES_PER_ELEM * n_total / kernel_s / 1e9, 1)
     tr = ROOT / "profiles" / "hbm_traffic.json"
+    if args.full:
+        result["shard_bit_exact"] = [r["bit_exact"] for r in per_rank]
+        result["self_check"] = {"what": "output bytes of buffer set 0 after the timed region == the checker (oracle/: C restatement of the reference arithmetic, pinned "
+                                        "against the reference's own kernels in tests/) on each rank's shard_range of tensor 0; null = checker not available on this box",
+                                "shards": [r["shard"] for r in per_rank], "all_bit_exact": all(r["bit_exact"] is True for r in per_rank)}
     if tr.exists() and world == 1 and n_total == NUMEL:      # the PMC passes were taken on the full-size launch
         try:
             rec = json.loads(tr.read_text()).get("quantize_f32_u8") or {}
@@ -294,7 +357,7 @@ def main():
     B = SimpleNamespace(args=args, ctx=ctx, stream=stream, dev=dev, rank=rank, world=world, use_dist=use_dist, n=n, n_total=n_total, nsets=nsets, scale=scale, zp=zp,
                         gib_per_step=gib_per_step, xs=xs, outs=outs, ptr_in=ptr_in, ptr_out=ptr_out, call_args=call_args, c_quantize=c_quantize, step=step,
                         time_loop=time_loop, shard_check=shard_check, xs0_host=xs0_host, result=result, side={})
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         watchdog = None
         try:
             import bench_extras
@@ -324,14 +387,23 @@ def main():
             result["cpu_baseline"] = {"value": None, "unit": "GiB/s", "cores": 0, "kind": "port", "sample": f"failed: {exc!r}"}
     emit(result)
     # The peer-to-peer transport has never run between two GPUs: its child job starts only now, with the line already out (its record: stderr).
-    if world > 1 and args.extras and not args.no_extras:
+    # The other ranks leave first, and rank 0 starts the child only once they are gone: no rank spins on the GPUs the child measures on, and the
+    # child's N ranks never hold the GPUs at the same time as this run's N.
+    if world > 1 and args.full and args.extras and not args.no_extras:
         try:
-            cpu_group = dist.new_group(backend="gloo")      # everybody waits on the CPU, not in a collective kernel spinning on the GPUs the child measures on
+            cpu_group = dist.new_group(backend="gloo")
             torch.cuda.synchronize()
+            procs = [None] * world
+            dist.all_gather_object(procs, (socket.gethostname(), os.getpid()), group=cpu_group)
             dist.barrier(group=cpu_group)
+            dist.destroy_process_group()      # every rank at the same point, nothing in flight: no communicator is left to notice the others leave
+            use_dist = False
             if rank == 0:
-                bench_extras.p2p_child(B)
-            dist.barrier(group=cpu_group)
+                others = [pid for host, pid in procs[1:] if host == procs[0][0]]
+                if wait_for_exit(others, 120.0):
+                    bench_extras.p2p_child(B)
+                else:
+                    print("bench.py p2p_transport_child_job: " + json.dumps({"error": "not run: the other ranks did not exit within 120 s"}), file=sys.stderr, flush=True)
         except Exception as exc:
             print(f"bench.py: p2p child job not run: {exc!r}", file=sys.stderr, flush=True)
     if use_dist:

@@ -23,6 +23,7 @@ OUT = Path(__file__).resolve().parent
 LENGTHS = [0, 1, 2, 3, 4, 5, 15, 16, 17, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000, 4099]
 F32_NAMES = {O.F32: "f32", O.BF16: "bf16"}
 Q_NAMES = {O.UINT8: "u8", O.UINT4: "u4", O.UINT2: "u2"}
+PART_BYTES = 1_000_000      # raw bytes of the blob per ref_vectors_part<i>.npz
 
 
 def edge_values(scale):
@@ -146,9 +147,13 @@ def main():
         chunks.append(b)
         off += b.size
     blob = np.concatenate(chunks) if chunks else np.zeros(0, np.uint8)
-    np.savez_compressed(OUT / "ref_vectors.npz", blob=blob)
+    for old in OUT.glob("ref_vectors_part*.npz"):
+        old.unlink()
+    parts = [OUT / f"ref_vectors_part{i}.npz" for i in range(-(-blob.size // PART_BYTES))]      # no stored file above 1 MB, even incompressible
+    for i, path in enumerate(parts):
+        np.savez_compressed(path, blob=blob[i * PART_BYTES: (i + 1) * PART_BYTES])
     (OUT / "ref_vectors.json").write_text(json.dumps({"cases": manifest, "index": index}, separators=(",", ":")))
-    print(f"{len(manifest)} cases, {blob.size/1e6:.2f} MB raw ->", (OUT / 'ref_vectors.npz').stat().st_size / 1e6, "MB")
+    print(f"{len(manifest)} cases, {blob.size/1e6:.2f} MB raw ->", sum(p.stat().st_size for p in parts) / 1e6, f"MB in {len(parts)} parts")
 
 
 if __name__ == "__main__":

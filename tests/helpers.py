@@ -14,7 +14,11 @@ def load_golden():
     global _cache
     if _cache is None:
         meta = json.loads((GOLDEN / "ref_vectors.json").read_text())
-        blob = np.load(GOLDEN / "ref_vectors.npz")["blob"]
+        parts, i = [], 0
+        while (GOLDEN / f"ref_vectors_part{i}.npz").exists():      # the blob in parts of at most 1 MB
+            parts.append(np.load(GOLDEN / f"ref_vectors_part{i}.npz")["blob"])
+            i += 1
+        blob = np.concatenate(parts)
         index = meta["index"]
 
         def get(name, field):

@@ -351,7 +351,7 @@ def _p2p_child_record(stderr: str):
 
 @pytest.mark.slow
 def test_bench_eight_ranks_sharing_the_gpu():
-    """The command the driver will run on an 8-GPU node plus --extras (the default prints the line with n1_reference and config 5 only -- what
+    """The command the driver will run on an 8-GPU node with --full --extras (--full alone prints the line with n1_reference and config 5 only -- what
     test_bench_two_ranks_default_flags_print_the_line_within_a_minute covers), with the eight ranks sharing this box's GPU over gloo (RCCL refuses two ranks on one
     device): 192 buffer sets of 3 408 000 elements per rank allocate, every barrier is reached, ONE JSON line comes out, the shards and the
     config-5 shards have the sizes BASELINE implies.  The numbers mean nothing; the control flow must not be what kills the first real run."""
@@ -366,7 +366,7 @@ def test_bench_eight_ranks_sharing_the_gpu():
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), str(root / "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--backend", "gloo",
-                        "--share-gpu", "--extras"], capture_output=True, text=True, timeout=1500, cwd=str(root),   # --extras: the driver's line + every side measurement
+                        "--share-gpu", "--full", "--extras"], capture_output=True, text=True, timeout=1500, cwd=str(root),   # --full --extras: the driver's line + every side measurement
                        env=dict(os.environ, PIQUANT_BENCH_EXTRAS_LIMIT_S="1200"))   # eight ranks on ONE GPU, collectives staged through the host: slow, and not the point
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -453,7 +453,7 @@ def test_quantize_shard_concatenation_is_the_whole_call(oracle_mod, world, qname
 # parameters right.
 # ---------------------------------------------------------------------------------------------------------------
 def test_bench_two_ranks_default_flags_print_the_line_within_a_minute():
-    """Round-5 verdict: the first scaling run must not be lost to a side measurement.  `bench.py --gpus 2` with DEFAULT flags is the contract line, its
+    """Round-5 verdict: the first scaling run must not be lost to a side measurement.  `bench.py --gpus 2 --full` without --extras is the contract line, its
     N = 1 reference point and config 5 (the one path with a collective) -- no all-reduce schedules, no graph replay, no weak scaling, no
     peer-to-peer child job -- and the line is on stdout within 60 s of the process start (two ranks sharing this box's one GPU)."""
     import json
@@ -466,7 +466,7 @@ def test_bench_two_ranks_default_flags_print_the_line_within_a_minute():
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PIQUANT_BENCH_EXTRAS")}
     t0 = time.perf_counter()
-    p = subprocess.Popen([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "20", "--warmup", "5"],
+    p = subprocess.Popen([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "20", "--warmup", "5", "--full"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=str(root), env=env)
     line = p.stdout.readline()
     t_line = time.perf_counter() - t0
@@ -482,7 +482,7 @@ def test_bench_two_ranks_default_flags_print_the_line_within_a_minute():
 
 
 def test_bench_two_ranks_sharing_the_gpu():
-    """`python bench.py --gpus 2 --extras` with NO launcher around it: bench.py starts its own two ranks, one JSON line comes out, and the line
+    """`python bench.py --gpus 2 --full --extras` with NO launcher around it: bench.py starts its own two ranks, one JSON line comes out, and the line
     validates itself -- ranks seen by the process group, every rank's shard bit-exact against the checker, the N = 1 point of the same run, both
     all-reduce schedules and the 8-byte MIN all-reduce in the extras."""
     import json
@@ -493,7 +493,7 @@ def test_bench_two_ranks_sharing_the_gpu():
 
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "20", "--warmup", "5", "--extras"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "20", "--warmup", "5", "--full", "--extras"],
                        capture_output=True, text=True, timeout=900, cwd=str(root), env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -560,7 +560,7 @@ def test_bench_headline_survives_side_measurements_that_overrun():
     env = dict(os.environ, PIQUANT_BENCH_EXTRAS_LIMIT_S="0.0005")   # fires while the first side measurement is being set up
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), str(root / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--backend", "gloo",
-                        "--share-gpu"], capture_output=True, text=True, timeout=600, cwd=str(root), env=env)
+                        "--share-gpu", "--full"], capture_output=True, text=True, timeout=600, cwd=str(root), env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

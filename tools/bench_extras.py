@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py's side measurements (`extras`): everything that is NOT the contract line.
 
-bench.py imports this module only when extras are on (the default) and calls it behind try/except and -- for N > 1 -- a watchdog: nothing in
+bench.py imports this module only with --full (and without --no-extras) and calls it behind try/except and -- for N > 1 -- a watchdog: nothing in
 here can cost the headline.  `B` is bench.py's state after the timed region (a SimpleNamespace: args, ctx, stream, dev, the rotating buffer
 sets xs / outs with their pointers, the prepared C calls, scale / zp, rank / world / use_dist, time_loop, shard_check, ...).
 
@@ -152,7 +152,7 @@ def p2p_all_reduce_child_job(args, world):
         if proc.returncode != 0 or not lines:
             return {"error": f"child job exit code {proc.returncode}", "stderr_tail": se[-600:]}
         rec = json.loads(lines[-1])
-        rec["how"] = "tools/p2p_all_reduce_bench.py as a child job of this run (own processes and process group on the same GPUs; this run's ranks idle on the CPU meanwhile)"
+        rec["how"] = "tools/p2p_all_reduce_bench.py as a child job of this run (own processes and process group on the same GPUs; this run's other ranks have exited, rank 0 waits on the CPU)"
         return rec
     except Exception as exc:
         return {"error": repr(exc)}

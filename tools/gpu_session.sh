@@ -26,10 +26,10 @@ for spec in $PHASES; do
                TUNE_SETS=${a2:-24} timeout 1200 ./tools/tune_kernels $NUMEL 200 $a1 > $OUT/tune_$a1.csv 2> $OUT/tune_$a1.err; say "tune $a1 rc=$?"
                python tools/summarize_tune.py $OUT/tune_$a1.csv | cut -c1-230 ;;
     xcd)       timeout 300 ./tools/diag_xcd_skew > $OUT/xcd_skew.txt 2>&1; say "xcd rc=$?"; grep "launches\|first start ->" $OUT/xcd_skew.txt ;;
-    bench)     timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; say "bench rc=$?"; cut -c1-1800 $OUT/bench.json; tail -5 $OUT/bench.err ;;
-    benchlong) timeout 900 python bench.py > $OUT/bench_long.json 2> $OUT/bench_long.err; say "benchlong rc=$?"; cut -c1-1500 $OUT/bench_long.json ;;
+    bench)     timeout 900 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; say "bench rc=$?"; cut -c1-1800 $OUT/bench.json; tail -5 $OUT/bench.err ;;
+    benchlong) timeout 900 python bench.py --full > $OUT/bench_long.json 2> $OUT/bench_long.err; say "benchlong rc=$?"; cut -c1-1500 $OUT/bench_long.json ;;
     bench2)    # the N = 2 control flow on one GPU: bench.py starts its own two ranks (gloo, sharing the device)
-               timeout 1200 python bench.py --gpus 2 --backend gloo --share-gpu --steps 20 --warmup 5 > $OUT/bench_n2_shared.json 2> $OUT/bench_n2_shared.err; say "bench2 rc=$?"
+               timeout 1200 python bench.py --gpus 2 --backend gloo --share-gpu --steps 20 --warmup 5 --full > $OUT/bench_n2_shared.json 2> $OUT/bench_n2_shared.err; say "bench2 rc=$?"
                cut -c1-3000 $OUT/bench_n2_shared.json; tail -5 $OUT/bench_n2_shared.err ;;
     wall)      timeout 600 python tools/diag_wall_overhead.py > $OUT/diag_wall_overhead.txt 2>&1; say "wall rc=$?"; cat $OUT/diag_wall_overhead.txt ;;
     matrix)    timeout 900 python tools/dtype_matrix.py > $OUT/dtype_matrix.json 2> $OUT/dtype_matrix.err; say "matrix rc=$?"

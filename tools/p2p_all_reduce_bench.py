@@ -4,7 +4,7 @@ the backend's fp32 all-reduce, on a process group of its own -- one JSON line on
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P tools/p2p_all_reduce_bench.py
 
-bench.py runs this as a CHILD job from its rank 0 while its own ranks wait on the CPU: the peer-to-peer transport has never run between two
+bench.py --full --extras runs this as a CHILD job from its rank 0 once its other ranks have exited: the peer-to-peer transport has never run between two
 GPUs, and a peer mapping that faults there takes the faulting process with it -- this process, not the one that owes the driver its line.
 (--share-gpu / --backend gloo: every rank on cuda:0, as in the one-GPU tests.)"""
 import argparse
