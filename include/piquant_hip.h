@@ -159,6 +159,28 @@ PIQUANT_EXPORT void piquant_hip_quantize_dynamic(piquant_context_t* ctx, const v
                                                  piquant_round_mode_t mode);
 PIQUANT_EXPORT void piquant_hip_set_fusion(piquant_context_t* ctx, int enabled);
 
+/* Group-wise quantization: one (scale, zero_point) per run of group_size contiguous elements instead of one per tensor, so that an
+ * outlier stretches the range of its own group only.  group_size is a power of two in [32, 4096] (128 is the usual choice); the tensor
+ * is cut into ngroups = ceil(numel / group_size) groups, the last one possibly partial.  Parameters live in two device arrays:
+ * float scales[ngroups] and uint8_t zero_points[ngroups] (a computed zero point lies in [0, 2^bits - 1]: 5 bytes per group).
+ *   piquant_hip_quantize_grouped, params_given == 0: group g's (scales[g], zero_points[g]) are written, bit-identical to what
+ *       piquant_hip_compute_quant_params_device writes for that slice alone (NaNs ignored; a group of nothing but NaNs gets the
+ *       degenerate (1.0, qmax >> 1)), and group g's bytes are piquant_hip_quantize_uniform of the slice with them.  ONE launch that reads
+ *       the input once (no scan, no atomics, no grid barrier).
+ *   params_given != 0: scales / zero_points are read instead ("quantize with these per-group parameters").
+ *   piquant_hip_dequantize_grouped: group g of `out` (op)= piquant_hip_dequantize_uniform of group g of `in` with its parameters.
+ * The position-independent form everywhere (the reference has no grouped call whose partition heads and tails could be mimicked);
+ * because group_size >= 32 is a power of two every group starts on a whole packed byte, so the output is the per-group outputs laid end
+ * to end.  Stochastic rounding draws ONE threshold per call (piquant_hip_set_stochastic_threshold pins it); in per-element mode the element
+ * index is the global index in the tensor.  Device (or pinned) buffers only; stream-ordered on the context's stream, no host
+ * synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
+                                                 size_t numel, size_t group_size, float* scales, uint8_t* zero_points, int params_given,
+                                                 piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
+                                                   size_t numel, size_t group_size, const float* scales, const uint8_t* zero_points,
+                                                   piquant_reduce_op_t op);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

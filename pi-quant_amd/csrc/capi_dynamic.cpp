@@ -414,3 +414,83 @@ int piquant_hip_peer_timeout(piquant_context_t* ctx, uint32_t* out_rank, uint32_
 }
 
 }  // extern "C"
+
+extern "C" {
+
+// Group-wise quantization (include/piquant_hip.h): one launch each, stream-ordered, device (or pinned) buffers only.
+static void check_group_size(size_t group_size) {
+    if (group_size < static_cast<size_t>(kGroupedMinG) || group_size > static_cast<size_t>(kGroupedMaxG) || (group_size & (group_size - 1)) != 0)
+        panic("group size %zu is not a power of two in [%d, %d]", group_size, kGroupedMinG, kGroupedMaxG);
+}
+
+void piquant_hip_quantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                  size_t group_size, float* scales, uint8_t* zero_points, int params_given, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;
+    if (!in || !out || !scales || !zero_points) panic("quantize_grouped: NULL buffer");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("quantize_grouped: scales must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const Resolved rin = ctx->resolve_ptr(in), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
+    if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped needs device (or pinned) buffers");
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // the call's one threshold (or the per-element seed and base), as quantize_uniform draws it
+    GroupedQuantLaunch q {};
+    q.in = rin.dev;
+    q.out = rout.dev;
+    q.numel = static_cast<int64_t>(numel);
+    q.group_size = static_cast<int64_t>(group_size);
+    q.scales = static_cast<float*>(rs.dev);
+    q.zero_points = static_cast<uint8_t*>(rz.dev);
+    q.params_given = params_given != 0;
+    q.dt_in = dtype_in;
+    q.dt_out = dtype_out;
+    q.round_mode = rm.round_mode;
+    q.threshold = rm.threshold;
+    q.seed = rm.seed;
+    q.index_base = rm.index_base;
+    {
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, q.params_given);
+        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                    size_t group_size, const float* scales, const uint8_t* zero_points, piquant_reduce_op_t op) {
+    if (!ctx) panic("piquant_hip_dequantize_grouped: context is NULL");
+    const dtype_row& dti = dtype_of(dtype_in);
+    const dtype_row& dto = dtype_of(dtype_out);
+    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
+    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
+    check_group_size(group_size);
+    if (numel == 0) return;
+    if (!in || !out || !scales || !zero_points) panic("dequantize_grouped: NULL buffer");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("dequantize_grouped: scales must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const Resolved rin = ctx->resolve_ptr(in), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
+    if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_dequantize_grouped needs device (or pinned) buffers");
+    GroupedDequantLaunch d {};
+    d.in = rin.dev;
+    d.out = rout.dev;
+    d.numel = static_cast<int64_t>(numel);
+    d.group_size = static_cast<int64_t>(group_size);
+    d.scales = static_cast<const float*>(rs.dev);
+    d.zero_points = static_cast<const uint8_t*>(rz.dev);
+    d.dt_in = dtype_in;
+    d.dt_out = dtype_out;
+    d.op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
+    {
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+}  // extern "C"

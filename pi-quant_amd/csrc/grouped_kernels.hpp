@@ -1,0 +1,427 @@
+// Group-wise quantization for gfx950: one (scale, zero point) per run of G contiguous elements, G a power of two in [32, 4096].
+//
+// Semantics (include/piquant_hip.h, piquant_hip_quantize_grouped): group g covers [g G, min((g + 1) G, numel)); its parameters are what
+// piquant_hip_compute_quant_params_device writes for that slice alone (NaNs ignored, a group of nothing but NaNs gets (1.0, qmax >> 1), the
+// f64 epilogue of minmax_kernels.hpp), and its bytes are piquant_hip_quantize_uniform of the slice with them -- the position-independent form.
+// Because G >= 32 is a power of two, every group starts on a whole packed byte and on a 16-byte input boundary, so the output is exactly the
+// per-group outputs laid end to end.
+//
+// Quantize: ONE streaming launch, no scan, no atomics, no grid barrier.  A wave owns a "chunk" of NG whole groups = NV rows of 64 consecutive
+// 16-byte input vectors (row r, lane l: vector r * 64 + l of the chunk, one coalesced 1 KiB load per row).  A group is V = G / EPV vectors:
+//   V <= 64   a group is LPG = V consecutive lanes of one row; the row holds 64 / V groups.  min / max: a segmented xor reduction of log2(V)
+//             steps (DPP quad permutes for 1 and 2, ds_swizzle for 4 .. 16 -- no LDS memory traffic -- and ds_bpermute for 32)
+//   V > 64    a group is RPG = V / 64 rows: every lane folds its RPG vectors, then the whole wave reduces (six steps)
+// The lane that starts a group parks the group's {min, max} in the wave's LDS slice; lane j < NG then runs the f64 epilogue for group j of the
+// chunk (one epilogue per group, not per lane), writes scales[g] / zero_points[g] (contiguous runs) and parks {1/scale, zp} for the lanes that
+// quantize.  Quantization and packing are the uniform kernels' (quantize_vec / quantize_vec_short), with the parameters in VGPRs instead of
+// SGPRs; the packed bytes go through the wave's LDS slice so that every lane writes 16 contiguous bytes with a write-through store.
+// The wave's last chunk may be partial (the tensor ends inside it): its missing elements are read as quiet NaNs -- which the fold ignores and
+// which quantize to 0, the bits a ragged quantize_uniform tail leaves empty -- and its stores are cut at the tensor's last packed byte.
+//
+// Dequantize: a wave owns NIN KiB of packed input (16 bytes per lane and row), staged through LDS and read back as the packed bytes of one
+// 16-byte output vector per lane and step, so that loads and stores are both coalesced 16-byte accesses; the group parameters of the chunk are
+// loaded once into LDS and every output vector picks its group's.
+#pragma once
+
+#include "dequant_kernels.hpp"
+#include "fused_kernels.hpp"
+#include "minmax_kernels.hpp"
+#include "quant_kernels.hpp"
+
+namespace pq {
+
+constexpr int kGroupedBlock = 256;   // four waves; waves never wait for one another (LDS slices are per wave)
+
+// lane l's value against lane l ^ OFF's: DPP quad permutes (VALU), ds_swizzle in bitmask mode inside 32 lanes (LDS pipe, no memory), ds_bpermute for 32
+template <int OFF>
+__device__ __forceinline__ float xor_lane(float v) {
+    const int i = __builtin_bit_cast(int, v);
+    int r;
+    if constexpr (OFF == 1) r = __builtin_amdgcn_update_dpp(i, i, 0xb1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
+    else if constexpr (OFF == 2) r = __builtin_amdgcn_update_dpp(i, i, 0x4e, 0xf, 0xf, false); // quad_perm [2,3,0,1]
+    else if constexpr (OFF < 32) r = __builtin_amdgcn_ds_swizzle(i, 0x1f | (OFF << 10));       // and 0x1f, or 0, xor OFF
+    else r = __shfl_xor(i, 32);
+    return __builtin_bit_cast(float, r);
+}
+
+// min / max over aligned runs of LPG lanes (LPG a power of two <= 64): every lane of a run ends with the run's result
+template <int LPG>
+__device__ __forceinline__ void segment_minmax(float& lo, float& hi) {
+    if constexpr (LPG > 1) { lo = __builtin_fminf(lo, xor_lane<1>(lo)); hi = __builtin_fmaxf(hi, xor_lane<1>(hi)); }
+    if constexpr (LPG > 2) { lo = __builtin_fminf(lo, xor_lane<2>(lo)); hi = __builtin_fmaxf(hi, xor_lane<2>(hi)); }
+    if constexpr (LPG > 4) { lo = __builtin_fminf(lo, xor_lane<4>(lo)); hi = __builtin_fmaxf(hi, xor_lane<4>(hi)); }
+    if constexpr (LPG > 8) { lo = __builtin_fminf(lo, xor_lane<8>(lo)); hi = __builtin_fmaxf(hi, xor_lane<8>(hi)); }
+    if constexpr (LPG > 16) { lo = __builtin_fminf(lo, xor_lane<16>(lo)); hi = __builtin_fmaxf(hi, xor_lane<16>(hi)); }
+    if constexpr (LPG > 32) { lo = __builtin_fminf(lo, xor_lane<32>(lo)); hi = __builtin_fmaxf(hi, xor_lane<32>(hi)); }
+}
+
+// same-wave LDS writes visible to the wave's later reads (DS operations of one wave execute in order; this keeps the compiler from reordering)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int DT_IN, int BITS, int G>
+struct GroupedQuantTile {
+    static constexpr int EPV = InVec<DT_IN>::EPV;
+    static constexpr int OB = EPV * BITS / 8;                       // packed bytes per input vector
+    static constexpr int V = G / EPV;                               // vectors per group
+    static constexpr int LPG = V < 64 ? V : 64;                     // lanes per group (per row)
+    static constexpr int RPG = V < 64 ? 1 : V / 64;                 // rows per group
+    static constexpr int NV_WANT = (16 / OB) > 4 ? 16 / OB : 4;     // rows for 16 output bytes per lane (at least 4 loads in flight)
+    static constexpr int NV = RPG > (V < NV_WANT ? V : NV_WANT) ? RPG : (V < NV_WANT ? V : NV_WANT);   // rows per lane (<= V: at most 64 groups)
+    static constexpr int SETS = NV / RPG;                           // groups per lane
+    static constexpr int GPR = 64 / LPG;                            // groups per row
+    static constexpr int NG = SETS * GPR;                           // groups per chunk
+    static constexpr int CHUNK_ELEMS = NV * 64 * EPV;
+    static constexpr int OUT_BYTES = NV * 64 * OB;
+    static constexpr int LANE_OUT_BYTES = NV * OB;
+    static_assert(NG >= 1 && NG <= 64 && NG * G == CHUNK_ELEMS, "a chunk is 1..64 whole groups");
+    static_assert(LANE_OUT_BYTES % 16 == 0 || LANE_OUT_BYTES == 8 || LANE_OUT_BYTES == 4, "store shapes of the staged output");
+};
+
+// one wave's chunk of `in` as NV rows of 16-byte vectors; elements at or past numel read as quiet NaNs
+template <int DT_IN, int NV>
+__device__ __forceinline__ void grouped_load(const void* in, int64_t numel, int64_t v0, int lane, bool full, u32x4 (&raw)[NV]) {
+    constexpr int EPV = InVec<DT_IN>::EPV;
+    const u32x4* in16 = static_cast<const u32x4*>(in);
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < NV; ++r) raw[r] = ld<true>(in16 + v0 + r * 64 + lane);
+        return;
+    }
+    constexpr uint32_t QNAN = DT_IN == DT_F32 ? 0x7fc00000u : 0x7fc07fc0u;
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const int64_t vec = v0 + r * 64 + lane;
+        if ((vec + 1) * EPV <= numel) {
+            raw[r] = ld<true>(in16 + vec);
+        } else {
+            raw[r] = u32x4 {QNAN, QNAN, QNAN, QNAN};
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {   // unrolled: constant register indices
+                const int64_t i = vec * EPV + e;
+                if (i >= numel) continue;
+                if constexpr (DT_IN == DT_F32) raw[r][e] = static_cast<const uint32_t*>(in)[i];
+                else raw[r][e >> 1] = (raw[r][e >> 1] & ((e & 1) ? 0x0000ffffu : 0xffff0000u)) |
+                                      (static_cast<uint32_t>(static_cast<const uint16_t*>(in)[i]) << ((e & 1) * 16));
+            }
+        }
+    }
+}
+
+// Quantize.  GIVEN: scales / zero_points are inputs ("quantize with these per-group parameters", no reduction); otherwise they are written.
+// p0 carries what is per call (threshold, seed, index base); its inv_scale / zero point are replaced per group.
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales, uint8_t* __restrict__ zero_points,
+                        int64_t ngroups, QuantParams p0) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR, NG = T::NG;
+    constexpr int WORDS = OB > 4 ? 2 : 1, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // {min, max} of the chunk's groups, then {1/scale, zero point}
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;                                   // first input vector of the chunk
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+
+    u32x4 raw[NV];
+    grouped_load<DT_IN, NV>(in, numel, v0, lane, full, raw);
+
+    const int64_t gj = g0 + lane;                                   // lane j < NG: group j of the chunk
+    bool bounded = true;
+    if constexpr (GIVEN) {
+        if (lane < NG && gj < ngroups) {
+            const float scale = scales[gj];
+            s_a[wave][lane] = __fdiv_rn(1.0f, scale);               // as the host forms 1 / scale for quantize_uniform
+            s_b[wave][lane] = __int_as_float(static_cast<int32_t>(zero_points[gj]));
+        }
+        bounded = false;                                            // no data range known: the long step everywhere
+    } else {
+        float lo[SETS], hi[SETS];
+#pragma unroll
+        for (int s = 0; s < SETS; ++s) {
+            lo[s] = 3.402823466e+38f;                               // the scan's identities (minmax_kernels.hpp)
+            hi[s] = -3.402823466e+38f;
+        }
+#pragma unroll
+        for (int r = 0; r < NV; ++r) minmax_vec<DT_IN>(raw[r], lo[r / RPG], hi[r / RPG]);   // every element quieted first: a signaling NaN poisons nothing
+#pragma unroll
+        for (int s = 0; s < SETS; ++s) {
+            segment_minmax<LPG>(lo[s], hi[s]);
+            if (lane % LPG == 0) {
+                s_a[wave][s * GPR + lane / LPG] = lo[s];
+                s_b[wave][s * GPR + lane / LPG] = hi[s];
+            }
+        }
+        wave_lds_sync();
+        if (lane < NG && gj < ngroups) {
+            const float glo = s_a[wave][lane], ghi = s_b[wave][lane];
+            float scale;
+            int64_t zp;
+            quant_params_epilogue(float_to_key(glo), float_to_key(-ghi), BITS, scale, zp);   // 0 <= zp <= 2^BITS - 1
+            const float inv = __fdiv_rn(1.0f, scale);
+            st<ST_WT>(scales + gj, scale);
+            st<ST_WT>(zero_points + gj, static_cast<uint8_t>(zp));
+            // the short step needs |x / scale| far below 2^31 for every element: |x| <= max(|min|, |max|) (quant_kernels.hpp, BoundedStep)
+            bounded = __fmul_rn(__builtin_fmaxf(__builtin_fabsf(glo), __builtin_fabsf(ghi)), inv) < 1.0e9f;
+            s_a[wave][lane] = inv;
+            s_b[wave][lane] = __int_as_float(static_cast<int32_t>(zp));
+        }
+    }
+    wave_lds_sync();
+    const bool short_step = full && __all(bounded ? 1 : 0) != 0;   // wave-uniform
+
+    [[maybe_unused]] ElementKeys keys {};
+    if constexpr (MODE == RM_STOCH_ELEM) keys = element_keys_for(p0, p0.index_base + static_cast<uint64_t>(v0 + lane) * EPV);
+    QuantParams p[SETS];
+    BoundedStep bstep[SETS];
+#pragma unroll
+    for (int s = 0; s < SETS; ++s) {
+        const int slot = s * GPR + lane / LPG;
+        p[s] = p0;
+        p[s].dyn = nullptr;
+        p[s].inv_scale = s_a[wave][slot];
+        p[s].zp32 = __float_as_int(s_b[wave][slot]);
+        p[s].zp64 = p[s].zp32;
+        bstep[s] = bounded_step_for<BITS>(p[s].zp32);
+    }
+    uint32_t w[NV][WORDS];
+    if (short_step) {
+#pragma unroll
+        for (int r = 0; r < NV; ++r)
+            quantize_vec_short<DT_IN, BITS, MODE>(raw[r], p[r / RPG], keys, static_cast<uint64_t>(v0 + r * 64 + lane) * EPV, bstep[r / RPG], w[r]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < NV; ++r) quantize_vec<DT_IN, BITS, MODE>(raw[r], p[r / RPG], keys, static_cast<uint64_t>(v0 + r * 64 + lane) * EPV, w[r]);
+    }
+
+    // stage the chunk's packed bytes, then lane-contiguous write-through stores
+    uint8_t* s = s_out[wave];
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        uint8_t* dst = s + (r * 64 + lane) * OB;
+        if constexpr (OB == 1) *dst = static_cast<uint8_t>(w[r][0]);
+        else if constexpr (OB == 2) *reinterpret_cast<uint16_t*>(dst) = static_cast<uint16_t>(w[r][0]);
+        else if constexpr (OB == 4) *reinterpret_cast<uint32_t*>(dst) = w[r][0];
+        else *reinterpret_cast<u32x2*>(dst) = u32x2 {w[r][0], w[r][1]};
+    }
+    wave_lds_sync();
+    uint8_t* o = out + v0 * OB;
+    if (full) {
+        if constexpr (T::LANE_OUT_BYTES >= 16) {
+#pragma unroll
+            for (int j = 0; j < T::LANE_OUT_BYTES / 16; ++j)
+                st<ST_WT>(reinterpret_cast<u32x4*>(o) + j * 64 + lane, reinterpret_cast<const u32x4*>(s)[j * 64 + lane]);
+        } else if constexpr (T::LANE_OUT_BYTES == 8) {
+            st<ST_WT>(reinterpret_cast<u32x2*>(o) + lane, reinterpret_cast<const u32x2*>(s)[lane]);
+        } else {
+            st<ST_WT>(reinterpret_cast<uint32_t*>(o) + lane, reinterpret_cast<const uint32_t*>(s)[lane]);
+        }
+    } else {
+        const int64_t left = (numel + PACK - 1) / PACK - v0 * OB;   // bytes of the tensor from the chunk's first byte on (< OUT_BYTES)
+        for (int b = lane; b < left; b += 64) o[b] = s[b];
+    }
+}
+
+// Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element.  Correct, not fast.
+template <int DT_IN, int BITS, int MODE, bool GIVEN>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_scalar_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, int64_t group_size, float* __restrict__ scales,
+                               uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0) {
+    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1;
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
+    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + (threadIdx.x >> 6); g < ngroups; g += waves) {
+        const int64_t b = g * group_size, e = b + group_size < numel ? b + group_size : numel;
+        float scale;
+        int64_t zp;
+        if constexpr (GIVEN) {
+            scale = scales[g];
+            zp = zero_points[g];
+        } else {
+            float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
+            for (int64_t i = b + lane; i < e; i += 64) {
+                const float x = quieted(InVec<DT_IN>::load_scalar(in, i));
+                lo = __builtin_fminf(lo, x);
+                hi = __builtin_fmaxf(hi, x);
+            }
+            lo = wave_min(lo);
+            hi = wave_max(hi);
+            quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
+            if (lane == 0) {
+                scales[g] = scale;
+                zero_points[g] = static_cast<uint8_t>(zp);
+            }
+        }
+        QuantParams p = p0;
+        p.dyn = nullptr;
+        p.inv_scale = __fdiv_rn(1.0f, scale);
+        p.zp64 = zp;
+        p.zp32 = static_cast<int32_t>(zp);
+        for (int64_t by = b / PACK + lane; by < (e + PACK - 1) / PACK; by += 64) {
+            uint32_t acc = 0;
+            for (int k = 0; k < PACK; ++k) {
+                const int64_t i = by * PACK + k;
+                if (i >= numel) break;
+                acc |= quant_one<MODE, QMAX>(InVec<DT_IN>::load_scalar(in, i), p, static_cast<uint64_t>(i)) << (k * BITS);
+            }
+            out[by] = static_cast<uint8_t>(acc);
+        }
+    }
+}
+
+template <int BITS, int DT_OUT>
+struct GroupedDequantTile {
+    static constexpr int PACK = 8 / BITS;
+    static constexpr int EPV = DT_OUT == DT_F32 ? 4 : 8;           // elements per 16-byte output vector
+    static constexpr int IB = EPV * BITS / 8;                       // packed bytes per output vector
+    static constexpr int NIN = 2;                                   // 16-byte input rows per lane
+    static constexpr int CHUNK_BYTES = NIN * 64 * 16;
+    static constexpr int CHUNK_ELEMS = CHUNK_BYTES * PACK;
+    static constexpr int OV = NIN * 16 / IB;                        // output vectors per lane
+};
+
+template <int BITS, int DT_OUT, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
+                          const uint8_t* __restrict__ zero_points, int64_t ngroups) {
+    using T = GroupedDequantTile<BITS, DT_OUT>;
+    constexpr int EPV = T::EPV, IB = T::IB, PACK = T::PACK, WAVES = kGroupedBlock / 64;
+    constexpr int NGD = T::CHUNK_ELEMS >= G ? T::CHUNK_ELEMS / G : 1;   // groups per chunk (chunk and group sizes are powers of two)
+    constexpr int FORM = DequantForm<BITS, DT_OUT>::value;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::CHUNK_BYTES];
+    __shared__ float s_scale[WAVES][NGD], s_bias[WAVES][NGD];
+    __shared__ int32_t s_zp[WAVES][NGD];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t e0 = chunk * T::CHUNK_ELEMS;
+    if (e0 >= numel) return;
+    const bool full = e0 + T::CHUNK_ELEMS <= numel;                 // wave-uniform
+    const int64_t b0 = e0 / PACK, nbytes = (numel + PACK - 1) / PACK;
+
+    u32x4 raw[T::NIN];
+#pragma unroll
+    for (int k = 0; k < T::NIN; ++k) {
+        const int64_t off = b0 + (k * 64 + lane) * 16;
+        if (full) {
+            raw[k] = ld<true>(reinterpret_cast<const u32x4*>(in + off));
+        } else {
+            raw[k] = u32x4 {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (off + j < nbytes) raw[k][j >> 2] |= static_cast<uint32_t>(in[off + j]) << ((j & 3) * 8);
+        }
+    }
+    const int64_t gfirst = e0 / G;
+    for (int j = lane; j < NGD; j += 64) {
+        if (gfirst + j < ngroups) {
+            const float scale = scales[gfirst + j];
+            const int32_t zp = zero_points[gfirst + j];
+            s_scale[wave][j] = scale;
+            s_bias[wave][j] = __fmul_rn(-static_cast<float>(zp), scale);   // as resolved(DequantParams) forms it
+            s_zp[wave][j] = zp;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < T::NIN; ++k) reinterpret_cast<u32x4*>(s_in[wave])[k * 64 + lane] = raw[k];
+    wave_lds_sync();
+
+    u32x4* out16 = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(out) + e0 * (DT_OUT == DT_F32 ? 4 : 2));
+#pragma unroll
+    for (int k = 0; k < T::OV; ++k) {
+        const int c = k * 64 + lane;                                // output vector of the chunk
+        const int ce = c * EPV;                                     // its first element, relative to e0
+        if (!full && e0 + ce >= numel) continue;
+        const int slot = NGD > 1 ? ce / G : 0;
+        DequantParams p {};
+        p.scale = s_scale[wave][slot];
+        p.bias = s_bias[wave][slot];
+        p.zp32 = s_zp[wave][slot];
+        p.zp64 = p.zp32;
+        uint32_t w[IB > 4 ? 2 : 1];
+        const uint8_t* src = s_in[wave] + c * IB;
+        if constexpr (IB == 1) w[0] = *src;
+        else if constexpr (IB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
+        else if constexpr (IB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
+        else {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
+            w[0] = t[0];
+            w[1] = t[1];
+        }
+        float f[EPV];
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p);
+        if (full || e0 + ce + EPV <= numel) {
+            u32x4 r;
+            u32x4 old {};
+            if constexpr (OP == OP_ADD) old = ld<false>(out16 + c);
+            if constexpr (DT_OUT == DT_F32) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (OP == OP_ADD) f[e] = __fadd_rn(f[e], __uint_as_float(old[e]));
+                    r[e] = __float_as_uint(f[e]);
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (OP == OP_ADD) {
+                        f[2 * e] = __fadd_rn(f[2 * e], __uint_as_float(old[e] << 16));
+                        f[2 * e + 1] = __fadd_rn(f[2 * e + 1], __uint_as_float(old[e] & 0xffff0000u));
+                    }
+                    r[e] = f32x2_to_bf16x2_bits(f[2 * e], f[2 * e + 1]);
+                }
+            }
+            st<ST_WT>(out16 + c, r);
+        } else {   // the tensor ends inside this vector
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                const int64_t i = e0 + ce + e;
+                if (i >= numel) continue;
+                if constexpr (DT_OUT == DT_F32) {
+                    float* o = static_cast<float*>(out);
+                    o[i] = OP == OP_ADD ? __fadd_rn(f[e], o[i]) : f[e];
+                } else {
+                    uint16_t* o = static_cast<uint16_t*>(out);
+                    o[i] = static_cast<uint16_t>(f32_to_bf16_bits(OP == OP_ADD ? __fadd_rn(f[e], bf16_bits_to_f32(o[i])) : f[e]));
+                }
+            }
+        }
+    }
+}
+
+// Guarded form for buffers that are not 16-byte aligned: element by element.
+template <int BITS, int DT_OUT, int OP>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_scalar_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, int64_t group_size, const float* __restrict__ scales,
+                                 const uint8_t* __restrict__ zero_points) {
+    constexpr int FORM = DequantForm<BITS, DT_OUT>::value;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kGroupedBlock;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kGroupedBlock + threadIdx.x; i < numel; i += stride) {
+        const int64_t g = i / group_size;
+        DequantParams p {};
+        p.scale = scales[g];
+        p.zp32 = zero_points[g];
+        p.zp64 = p.zp32;
+        p.bias = __fmul_rn(-static_cast<float>(p.zp32), p.scale);
+        const int64_t bit = i * BITS;
+        const float f = dequant_one<FORM>((in[bit >> 3] >> (bit & 7)) & ((1u << BITS) - 1u), p);
+        if constexpr (DT_OUT == DT_F32) {
+            float* o = static_cast<float*>(out);
+            o[i] = OP == OP_ADD ? __fadd_rn(f, o[i]) : f;
+        } else {
+            uint16_t* o = static_cast<uint16_t*>(out);
+            o[i] = static_cast<uint16_t>(f32_to_bf16_bits(OP == OP_ADD ? __fadd_rn(f, bf16_bits_to_f32(o[i])) : f));
+        }
+    }
+}
+
+}  // namespace pq

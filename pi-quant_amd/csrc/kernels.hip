@@ -5,6 +5,7 @@
 
 #include "dequant_kernels.hpp"
 #include "fused_kernels.hpp"
+#include "grouped_kernels.hpp"
 #include "minmax_kernels.hpp"
 #include "quant_kernels.hpp"
 #include "requant_kernels.hpp"
@@ -750,6 +751,149 @@ void launch_minmax(const void* in, int dt_in, int64_t numel, int32_t* state, con
         case DT_F32: minmax_t<DT_F32>(in, numel, state, ep, stream, num_cu); break;
         case DT_BF16: minmax_t<DT_BF16>(in, numel, state, ep, stream, num_cu); break;
         default: panic("min/max scan needs a float dtype, got %d", dt_in);
+    }
+    PQ_HIP(hipGetLastError());
+}
+
+namespace {
+
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN>
+void quantize_grouped_tile(const GroupedQuantLaunch& q, const QuantParams& p, int64_t ngroups, hipStream_t stream) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    const int64_t chunks = (ngroups + T::NG - 1) / T::NG;
+    const int64_t blocks = (chunks + kGroupedBlock / 64 - 1) / (kGroupedBlock / 64);
+    if (blocks > 0x7fffffff) panic("quantize_grouped: %lld blocks in one launch", static_cast<long long>(blocks));
+    PQ_LAUNCH((quantize_grouped_kernel<DT_IN, BITS, MODE, G, GIVEN>), dim3(static_cast<unsigned>(blocks)), dim3(kGroupedBlock), 0, stream, q.in,
+              static_cast<uint8_t*>(q.out), q.numel, q.scales, q.zero_points, ngroups, p);
+}
+
+template <int DT_IN, int BITS, int MODE, bool GIVEN>
+void quantize_grouped_g(const GroupedQuantLaunch& q, const QuantParams& p, hipStream_t stream, int num_cu) {
+    const int64_t ngroups = (q.numel + q.group_size - 1) / q.group_size;
+    if (!aligned16(q.in) || !aligned16(q.out)) {
+        const unsigned grid = capped_grid((ngroups + kGroupedBlock / 64 - 1) / (kGroupedBlock / 64), 16, num_cu);
+        PQ_LAUNCH((quantize_grouped_scalar_kernel<DT_IN, BITS, MODE, GIVEN>), dim3(grid), dim3(kGroupedBlock), 0, stream, q.in, static_cast<uint8_t*>(q.out),
+                  q.numel, q.group_size, q.scales, q.zero_points, ngroups, p);
+        return;
+    }
+    switch (q.group_size) {
+        case 32: quantize_grouped_tile<DT_IN, BITS, MODE, 32, GIVEN>(q, p, ngroups, stream); return;
+        case 64: quantize_grouped_tile<DT_IN, BITS, MODE, 64, GIVEN>(q, p, ngroups, stream); return;
+        case 128: quantize_grouped_tile<DT_IN, BITS, MODE, 128, GIVEN>(q, p, ngroups, stream); return;
+        case 256: quantize_grouped_tile<DT_IN, BITS, MODE, 256, GIVEN>(q, p, ngroups, stream); return;
+        case 512: quantize_grouped_tile<DT_IN, BITS, MODE, 512, GIVEN>(q, p, ngroups, stream); return;
+        case 1024: quantize_grouped_tile<DT_IN, BITS, MODE, 1024, GIVEN>(q, p, ngroups, stream); return;
+        case 2048: quantize_grouped_tile<DT_IN, BITS, MODE, 2048, GIVEN>(q, p, ngroups, stream); return;
+        case 4096: quantize_grouped_tile<DT_IN, BITS, MODE, 4096, GIVEN>(q, p, ngroups, stream); return;
+        default: panic("quantize_grouped: group size %lld (a power of two in [%d, %d] is needed)", static_cast<long long>(q.group_size), kGroupedMinG, kGroupedMaxG);
+    }
+}
+
+template <int DT_IN, int BITS, int MODE>
+void quantize_grouped_given(const GroupedQuantLaunch& q, const QuantParams& p, hipStream_t stream, int num_cu) {
+    if (q.params_given) quantize_grouped_g<DT_IN, BITS, MODE, true>(q, p, stream, num_cu);
+    else quantize_grouped_g<DT_IN, BITS, MODE, false>(q, p, stream, num_cu);
+}
+
+template <int DT_IN, int BITS>
+void quantize_grouped_mode(const GroupedQuantLaunch& q, const QuantParams& p, hipStream_t stream, int num_cu) {
+    switch (q.round_mode) {
+        case RM_NEAREST_FAST:
+        case RM_NEAREST_I64:
+            // the nearest step of quantize_uniform for the pair (quantize_mode above): f32 -> uint2 has only the generic one
+            if constexpr (DT_IN == DT_F32 && BITS == 2) quantize_grouped_given<DT_IN, BITS, RM_NEAREST_I64>(q, p, stream, num_cu);
+            else quantize_grouped_given<DT_IN, BITS, RM_NEAREST_FAST>(q, p, stream, num_cu);
+            return;
+        case RM_STOCH_CALL: quantize_grouped_given<DT_IN, BITS, RM_STOCH_CALL>(q, p, stream, num_cu); return;
+        case RM_STOCH_ELEM: quantize_grouped_given<DT_IN, BITS, RM_STOCH_ELEM>(q, p, stream, num_cu); return;
+        default: panic("invalid rounding mode %d", q.round_mode);
+    }
+}
+
+template <int DT_IN>
+void quantize_grouped_bits(const GroupedQuantLaunch& q, const QuantParams& p, hipStream_t stream, int num_cu) {
+    switch (q.dt_out) {
+        case DT_UINT8: quantize_grouped_mode<DT_IN, 8>(q, p, stream, num_cu); return;
+        case DT_UINT4: quantize_grouped_mode<DT_IN, 4>(q, p, stream, num_cu); return;
+        case DT_UINT2: quantize_grouped_mode<DT_IN, 2>(q, p, stream, num_cu); return;
+        default: panic("invalid quantization types: %d -> %d", q.dt_in, q.dt_out);
+    }
+}
+
+template <int BITS, int DT_OUT, int OP, int G>
+void dequantize_grouped_tile(const GroupedDequantLaunch& d, int64_t ngroups, hipStream_t stream) {
+    using T = GroupedDequantTile<BITS, DT_OUT>;
+    const int64_t chunks = (d.numel + T::CHUNK_ELEMS - 1) / T::CHUNK_ELEMS;
+    const int64_t blocks = (chunks + kGroupedBlock / 64 - 1) / (kGroupedBlock / 64);
+    if (blocks > 0x7fffffff) panic("dequantize_grouped: %lld blocks in one launch", static_cast<long long>(blocks));
+    PQ_LAUNCH((dequantize_grouped_kernel<BITS, DT_OUT, OP, G>), dim3(static_cast<unsigned>(blocks)), dim3(kGroupedBlock), 0, stream,
+              static_cast<const uint8_t*>(d.in), d.out, d.numel, d.scales, d.zero_points, ngroups);
+}
+
+template <int BITS, int DT_OUT, int OP>
+void dequantize_grouped_g(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu) {
+    const int64_t ngroups = (d.numel + d.group_size - 1) / d.group_size;
+    if (!aligned16(d.in) || !aligned16(d.out)) {
+        const unsigned grid = capped_grid((d.numel + kGroupedBlock - 1) / kGroupedBlock, 16, num_cu);
+        PQ_LAUNCH((dequantize_grouped_scalar_kernel<BITS, DT_OUT, OP>), dim3(grid), dim3(kGroupedBlock), 0, stream, static_cast<const uint8_t*>(d.in), d.out,
+                  d.numel, d.group_size, d.scales, d.zero_points);
+        return;
+    }
+    switch (d.group_size) {
+        case 32: dequantize_grouped_tile<BITS, DT_OUT, OP, 32>(d, ngroups, stream); return;
+        case 64: dequantize_grouped_tile<BITS, DT_OUT, OP, 64>(d, ngroups, stream); return;
+        case 128: dequantize_grouped_tile<BITS, DT_OUT, OP, 128>(d, ngroups, stream); return;
+        case 256: dequantize_grouped_tile<BITS, DT_OUT, OP, 256>(d, ngroups, stream); return;
+        case 512: dequantize_grouped_tile<BITS, DT_OUT, OP, 512>(d, ngroups, stream); return;
+        case 1024: dequantize_grouped_tile<BITS, DT_OUT, OP, 1024>(d, ngroups, stream); return;
+        case 2048: dequantize_grouped_tile<BITS, DT_OUT, OP, 2048>(d, ngroups, stream); return;
+        case 4096: dequantize_grouped_tile<BITS, DT_OUT, OP, 4096>(d, ngroups, stream); return;
+        default: panic("dequantize_grouped: group size %lld (a power of two in [%d, %d] is needed)", static_cast<long long>(d.group_size), kGroupedMinG, kGroupedMaxG);
+    }
+}
+
+template <int BITS, int DT_OUT>
+void dequantize_grouped_op(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu) {
+    switch (d.op) {
+        case OP_SET: dequantize_grouped_g<BITS, DT_OUT, OP_SET>(d, stream, num_cu); return;
+        case OP_ADD: dequantize_grouped_g<BITS, DT_OUT, OP_ADD>(d, stream, num_cu); return;
+        default: panic("invalid reduce op %d", d.op);
+    }
+}
+
+template <int BITS>
+void dequantize_grouped_out(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu) {
+    switch (d.dt_out) {
+        case DT_F32: dequantize_grouped_op<BITS, DT_F32>(d, stream, num_cu); return;
+        case DT_BF16: dequantize_grouped_op<BITS, DT_BF16>(d, stream, num_cu); return;
+        default: panic("invalid dequantization types: %d -> %d", d.dt_in, d.dt_out);
+    }
+}
+
+}  // namespace
+
+void launch_quantize_grouped(const GroupedQuantLaunch& q, hipStream_t stream, int num_cu) {
+    if (q.numel <= 0) return;
+    QuantParams p {};
+    p.threshold = q.threshold;
+    p.seed_lo = static_cast<uint32_t>(q.seed);
+    p.seed_hi = static_cast<uint32_t>(q.seed >> 32);
+    p.index_base = q.index_base;
+    switch (q.dt_in) {
+        case DT_F32: quantize_grouped_bits<DT_F32>(q, p, stream, num_cu); break;
+        case DT_BF16: quantize_grouped_bits<DT_BF16>(q, p, stream, num_cu); break;
+        default: panic("invalid quantization types: %d -> %d", q.dt_in, q.dt_out);
+    }
+    PQ_HIP(hipGetLastError());
+}
+
+void launch_dequantize_grouped(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu) {
+    if (d.numel <= 0) return;
+    switch (d.dt_in) {
+        case DT_UINT8: dequantize_grouped_out<8>(d, stream, num_cu); break;
+        case DT_UINT4: dequantize_grouped_out<4>(d, stream, num_cu); break;
+        case DT_UINT2: dequantize_grouped_out<2>(d, stream, num_cu); break;
+        default: panic("invalid dequantization types: %d -> %d", d.dt_in, d.dt_out);
     }
     PQ_HIP(hipGetLastError());
 }

@@ -90,10 +90,44 @@ struct DequantBatchLaunch {
 };
 void launch_dequantize_batch(const DequantBatchLaunch& d, hipStream_t stream);
 
+// Group-wise quantization (grouped_kernels.hpp): one (scale, zero point) per run of group_size contiguous elements, group_size a power of
+// two in [32, 4096].  Quantize computes the parameters (written to scales / zero_points) or, with params_given, reads them; either way ONE
+// launch.  Buffers 16-byte aligned take the streaming kernels, anything else the guarded one-wave-per-group kernel.
+constexpr int kGroupedMinG = 32, kGroupedMaxG = 4096;
+struct GroupedQuantLaunch {
+    const void* in;
+    void* out;
+    int64_t numel;
+    int64_t group_size;
+    float* scales;         // float32[ngroups], device
+    uint8_t* zero_points;  // uint8[ngroups], device
+    bool params_given;
+    int dt_in;             // DT_F32 / DT_BF16
+    int dt_out;            // DT_UINT2/4/8
+    int round_mode;        // RM_* (device_math.hpp)
+    float threshold;
+    uint64_t seed;
+    uint64_t index_base;
+};
+
+struct GroupedDequantLaunch {
+    const void* in;
+    void* out;
+    int64_t numel;
+    int64_t group_size;
+    const float* scales;
+    const uint8_t* zero_points;
+    int dt_in;             // DT_UINT2/4/8
+    int dt_out;            // DT_F32 / DT_BF16
+    int op;                // OP_SET / OP_ADD
+};
+
 // All launches are asynchronous on `stream`; num_cu sizes capped grids.
 void launch_quantize(const QuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize(const DequantLaunch& d, hipStream_t stream, int num_cu);
 void launch_requantize(const RequantLaunch& r, hipStream_t stream, int num_cu);
+void launch_quantize_grouped(const GroupedQuantLaunch& q, hipStream_t stream, int num_cu);
+void launch_dequantize_grouped(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -420,6 +420,23 @@ class Context:
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_dequantize_dp(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, params_ptr, reduce_op.value)
 
+    def quantize_grouped_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                             scales_ptr: int, zero_points_ptr: int, params_given: bool, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """Group-wise quantize (``piquant_hip_quantize_grouped``): one (scale, zero point) per ``group_size`` contiguous elements, in a
+        float32[ngroups] and a uint8[ngroups] device array -- written from the data, or read when ``params_given``."""
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+                                       1 if params_given else 0, round_mode.value)
+
+    def dequantize_grouped_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                               scales_ptr: int, zero_points_ptr: int, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """Group-wise dequantize (``piquant_hip_dequantize_grouped``), the parameters of ``quantize_grouped_ptr``."""
+        assert dtype_in.is_quantized and dtype_out.is_dequantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_grouped(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+                                         reduce_op.value)
+
     def compute_quant_params_dist_ptr(self, ptr: int, dtype: DataType, numel: int, target_quant_dtype: DataType, nccl_comm: int,
                                       _device_ptrs: bool = False) -> Tuple[float, int]:
         """Sharded ``compute_quant_params`` with the all-reduce done natively: ``nccl_comm`` is an ``ncclComm_t`` (RCCL)."""

@@ -392,6 +392,92 @@ def dequantize_dynamic(tensor: torch.Tensor, params: torch.Tensor, *, dtype: tor
     return out
 
 
+# ---- group-wise quantization: one (scale, zero point) per run of group_size contiguous elements --------------------------------------------
+GROUP_SIZES = tuple(1 << k for k in range(5, 13))   # powers of two in [32, 4096]
+
+
+def num_groups(numel: int, group_size: int) -> int:
+    """Groups of a tensor of ``numel`` elements (the last one may be partial)."""
+    return (int(numel) + int(group_size) - 1) // int(group_size)
+
+
+def _check_group_size(group_size) -> None:
+    _require(isinstance(group_size, int) and not isinstance(group_size, bool) and group_size in GROUP_SIZES,
+             f'group_size must be a power of two in [32, 4096], got {group_size!r}')
+
+
+def _check_group_params(scales, zero_points, ngroups: int) -> None:
+    """Shape and dtype of the per-group parameters (device placement is checked against the tensor separately)."""
+    _require(isinstance(scales, torch.Tensor) and scales.dtype == torch.float32 and scales.dim() == 1 and scales.numel() == ngroups and scales.is_contiguous(),
+             f'scales must be a contiguous 1-D float32 tensor of {ngroups} elements')
+    _require(isinstance(zero_points, torch.Tensor) and zero_points.dtype == torch.uint8 and zero_points.dim() == 1 and zero_points.numel() == ngroups and
+             zero_points.is_contiguous(), f'zero_points must be a contiguous 1-D uint8 tensor of {ngroups} elements')
+
+
+def quantize_grouped(tensor: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
+                     out: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None,
+                     zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Group-wise quantization: the flattened tensor is cut into ``ceil(numel / group_size)`` groups of ``group_size`` contiguous elements
+    (the last may be partial), each with its own (scale, zero point).  Returns (quantized, scales, zero_points): the quantized tensor has the
+    input's shape and ``dtype``; ``scales`` is float32[ngroups], ``zero_points`` uint8[ngroups], both on the tensor's device.  Group g's
+    parameters equal ``compute_quant_params`` of that slice and its bytes equal the position-independent quantize of the slice with them.
+    Passing both ``scales`` and ``zero_points`` quantizes with those parameters instead of computing them.  One asynchronous launch on the
+    current stream (``include/piquant_hip.h``, piquant_hip_quantize_grouped)."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    ngroups = num_groups(tensor.numel(), group_size)
+    given = scales is not None
+    if given:
+        _check_group_params(scales, zero_points, ngroups)
+    _check_float_input(tensor)
+    if given:
+        _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
+    else:
+        scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
+        zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    if out is None:
+        out = torch.empty(tensor.shape, dtype=dtype, device=tensor.device)
+    else:
+        _check_packed_out(out, torch_to_piquant_dtype(dtype), tensor.numel(), tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_grouped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(dtype), tensor.numel(),
+                             group_size, scales.data_ptr(), zero_points.data_ptr(), given, _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, scales, zero_points
+
+
+def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor, *, dtype: torch.dtype, group_size: int,
+                       reduce_op: str = 'set', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                       quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
+    """Inverse of ``quantize_grouped``: group g of the result (``reduce_op='set'``) or of ``out`` (``'add'``) is the dequantized group g with
+    ``scales[g]`` / ``zero_points[g]``.  A raw uint8 buffer of packed bytes needs ``quant_dtype=`` and ``shape=``."""
+    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
+    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
+    _check_group_size(group_size)
+    _require(isinstance(tensor, torch.Tensor) and (tensor.dtype in _QUANT_TYPES or quant_dtype is not None), 'tensor must be a quantized tensor')
+    dtype_in, logical_shape = _quant_meta(tensor, quant_dtype, shape)
+    numel = _numel_of(logical_shape)
+    _check_group_params(scales, zero_points, num_groups(numel, group_size))
+    _require(tensor.is_cuda, 'dequantize_grouped needs a ROCm device tensor')
+    _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    _check_packed_in(tensor, dtype_in, numel, tensor.device, 'tensor')
+    if out is None:
+        if reduce_op == 'add':
+            raise ValueError("reduce_op='add' accumulates into out=; pass the accumulator tensor")
+        out = torch.empty(logical_shape, dtype=dtype, device=tensor.device)
+    else:
+        _check_float_out(out, dtype, numel, tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.dequantize_grouped_ptr(tensor.data_ptr(), dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, group_size, scales.data_ptr(),
+                               zero_points.data_ptr(), _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return out
+
 def dequantize_sum(tensors, params, *, dtype: torch.dtype, reduce_op: str = 'set', ctx: Optional[Context] = None,
                    out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
     """out (op)= sum_i dequantize(tensors[i]) with (scale, zero_point) of input i read from the device record ``params[i]``: one pass

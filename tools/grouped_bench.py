@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Group-wise quantization at the headline size (numel 27 264 000), next to the per-tensor calls of the same pairs.
+
+Protocol of the headline numbers: input buffers rotated over >= 3.3 GB (no call finds its input in the 256 MiB Infinity Cache), HIP events around
+windows of back-to-back calls, the median of several windows.  Rows: every quantize pair at G in {32, 128, 1024, 4096} against quantize_uniform and
+against scan + quantize (compute_quant_params_device -> quantize_dp, two launches); every dequantize pair at G = 128 against dequantize_uniform.
+Each row gives us per call, algorithmic bytes (the 5 bytes per group included) and the fraction of 8 TB/s.  Writes profiles/grouped_bench.json.
+
+    python tools/grouped_bench.py [--windows 7] [--rotate-gb 3.3] [--out profiles/grouped_bench.json]
+"""
+import argparse
+import json
+import statistics
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "pi-quant_amd"))
+
+import piquant  # noqa: E402
+import piquant.torch as pt  # noqa: E402
+
+NUMEL = 27_264_000
+HBM_PEAK_GBS = 8000.0
+QUANT = {"uint8": (piquant.DataType.UINT8, 8), "uint4": (piquant.DataType.UINT4, 4), "uint2": (piquant.DataType.UINT2, 2)}
+FLOAT = {"f32": (piquant.DataType.F32, torch.float32, 4), "bf16": (piquant.DataType.BF16, torch.bfloat16, 2)}
+GROUPS = (32, 128, 1024, 4096)
+
+
+def timed(call, nbuf, windows, per_window, stream):
+    """median us per call over `windows` windows of `per_window` calls, buffer i % nbuf for call i"""
+    for i in range(min(nbuf, 8)):
+        call(i)
+    torch.cuda.synchronize()
+    res, k = [], 0
+    for _ in range(windows):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(per_window):
+            call(k % nbuf)
+            k += 1
+        b.record(stream)
+        b.synchronize()
+        res.append(a.elapsed_time(b) * 1000.0 / per_window)
+    return statistics.median(res), res
+
+
+def row(kind, pair, g, us, nbytes, samples):
+    r = {"kind": kind, "pair": pair, "group_size": g, "us": round(us, 3), "bytes": int(nbytes), "tb_s": round(nbytes / us / 1e6, 3),
+         "frac_8tbs": round(nbytes / us / 1e6 / (HBM_PEAK_GBS / 1000.0), 4), "windows_us": [round(s, 3) for s in samples]}
+    print(f"{kind:22s} {pair:12s} G={g if g else '-':>5} {us:8.2f} us  {nbytes / 1e6:8.1f} MB  {r['frac_8tbs']:.3f} of 8 TB/s", flush=True)
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--rotate-gb", type=float, default=3.3)
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "grouped_bench.json"))
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream()
+    ctx = piquant.Context.get(0)
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_blocking(False)
+    ctx.assume_device_pointers(True)
+    rows = []
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
+        g = torch.Generator(device=dev)
+        g.manual_seed(1)
+        xs = [torch.empty(NUMEL, dtype=tdt, device=dev).normal_(generator=g) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 64)
+        for qname, (qdt, bits) in QUANT.items():
+            pair = f"{fname}->{qname}"
+            nq = qdt.packed_nbytes(NUMEL)
+            outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            rec = [torch.empty(16, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            scale, zp = pt.compute_quant_params(xs[0], dtype={8: torch.uint8, 4: torch.quint4x2, 2: torch.quint2x4}[bits])
+            us, s = timed(lambda i: ctx.quantize_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, scale, zp, piquant.RoundMode.NEAREST,
+                                                     _device_ptrs=True, uniform=True), nbuf, args.windows, per_window, stream)
+            rows.append(row("quantize_uniform", pair, 0, us, NUMEL * esize + nq, s))
+            us, s = timed(lambda i: (ctx.compute_quant_params_device_ptr(xs[i].data_ptr(), fdt, NUMEL, qdt, rec[i].data_ptr(), _device_ptrs=True),
+                                     ctx.quantize_dp_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, rec[i].data_ptr(), piquant.RoundMode.NEAREST,
+                                                         _device_ptrs=True)), nbuf, args.windows, per_window, stream)
+            rows.append(row("scan+quantize", pair, 0, us, 2 * NUMEL * esize + nq, s))
+            for G in GROUPS:
+                ng = pt.num_groups(NUMEL, G)
+                sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+                zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+                us, s = timed(lambda i: ctx.quantize_grouped_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                                                 False, piquant.RoundMode.NEAREST, _device_ptrs=True), nbuf, args.windows, per_window, stream)
+                rows.append(row("quantize_grouped", pair, G, us, NUMEL * esize + nq + 5 * ng, s))
+                if G == 128:   # dequantize of the same pair, with this call's parameters
+                    dpair = f"{qname}->{fname}"
+                    ys = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+                    us, s = timed(lambda i: ctx.dequantize_ptr(outs[i].data_ptr(), qdt, ys[i].data_ptr(), fdt, NUMEL, scale, zp, piquant.ReduceOp.SET,
+                                                               _device_ptrs=True, uniform=True), nbuf, args.windows, per_window, stream)
+                    rows.append(row("dequantize_uniform", dpair, 0, us, NUMEL * esize + nq, s))
+                    us, s = timed(lambda i: ctx.dequantize_grouped_ptr(outs[i].data_ptr(), qdt, ys[i].data_ptr(), fdt, NUMEL, G, sc[i].data_ptr(),
+                                                                       zs[i].data_ptr(), piquant.ReduceOp.SET, _device_ptrs=True),
+                                  nbuf, args.windows, per_window, stream)
+                    rows.append(row("dequantize_grouped", dpair, G, us, NUMEL * esize + nq + 5 * ng, s))
+                    del ys
+                del sc, zs
+            del outs, rec
+        del xs
+        torch.cuda.empty_cache()
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
+                               "windows": args.windows, "rows": rows}, indent=1) + "\n")
+    print(f"wrote {out}")
+
+
+if __name__ == "__main__":
+    main()
