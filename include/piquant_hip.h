@@ -180,6 +180,29 @@ PIQUANT_EXPORT void piquant_hip_quantize_grouped(piquant_context_t* ctx, const v
 PIQUANT_EXPORT void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
                                                    size_t numel, size_t group_size, const float* scales, const uint8_t* zero_points,
                                                    piquant_reduce_op_t op);
+/* Batches of the group-wise calls: tensor i has its own input, output, scales, zero_points and numels[i]; all share the dtype pair, group_size,
+ * params_given / op and the round mode.  Tensor i's results are those of the single call on it; a stochastic batch draws ONE threshold (in
+ * per-element mode every tensor indexes its own elements from 0).  Up to 16 tensors per launch (more: one launch per 16); empty tensors are
+ * skipped, and a tensor whose input or output is not 16-byte aligned goes through the single call.
+ * piquant_hip_reduce_quantize_grouped: (out, scales, zero_points) = quantize_grouped(acc + dequantize_grouped(inputs[0]) + ... +
+ *       dequantize_grouped(inputs[count - 1])), term i with its own per-group parameters input_scales[i] / input_zero_points[i] (the same
+ *       group_size; every term has numel elements of type dtype_out).  The terms are added in order and the running sum is rounded to dtype_acc
+ *       after each one: bit for bit piquant_hip_dequantize_grouped(inputs[i], ..., PIQUANT_REDUCE_OP_ADD) into acc for i = 0 .. count - 1 followed
+ *       by piquant_hip_quantize_grouped(acc) with computed parameters -- in ONE launch that keeps the sum on chip (no scan, no atomics, no grid
+ *       barrier).  More than 16 terms: the surplus is first added into acc by grouped dequantize ADD launches and the last 16 are fused; buffers
+ *       that are not 16-byte aligned take that two-step form for every term.  count == 0 is piquant_hip_quantize_grouped(acc).  The contents of
+ *       acc afterwards are unspecified.  The owner's step of a grouped mesh all-reduce (count = world - 1) and every hop of a grouped ring (count = 1).
+ * Device (or pinned) buffers only; stream-ordered on the context's stream, no host synchronisation, no allocation (hipGraph-capturable). */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                                       piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                                       uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                                         piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales,
+                                                         const uint8_t* const* zero_points, size_t count, piquant_reduce_op_t op);
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
+                                                        const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                                        piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                                        piquant_round_mode_t mode);
 
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a

@@ -494,3 +494,216 @@ void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piqu
 }
 
 }  // extern "C"
+
+extern "C" {
+
+// Batches and the fused reduce of the group-wise calls (include/piquant_hip.h): stream-ordered, device (or pinned) buffers only, no allocation.
+static inline bool grouped_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                        piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                        uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_batch: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_batch: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
+    GroupedQuantBatchLaunch b {};
+    b.group_size = static_cast<int64_t>(group_size);
+    b.params_given = params_given != 0;
+    b.dt_in = dtype_in;
+    b.dt_out = dtype_out;
+    b.round_mode = rm.round_mode;
+    b.threshold = rm.threshold;
+    b.seed = rm.seed;
+    b.index_base = rm.index_base;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, b.params_given);
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        if (!inputs[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_batch: NULL buffer %zu", i);
+        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_batch: scales %zu must be 4-byte aligned", i);
+        const Resolved rin = ctx->resolve_ptr(inputs[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]), rz = resolve(zero_points[i]);
+        if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped_batch needs device (or pinned) buffers");
+        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rout.dev)) {   // the single call's guarded kernel, same bytes
+            GroupedQuantLaunch q {};
+            q.in = rin.dev;
+            q.out = rout.dev;
+            q.numel = static_cast<int64_t>(numels[i]);
+            q.group_size = b.group_size;
+            q.scales = static_cast<float*>(rs.dev);
+            q.zero_points = static_cast<uint8_t*>(rz.dev);
+            q.params_given = b.params_given;
+            q.dt_in = dtype_in;
+            q.dt_out = dtype_out;
+            q.round_mode = b.round_mode;
+            q.threshold = b.threshold;
+            q.seed = b.seed;
+            q.index_base = b.index_base;
+            launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        b.in[b.count] = rin.dev;
+        b.out[b.count] = rout.dev;
+        b.scales[b.count] = static_cast<float*>(rs.dev);
+        b.zero_points[b.count] = static_cast<uint8_t*>(rz.dev);
+        b.numel[b.count] = static_cast<int64_t>(numels[i]);
+        if (++b.count == kGroupedBatchMaxTensors) {
+            launch_quantize_grouped_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_quantize_grouped_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                          piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales,
+                                          const uint8_t* const* zero_points, size_t count, piquant_reduce_op_t op) {
+    if (!ctx) panic("piquant_hip_dequantize_grouped_batch: context is NULL");
+    const dtype_row& dti = dtype_of(dtype_in);
+    const dtype_row& dto = dtype_of(dtype_out);
+    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
+    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_dequantize_grouped_batch: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    GroupedDequantBatchLaunch b {};
+    b.group_size = static_cast<int64_t>(group_size);
+    b.dt_in = dtype_in;
+    b.dt_out = dtype_out;
+    b.op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        if (!inputs[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("dequantize_grouped_batch: NULL buffer %zu", i);
+        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("dequantize_grouped_batch: scales %zu must be 4-byte aligned", i);
+        const Resolved rin = ctx->resolve_ptr(inputs[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]), rz = resolve(zero_points[i]);
+        if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_dequantize_grouped_batch needs device (or pinned) buffers");
+        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rout.dev)) {
+            GroupedDequantLaunch d {};
+            d.in = rin.dev;
+            d.out = rout.dev;
+            d.numel = static_cast<int64_t>(numels[i]);
+            d.group_size = b.group_size;
+            d.scales = static_cast<const float*>(rs.dev);
+            d.zero_points = static_cast<const uint8_t*>(rz.dev);
+            d.dt_in = dtype_in;
+            d.dt_out = dtype_out;
+            d.op = b.op;
+            launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        b.in[b.count] = rin.dev;
+        b.out[b.count] = rout.dev;
+        b.scales[b.count] = static_cast<const float*>(rs.dev);
+        b.zero_points[b.count] = static_cast<const uint8_t*>(rz.dev);
+        b.numel[b.count] = static_cast<int64_t>(numels[i]);
+        if (++b.count == kGroupedBatchMaxTensors) {
+            launch_dequantize_grouped_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_dequantize_grouped_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
+                                         const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                         piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_reduce_quantize_grouped: context is NULL");
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;
+    if (!acc || !out || !scales || !zero_points) panic("reduce_quantize_grouped: NULL buffer");
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped: NULL argument");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped: scales must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const Resolved racc = ctx->resolve_ptr(acc), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
+    if (racc.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_reduce_quantize_grouped needs device (or pinned) buffers");
+    // the terms, resolved; every buffer 16-byte aligned takes the fused kernel, anything else the two-step form (same bytes)
+    std::vector<const void*> tin(count);
+    std::vector<const float*> tsc(count);
+    std::vector<const uint8_t*> tzp(count);
+    bool aligned = grouped_aligned16(racc.dev) && grouped_aligned16(rout.dev);
+    for (size_t i = 0; i < count; ++i) {
+        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped: NULL input %zu", i);
+        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped: input scales %zu must be 4-byte aligned", i);
+        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
+        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped needs device (or pinned) buffers");
+        tin[i] = ri.dev;
+        tsc[i] = static_cast<const float*>(rsi.dev);
+        tzp[i] = static_cast<const uint8_t*>(rzi.dev);
+        aligned = aligned && grouped_aligned16(ri.dev);
+    }
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // the call's one threshold, whichever form runs
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the terms' parameters are written by whatever was enqueued just before
+    // terms that are not fused: grouped dequantize ADD into acc, in order
+    const size_t fused_from = aligned ? (count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0) : count;
+    for (size_t i = 0; i < fused_from; ++i) {
+        GroupedDequantLaunch d {};
+        d.in = tin[i];
+        d.out = racc.dev;
+        d.numel = static_cast<int64_t>(numel);
+        d.group_size = static_cast<int64_t>(group_size);
+        d.scales = tsc[i];
+        d.zero_points = tzp[i];
+        d.dt_in = dtype_out;
+        d.dt_out = dtype_acc;
+        d.op = OP_ADD;
+        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+    }
+    if (aligned && count > 0) {
+        GroupedReduceLaunch r {};
+        r.acc = racc.dev;
+        r.out = rout.dev;
+        r.numel = static_cast<int64_t>(numel);
+        r.group_size = static_cast<int64_t>(group_size);
+        r.scales = static_cast<float*>(rs.dev);
+        r.zero_points = static_cast<uint8_t*>(rz.dev);
+        for (size_t i = fused_from; i < count; ++i) {
+            r.in[r.count] = tin[i];
+            r.in_scales[r.count] = tsc[i];
+            r.in_zero_points[r.count] = tzp[i];
+            ++r.count;
+        }
+        r.dt_acc = dtype_acc;
+        r.dt_out = dtype_out;
+        r.round_mode = rm.round_mode;
+        r.threshold = rm.threshold;
+        r.seed = rm.seed;
+        r.index_base = rm.index_base;
+        launch_reduce_quantize_grouped(r, ctx->stream);
+    } else {   // k == 0, or the two-step form: quantize_grouped(acc)
+        GroupedQuantLaunch q {};
+        q.in = racc.dev;
+        q.out = rout.dev;
+        q.numel = static_cast<int64_t>(numel);
+        q.group_size = static_cast<int64_t>(group_size);
+        q.scales = static_cast<float*>(rs.dev);
+        q.zero_points = static_cast<uint8_t*>(rz.dev);
+        q.params_given = false;
+        q.dt_in = dtype_acc;
+        q.dt_out = dtype_out;
+        q.round_mode = rm.round_mode;
+        q.threshold = rm.threshold;
+        q.seed = rm.seed;
+        q.index_base = rm.index_base;
+        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+}  // extern "C"

@@ -18,6 +18,11 @@
 // The wave's last chunk may be partial (the tensor ends inside it): its missing elements are read as quiet NaNs -- which the fold ignores and
 // which quantize to 0, the bits a ragged quantize_uniform tail leaves empty -- and its stores are cut at the tensor's last packed byte.
 //
+// Fused reduce + quantize (reduce_quantize_grouped_kernel): the quantize tile with up to 16 packed terms added into the resident rows first,
+// each term's chunk staged through the wave's LDS slice and dequantized with its own group parameters -- the bytes of grouped dequantize ADD per
+// term followed by quantize.  Batches (quantize_grouped_batch_kernel, dequantize_grouped_batch_kernel): up to 16 tensors in one launch, a wave
+// finding its tensor in a prefix table of chunk counts, then running the single kernel's body.
+//
 // Dequantize: a wave owns NIN KiB of packed input (16 bytes per lane and row), staged through LDS and read back as the packed bytes of one
 // 16-byte output vector per lane and step, so that loads and stores are both coalesced 16-byte accesses; the group parameters of the chunk are
 // loaded once into LDS and every output vector picks its group's.
@@ -111,36 +116,26 @@ __device__ __forceinline__ void grouped_load(const void* in, int64_t numel, int6
     }
 }
 
-// Quantize.  GIVEN: scales / zero_points are inputs ("quantize with these per-group parameters", no reduction); otherwise they are written.
-// p0 carries what is per call (threshold, seed, index base); its inv_scale / zero point are replaced per group.
-template <int DT_IN, int BITS, int MODE, int G, bool GIVEN>
-__global__ void __launch_bounds__(kGroupedBlock)
-quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales, uint8_t* __restrict__ zero_points,
-                        int64_t ngroups, QuantParams p0) {
+// Quantize of one chunk whose NV rows are in `raw` (grouped_load: elements at or past numel are quiet NaNs): parameters, quantization, staged
+// stores.  GIVEN: scales / zero_points are inputs ("quantize with these per-group parameters", no reduction); otherwise they are written.
+// p0 carries what is per call (threshold, seed, index base); its inv_scale / zero point are replaced per group.  The wave's LDS
+// slices (stage: OUT_BYTES bytes; s_a, s_b: NG floats each).
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN, int NV_ = GroupedQuantTile<DT_IN, BITS, G>::NV>
+__device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_t* __restrict__ out, int64_t numel,
+                                                       float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
+                                                       int64_t g0, bool full, int lane, uint8_t* stage, float* s_a, float* s_b) {
     using T = GroupedQuantTile<DT_IN, BITS, G>;
     constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR, NG = T::NG;
-    constexpr int WORDS = OB > 4 ? 2 : 1, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
-    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // {min, max} of the chunk's groups, then {1/scale, zero point}
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    const int64_t g0 = chunk * NG;
-    if (g0 >= ngroups) return;
+    constexpr int WORDS = OB > 4 ? 2 : 1, PACK = 8 / BITS;
     const int64_t v0 = g0 * T::V;                                   // first input vector of the chunk
-    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
-
-    u32x4 raw[NV];
-    grouped_load<DT_IN, NV>(in, numel, v0, lane, full, raw);
 
     const int64_t gj = g0 + lane;                                   // lane j < NG: group j of the chunk
     bool bounded = true;
     if constexpr (GIVEN) {
         if (lane < NG && gj < ngroups) {
             const float scale = scales[gj];
-            s_a[wave][lane] = __fdiv_rn(1.0f, scale);               // as the host forms 1 / scale for quantize_uniform
-            s_b[wave][lane] = __int_as_float(static_cast<int32_t>(zero_points[gj]));
+            s_a[lane] = __fdiv_rn(1.0f, scale);                     // as the host forms 1 / scale for quantize_uniform
+            s_b[lane] = __int_as_float(static_cast<int32_t>(zero_points[gj]));
         }
         bounded = false;                                            // no data range known: the long step everywhere
     } else {
@@ -156,13 +151,13 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
         for (int s = 0; s < SETS; ++s) {
             segment_minmax<LPG>(lo[s], hi[s]);
             if (lane % LPG == 0) {
-                s_a[wave][s * GPR + lane / LPG] = lo[s];
-                s_b[wave][s * GPR + lane / LPG] = hi[s];
+                s_a[s * GPR + lane / LPG] = lo[s];
+                s_b[s * GPR + lane / LPG] = hi[s];
             }
         }
         wave_lds_sync();
         if (lane < NG && gj < ngroups) {
-            const float glo = s_a[wave][lane], ghi = s_b[wave][lane];
+            const float glo = s_a[lane], ghi = s_b[lane];
             float scale;
             int64_t zp;
             quant_params_epilogue(float_to_key(glo), float_to_key(-ghi), BITS, scale, zp);   // 0 <= zp <= 2^BITS - 1
@@ -171,8 +166,8 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
             st<ST_WT>(zero_points + gj, static_cast<uint8_t>(zp));
             // the short step needs |x / scale| far below 2^31 for every element: |x| <= max(|min|, |max|) (quant_kernels.hpp, BoundedStep)
             bounded = __fmul_rn(__builtin_fmaxf(__builtin_fabsf(glo), __builtin_fabsf(ghi)), inv) < 1.0e9f;
-            s_a[wave][lane] = inv;
-            s_b[wave][lane] = __int_as_float(static_cast<int32_t>(zp));
+            s_a[lane] = inv;
+            s_b[lane] = __int_as_float(static_cast<int32_t>(zp));
         }
     }
     wave_lds_sync();
@@ -187,8 +182,8 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
         const int slot = s * GPR + lane / LPG;
         p[s] = p0;
         p[s].dyn = nullptr;
-        p[s].inv_scale = s_a[wave][slot];
-        p[s].zp32 = __float_as_int(s_b[wave][slot]);
+        p[s].inv_scale = s_a[slot];
+        p[s].zp32 = __float_as_int(s_b[slot]);
         p[s].zp64 = p[s].zp32;
         bstep[s] = bounded_step_for<BITS>(p[s].zp32);
     }
@@ -203,10 +198,9 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
     }
 
     // stage the chunk's packed bytes, then lane-contiguous write-through stores
-    uint8_t* s = s_out[wave];
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
-        uint8_t* dst = s + (r * 64 + lane) * OB;
+        uint8_t* dst = stage + (r * 64 + lane) * OB;
         if constexpr (OB == 1) *dst = static_cast<uint8_t>(w[r][0]);
         else if constexpr (OB == 2) *reinterpret_cast<uint16_t*>(dst) = static_cast<uint16_t>(w[r][0]);
         else if constexpr (OB == 4) *reinterpret_cast<uint32_t*>(dst) = w[r][0];
@@ -218,16 +212,233 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
         if constexpr (T::LANE_OUT_BYTES >= 16) {
 #pragma unroll
             for (int j = 0; j < T::LANE_OUT_BYTES / 16; ++j)
-                st<ST_WT>(reinterpret_cast<u32x4*>(o) + j * 64 + lane, reinterpret_cast<const u32x4*>(s)[j * 64 + lane]);
+                st<ST_WT>(reinterpret_cast<u32x4*>(o) + j * 64 + lane, reinterpret_cast<const u32x4*>(stage)[j * 64 + lane]);
         } else if constexpr (T::LANE_OUT_BYTES == 8) {
-            st<ST_WT>(reinterpret_cast<u32x2*>(o) + lane, reinterpret_cast<const u32x2*>(s)[lane]);
+            st<ST_WT>(reinterpret_cast<u32x2*>(o) + lane, reinterpret_cast<const u32x2*>(stage)[lane]);
         } else {
-            st<ST_WT>(reinterpret_cast<uint32_t*>(o) + lane, reinterpret_cast<const uint32_t*>(s)[lane]);
+            st<ST_WT>(reinterpret_cast<uint32_t*>(o) + lane, reinterpret_cast<const uint32_t*>(stage)[lane]);
         }
     } else {
         const int64_t left = (numel + PACK - 1) / PACK - v0 * OB;   // bytes of the tensor from the chunk's first byte on (< OUT_BYTES)
-        for (int b = lane; b < left; b += 64) o[b] = s[b];
+        for (int b = lane; b < left; b += 64) o[b] = stage[b];
     }
+}
+
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales, uint8_t* __restrict__ zero_points,
+                        int64_t ngroups, QuantParams p0) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // {min, max} of the chunk's groups, then {1/scale, zero point}
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+
+    u32x4 raw[NV];
+    grouped_load<DT_IN, NV>(in, numel, g0 * T::V, lane, full, raw);
+    grouped_quantize_chunk<DT_IN, BITS, MODE, G, GIVEN>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, s_out[wave], s_a[wave], s_b[wave]);
+}
+
+// Batch: up to kGroupedBatchMax independent tensors in ONE launch.  The chunks of tensor t are [chunk_begin[t], chunk_begin[t + 1]) of the grid's
+// waves; a wave finds its tensor from the prefix table (wave-uniform, <= 15 compares) and then runs exactly the single-tensor kernel's body.
+constexpr int kGroupedBatchMax = 16;
+struct GroupedQuantBatchArgs {
+    const void* in[kGroupedBatchMax];
+    uint8_t* out[kGroupedBatchMax];
+    float* scales[kGroupedBatchMax];
+    uint8_t* zero_points[kGroupedBatchMax];
+    int64_t numel[kGroupedBatchMax];
+    int64_t chunk_begin[kGroupedBatchMax + 1];
+    int count;
+};
+
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_batch_kernel(GroupedQuantBatchArgs a, QuantParams p0) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (c >= a.chunk_begin[a.count]) return;
+    int t = 0;
+    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    const int64_t numel = a.numel[t];
+    const int64_t ngroups = (numel + G - 1) / G;
+    const int64_t g0 = (c - a.chunk_begin[t]) * NG;
+    const bool full = (g0 + NG) * G <= numel;
+
+    u32x4 raw[NV];
+    grouped_load<DT_IN, NV>(a.in[t], numel, g0 * T::V, lane, full, raw);
+    grouped_quantize_chunk<DT_IN, BITS, MODE, G, GIVEN>(raw, a.out[t], numel, a.scales[t], a.zero_points[t], ngroups, p0, g0, full, lane, s_out[wave],
+                                                        s_a[wave], s_b[wave]);
+}
+
+// Fused reduce + quantize: out, scales, zero_points = quantize_grouped(acc + dequantize_grouped(in_0) + ... + dequantize_grouped(in_{k-1})), the terms
+// added in order with the running sum rounded to the accumulator's type after each one -- the bytes of k grouped dequantize ADD calls into acc
+// followed by quantize_grouped(acc), without the sum ever leaving the registers.  The terms are packed tensors of the same numel and group size,
+// each with its own per-group parameters (same G as the output groups).  A term's chunk is NV * 64 * OB contiguous bytes: staged through the
+// wave's LDS slice with coalesced 16-byte loads (the next term's in flight while the current one is added), read back as the OB packed bytes of
+// each of the lane's NV input vectors; lane j < NG loads group j's {scale, zero point}.
+constexpr int kGroupedReduceMaxTerms = 16;
+struct GroupedTerms {
+    const uint8_t* in[kGroupedReduceMaxTerms];
+    const float* scales[kGroupedReduceMaxTerms];
+    const uint8_t* zero_points[kGroupedReduceMaxTerms];
+    int count;
+};
+
+template <int DT_IN, int BITS, int G>
+struct GroupedTermLoad {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    static constexpr int LOB = T::LANE_OUT_BYTES;
+    static constexpr int N16 = LOB >= 16 ? LOB / 16 : 1;   // 16-byte loads per lane (one 8- or 4-byte load below 16)
+    u32x4 v[N16];
+    float scale, bias;
+    int32_t zp;
+
+    // full chunk: the lane's share of the chunk's packed bytes (coalesced) and, for lane j < NG, group j's parameters
+    __device__ __forceinline__ void load(const uint8_t* __restrict__ q, const float* __restrict__ sc, const uint8_t* __restrict__ zps, int64_t v0, int64_t gj,
+                                         bool has_group, int lane) {
+        const uint8_t* c = q + v0 * T::OB;
+        if constexpr (LOB >= 16) {
+#pragma unroll
+            for (int j = 0; j < N16; ++j) v[j] = ld<true>(reinterpret_cast<const u32x4*>(c) + j * 64 + lane);
+        } else if constexpr (LOB == 8) {
+            const u32x2 t = ld<true>(reinterpret_cast<const u32x2*>(c) + lane);
+            v[0] = u32x4 {t[0], t[1], 0u, 0u};
+        } else {
+            v[0] = u32x4 {ld<true>(reinterpret_cast<const uint32_t*>(c) + lane), 0u, 0u, 0u};
+        }
+        params(sc, zps, gj, has_group);
+    }
+
+    __device__ __forceinline__ void params(const float* __restrict__ sc, const uint8_t* __restrict__ zps, int64_t gj, bool has_group) {
+        if (has_group) {
+            scale = sc[gj];
+            zp = zps[gj];
+        }
+    }
+
+    __device__ __forceinline__ void park(uint8_t* stage, int lane) const {
+        if constexpr (LOB >= 16) {
+#pragma unroll
+            for (int j = 0; j < N16; ++j) reinterpret_cast<u32x4*>(stage)[j * 64 + lane] = v[j];
+        } else if constexpr (LOB == 8) {
+            reinterpret_cast<u32x2*>(stage)[lane] = u32x2 {v[0][0], v[0][1]};
+        } else {
+            reinterpret_cast<uint32_t*>(stage)[lane] = v[0][0];
+        }
+    }
+};
+
+// raw[r] (op)= the dequantized packed bytes of input vector r of the lane (ADD: rounded to DT_ACC after the add), group parameters per set
+template <int DT_ACC, int BITS, int G, int NV_ = GroupedQuantTile<DT_ACC, BITS, G>::NV>
+__device__ __forceinline__ void grouped_add_term(u32x4 (&raw)[NV_], const uint8_t* stage, const float* s_scale,
+                                                 const float* s_bias, const int32_t* s_zp, int lane) {
+    using T = GroupedQuantTile<DT_ACC, BITS, G>;
+    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
+    constexpr int FORM = DequantForm<BITS, DT_ACC>::value;
+    DequantParams p[SETS];
+#pragma unroll
+    for (int s = 0; s < SETS; ++s) {
+        const int slot = s * GPR + lane / LPG;
+        p[s] = DequantParams {};
+        p[s].scale = s_scale[slot];
+        p[s].bias = s_bias[slot];
+        p[s].zp32 = s_zp[slot];
+        p[s].zp64 = p[s].zp32;
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const uint8_t* src = stage + (r * 64 + lane) * OB;
+        uint32_t w[OB > 4 ? 2 : 1];
+        if constexpr (OB == 1) w[0] = *src;
+        else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
+        else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
+        else {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
+            w[0] = t[0];
+            w[1] = t[1];
+        }
+        float f[EPV];
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p[r / RPG]);
+        if constexpr (DT_ACC == DT_F32) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) raw[r][e] = __float_as_uint(__fadd_rn(f[e], __uint_as_float(raw[r][e])));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                raw[r][e] = f32x2_to_bf16x2_bits(__fadd_rn(f[2 * e], __uint_as_float(raw[r][e] << 16)),
+                                                 __fadd_rn(f[2 * e + 1], __uint_as_float(raw[r][e] & 0xffff0000u)));
+        }
+    }
+}
+
+template <int DT_ACC, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+reduce_quantize_grouped_kernel(const void* __restrict__ acc, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                               uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0, GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_ACC, BITS, G>;
+    using L = GroupedTermLoad<DT_ACC, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];
+    __shared__ int32_t s_z[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_out[wave];
+
+    u32x4 raw[NV];
+    L next;
+    if (full && terms.count > 0) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+    grouped_load<DT_ACC, NV>(acc, numel, v0, lane, full, raw);
+    for (int i = 0; i < terms.count; ++i) {
+        if (full) {
+            const L cur = next;
+            cur.park(stage, lane);
+            if (has_group) {
+                s_a[wave][lane] = cur.scale;
+                s_b[wave][lane] = __fmul_rn(-static_cast<float>(cur.zp), cur.scale);   // as resolved(DequantParams) forms it
+                s_z[wave][lane] = cur.zp;
+            }
+            if (i + 1 < terms.count) next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+        } else {
+            // the tensor ends inside this chunk: byte loads up to the term's last byte, zeros behind it (they meet quiet NaNs, which stay NaN)
+            const uint8_t* c = terms.in[i] + v0 * T::OB;
+            const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
+            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
+            if (has_group) {
+                const float scale = terms.scales[i][gj];
+                const int32_t zp = terms.zero_points[i][gj];
+                s_a[wave][lane] = scale;
+                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
+                s_z[wave][lane] = zp;
+            }
+        }
+        wave_lds_sync();
+        grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+        wave_lds_sync();
+    }
+    grouped_quantize_chunk<DT_ACC, BITS, MODE, G, false>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave]);
 }
 
 // Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element.  Correct, not fast.
@@ -288,23 +499,20 @@ struct GroupedDequantTile {
     static constexpr int OV = NIN * 16 / IB;                        // output vectors per lane
 };
 
-template <int BITS, int DT_OUT, int OP, int G>
-__global__ void __launch_bounds__(kGroupedBlock)
-dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
-                          const uint8_t* __restrict__ zero_points, int64_t ngroups) {
-    using T = GroupedDequantTile<BITS, DT_OUT>;
-    constexpr int EPV = T::EPV, IB = T::IB, PACK = T::PACK, WAVES = kGroupedBlock / 64;
-    constexpr int NGD = T::CHUNK_ELEMS >= G ? T::CHUNK_ELEMS / G : 1;   // groups per chunk (chunk and group sizes are powers of two)
-    constexpr int FORM = DequantForm<BITS, DT_OUT>::value;
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::CHUNK_BYTES];
-    __shared__ float s_scale[WAVES][NGD], s_bias[WAVES][NGD];
-    __shared__ int32_t s_zp[WAVES][NGD];
+template <int BITS, int DT_OUT, int G>
+struct GroupedDequantSlots {
+    static constexpr int value = GroupedDequantTile<BITS, DT_OUT>::CHUNK_ELEMS >= G ? GroupedDequantTile<BITS, DT_OUT>::CHUNK_ELEMS / G : 1;
+};
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    const int64_t e0 = chunk * T::CHUNK_ELEMS;
-    if (e0 >= numel) return;
+// Dequantize of the chunk that starts at element e0 (< numel); s_in / s_scale / s_bias / s_zp: the wave's LDS slices
+template <int BITS, int DT_OUT, int OP, int G>
+__device__ __forceinline__ void grouped_dequantize_chunk(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
+                                                         const uint8_t* __restrict__ zero_points, int64_t ngroups, int64_t e0, int lane, uint8_t* s_in,
+                                                         float* s_scale, float* s_bias, int32_t* s_zp) {
+    using T = GroupedDequantTile<BITS, DT_OUT>;
+    constexpr int EPV = T::EPV, IB = T::IB, PACK = T::PACK;
+    constexpr int NGD = GroupedDequantSlots<BITS, DT_OUT, G>::value;   // groups per chunk (chunk and group sizes are powers of two)
+    constexpr int FORM = DequantForm<BITS, DT_OUT>::value;
     const bool full = e0 + T::CHUNK_ELEMS <= numel;                 // wave-uniform
     const int64_t b0 = e0 / PACK, nbytes = (numel + PACK - 1) / PACK;
 
@@ -326,13 +534,13 @@ dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out
         if (gfirst + j < ngroups) {
             const float scale = scales[gfirst + j];
             const int32_t zp = zero_points[gfirst + j];
-            s_scale[wave][j] = scale;
-            s_bias[wave][j] = __fmul_rn(-static_cast<float>(zp), scale);   // as resolved(DequantParams) forms it
-            s_zp[wave][j] = zp;
+            s_scale[j] = scale;
+            s_bias[j] = __fmul_rn(-static_cast<float>(zp), scale);   // as resolved(DequantParams) forms it
+            s_zp[j] = zp;
         }
     }
 #pragma unroll
-    for (int k = 0; k < T::NIN; ++k) reinterpret_cast<u32x4*>(s_in[wave])[k * 64 + lane] = raw[k];
+    for (int k = 0; k < T::NIN; ++k) reinterpret_cast<u32x4*>(s_in)[k * 64 + lane] = raw[k];
     wave_lds_sync();
 
     u32x4* out16 = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(out) + e0 * (DT_OUT == DT_F32 ? 4 : 2));
@@ -343,12 +551,12 @@ dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out
         if (!full && e0 + ce >= numel) continue;
         const int slot = NGD > 1 ? ce / G : 0;
         DequantParams p {};
-        p.scale = s_scale[wave][slot];
-        p.bias = s_bias[wave][slot];
-        p.zp32 = s_zp[wave][slot];
+        p.scale = s_scale[slot];
+        p.bias = s_bias[slot];
+        p.zp32 = s_zp[slot];
         p.zp64 = p.zp32;
         uint32_t w[IB > 4 ? 2 : 1];
-        const uint8_t* src = s_in[wave] + c * IB;
+        const uint8_t* src = s_in + c * IB;
         if constexpr (IB == 1) w[0] = *src;
         else if constexpr (IB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
         else if constexpr (IB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
@@ -396,6 +604,56 @@ dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out
             }
         }
     }
+}
+
+template <int BITS, int DT_OUT, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
+                          const uint8_t* __restrict__ zero_points, int64_t ngroups) {
+    using T = GroupedDequantTile<BITS, DT_OUT>;
+    constexpr int WAVES = kGroupedBlock / 64, NGD = GroupedDequantSlots<BITS, DT_OUT, G>::value;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::CHUNK_BYTES];
+    __shared__ float s_scale[WAVES][NGD], s_bias[WAVES][NGD];
+    __shared__ int32_t s_zp[WAVES][NGD];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t e0 = chunk * T::CHUNK_ELEMS;
+    if (e0 >= numel) return;
+    grouped_dequantize_chunk<BITS, DT_OUT, OP, G>(in, out, numel, scales, zero_points, ngroups, e0, lane, s_in[wave], s_scale[wave], s_bias[wave], s_zp[wave]);
+}
+
+// Batch: up to kGroupedBatchMax independent tensors in ONE launch, the chunks of tensor t being [chunk_begin[t], chunk_begin[t + 1]) of the grid's
+// waves (as quantize_grouped_batch_kernel)
+struct GroupedDequantBatchArgs {
+    const uint8_t* in[kGroupedBatchMax];
+    void* out[kGroupedBatchMax];
+    const float* scales[kGroupedBatchMax];
+    const uint8_t* zero_points[kGroupedBatchMax];
+    int64_t numel[kGroupedBatchMax];
+    int64_t chunk_begin[kGroupedBatchMax + 1];
+    int count;
+};
+
+template <int BITS, int DT_OUT, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_batch_kernel(GroupedDequantBatchArgs a) {
+    using T = GroupedDequantTile<BITS, DT_OUT>;
+    constexpr int WAVES = kGroupedBlock / 64, NGD = GroupedDequantSlots<BITS, DT_OUT, G>::value;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::CHUNK_BYTES];
+    __shared__ float s_scale[WAVES][NGD], s_bias[WAVES][NGD];
+    __shared__ int32_t s_zp[WAVES][NGD];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (c >= a.chunk_begin[a.count]) return;
+    int t = 0;
+    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    const int64_t numel = a.numel[t];
+    grouped_dequantize_chunk<BITS, DT_OUT, OP, G>(a.in[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G,
+                                                  (c - a.chunk_begin[t]) * T::CHUNK_ELEMS, lane, s_in[wave], s_scale[wave], s_bias[wave], s_zp[wave]);
 }
 
 // Guarded form for buffers that are not 16-byte aligned: element by element.

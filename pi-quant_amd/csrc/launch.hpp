@@ -122,12 +122,70 @@ struct GroupedDequantLaunch {
     int op;                // OP_SET / OP_ADD
 };
 
+// Batches (up to kGroupedBatchMaxTensors tensors of one dtype pair, group size and round mode in ONE launch, every buffer 16-byte aligned and every
+// tensor non-empty: the caller sends anything else through the single calls) and the fused reduce + quantize (every buffer 16-byte aligned, at
+// most kGroupedReduceMaxInputs terms: the caller adds the surplus first, or runs the two-step form for misaligned buffers).
+constexpr int kGroupedBatchMaxTensors = 16;
+struct GroupedQuantBatchLaunch {
+    const void* in[kGroupedBatchMaxTensors];
+    void* out[kGroupedBatchMaxTensors];
+    float* scales[kGroupedBatchMaxTensors];
+    uint8_t* zero_points[kGroupedBatchMaxTensors];
+    int64_t numel[kGroupedBatchMaxTensors];
+    int count;
+    int64_t group_size;
+    bool params_given;
+    int dt_in;
+    int dt_out;
+    int round_mode;
+    float threshold;
+    uint64_t seed;
+    uint64_t index_base;
+};
+
+struct GroupedDequantBatchLaunch {
+    const void* in[kGroupedBatchMaxTensors];
+    void* out[kGroupedBatchMaxTensors];
+    const float* scales[kGroupedBatchMaxTensors];
+    const uint8_t* zero_points[kGroupedBatchMaxTensors];
+    int64_t numel[kGroupedBatchMaxTensors];
+    int count;
+    int64_t group_size;
+    int dt_in;
+    int dt_out;
+    int op;
+};
+
+// out, scales, zero_points = quantize_grouped(acc + sum_i dequantize_grouped(in[i], in_scales[i], in_zero_points[i])), terms added in order
+constexpr int kGroupedReduceMaxInputs = 16;
+struct GroupedReduceLaunch {
+    const void* acc;
+    void* out;
+    int64_t numel;
+    int64_t group_size;
+    float* scales;
+    uint8_t* zero_points;
+    const void* in[kGroupedReduceMaxInputs];
+    const float* in_scales[kGroupedReduceMaxInputs];
+    const uint8_t* in_zero_points[kGroupedReduceMaxInputs];
+    int count;
+    int dt_acc;            // DT_F32 / DT_BF16
+    int dt_out;            // DT_UINT2/4/8 (the terms' type too)
+    int round_mode;
+    float threshold;
+    uint64_t seed;
+    uint64_t index_base;
+};
+
 // All launches are asynchronous on `stream`; num_cu sizes capped grids.
 void launch_quantize(const QuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize(const DequantLaunch& d, hipStream_t stream, int num_cu);
 void launch_requantize(const RequantLaunch& r, hipStream_t stream, int num_cu);
 void launch_quantize_grouped(const GroupedQuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize_grouped(const GroupedDequantLaunch& d, hipStream_t stream, int num_cu);
+void launch_quantize_grouped_batch(const GroupedQuantBatchLaunch& b, hipStream_t stream);
+void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStream_t stream);
+void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -145,7 +145,9 @@ __device__ __forceinline__ uint32_t fold_keys(int32_t* keys, float lo, float hi)
 
 // Arms a scan state buffer: identity keys (+FLT_MAX for min and for -max), all arrival counters zero; with_gather != 0 (a
 // kMinmaxScanStateInts buffer, as opposed to the kMinmaxStateInts slot buffers inside the fused kernel's state) also empties the
-// per-block words of the gather end.
+// per-block words of the gather end.  (This kernel and minmax_epilogue_kernel are plain functions, defined by the one unit that launches
+// them, kernels.hip; other units that include the header for its device helpers define PQ_MINMAX_HELPERS_ONLY.)
+#ifndef PQ_MINMAX_HELPERS_ONLY
 __global__ void __launch_bounds__(64) arm_slots_kernel(int32_t* state, int with_gather) {
     if (threadIdx.x < kMinmaxSlots) {
         state[threadIdx.x * kMinmaxSlotStride + 0] = float_to_key(3.402823466e+38f);
@@ -158,6 +160,7 @@ __global__ void __launch_bounds__(64) arm_slots_kernel(int32_t* state, int with_
         for (int i = threadIdx.x; i < kMinmaxGatherMax; i += 64) words[i] = kMinmaxNotArrived;
     }
 }
+#endif
 
 // What a finished scan does with its folded key pair (lane 0 of the finishing wave).
 __device__ __forceinline__ void minmax_action(int32_t k0, int32_t k1, const MinmaxEpilogue& ep);
@@ -203,9 +206,11 @@ __device__ __forceinline__ void minmax_action(int32_t k0, int32_t k1, const Minm
 
 // The same as a kernel of its own, for slot buffers filled by EP_NONE scans (staged host input) and for empty inputs (an armed
 // buffer folds to the identities, reference kernels_specialized.inl:1422-1423).
+#ifndef PQ_MINMAX_HELPERS_ONLY
 __global__ void __launch_bounds__(64) minmax_epilogue_kernel(int32_t* state, MinmaxEpilogue ep, int rearm) {
     minmax_finish(state, static_cast<int>(threadIdx.x), ep, rearm != 0);
 }
+#endif
 
 // End of a scan block.  Wave 0: lane 0 folds the block's extremes into its slot and -- unless the scan leaves the keys in
 // the slots (EP_NONE) -- counts the block in: per slot first (blocks b with b % 64 == slot), and the block that completes a

@@ -437,6 +437,45 @@ class Context:
         C.piquant_hip_dequantize_grouped(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
                                          reduce_op.value)
 
+    def quantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
+                                   zero_points_ptrs, params_given: bool, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_ptr`` for several independent tensors (own parameter arrays each), up to 16 per kernel launch
+        (``piquant_hip_quantize_grouped_batch``); one stochastic threshold for the batch."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and dtype_out.is_quantized and n == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
+                                             (_C.c_size_t * n)(*numels), group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
+                                             1 if params_given else 0, round_mode.value)
+
+    def dequantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
+                                     zero_points_ptrs, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """``dequantize_grouped_ptr`` for several independent tensors, up to 16 per kernel launch (``piquant_hip_dequantize_grouped_batch``)."""
+        n = len(ptrs_in)
+        assert dtype_in.is_quantized and dtype_out.is_dequantized and n == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
+                                               (_C.c_size_t * n)(*numels), group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
+                                               reduce_op.value)
+
+    def reduce_quantize_grouped_ptr(self, ptr_acc: int, dtype_acc: DataType, ptrs_in, scales_in, zero_points_in, ptr_out: int, dtype_out: DataType,
+                                    numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
+                                    _device_ptrs: bool = False) -> None:
+        """out, scales, zero_points = quantize_grouped(acc + sum_i dequantize_grouped(input i)), input i with its own per-group parameters
+        (``piquant_hip_reduce_quantize_grouped``: one launch for up to 16 terms); the inputs have type ``dtype_out``.  ``acc`` is unspecified
+        afterwards."""
+        n = len(ptrs_in)
+        assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
+        self.assume_device_pointers(_device_ptrs)
+        m = max(n, 1)
+        C.piquant_hip_reduce_quantize_grouped(self._ctx, ptr_acc, dtype_acc.value, (_C.c_void_p * m)(*ptrs_in), (_C.c_void_p * m)(*scales_in),
+                                              (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+                                              round_mode.value)
+
     def compute_quant_params_dist_ptr(self, ptr: int, dtype: DataType, numel: int, target_quant_dtype: DataType, nccl_comm: int,
                                       _device_ptrs: bool = False) -> Tuple[float, int]:
         """Sharded ``compute_quant_params`` with the all-reduce done natively: ``nccl_comm`` is an ``ncclComm_t`` (RCCL)."""

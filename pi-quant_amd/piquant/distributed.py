@@ -10,7 +10,7 @@ over pool threads (``src/piquant.cpp:132-176``).  Here the same split rule shard
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -398,6 +398,24 @@ class _KeyMesh:
 _HEADER_BYTES = 16   # wire header per hop == the device parameter record {float scale, float 1/scale, int64 zero_point}
 
 
+class GroupedWireLayout(NamedTuple):
+    """One chunk's record on the grouped wire: ``float32 scales[ngroups] | uint8 zero_points[ngroups] | pad to 16 | packed bytes``."""
+    ngroups: int
+    zero_points_offset: int
+    data_offset: int         # 16-byte aligned: the packed bytes start on a vector boundary of the kernels
+    nbytes: int              # the whole record (scales, zero points, padding, packed bytes)
+
+
+def grouped_wire_layout(numel: int, group_size: int, packed_bits: int) -> GroupedWireLayout:
+    """Layout of the grouped wire record of a chunk of ``numel`` elements (``quantized_all_reduce(group_size=...)``): ngroups = ceil(numel /
+    group_size) float32 scales, then as many uint8 zero points, zero padding up to a multiple of 16 bytes, then the packed bytes (``packed_bits``
+    per element, whole bytes).  The record of an empty chunk is empty."""
+    ngroups = -(-int(numel) // int(group_size))
+    zp = 4 * ngroups
+    data = -(-(zp + ngroups) // 16) * 16
+    return GroupedWireLayout(ngroups, zp, data, data + -(-int(numel) * int(packed_bits) // 8))
+
+
 class _DeviceOps:
     """Wire encode / decode on ROCm device tensors (HIP kernels through libpiquant.so).  The parameters are derived on
     the device straight into the buffer's header and read back from it by the receiver's dequantize kernel: a hop
@@ -465,6 +483,53 @@ class _DeviceOps:
         ps = [b.data_ptr() for b in bufs]
         self._cx(out).dequantize_sum_ptr([p + _HEADER_BYTES for p in ps], ps, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype),
                                          out.numel(), ReduceOp.ADD, _device_ptrs=True)
+
+    # ---- the grouped wire (grouped_wire_layout): per-group parameters in front of the packed bytes ----
+    @staticmethod
+    def _record(buf: torch.Tensor, numel: int, qdtype: torch.dtype, group_size: int):
+        """(scales, zero points, packed bytes) addresses of the grouped record in ``buf``"""
+        lay = grouped_wire_layout(numel, group_size, torch_to_piquant_dtype(qdtype).bit_size)
+        p = buf.data_ptr()
+        return p, p + lay.zero_points_offset, p + lay.data_offset
+
+    def encode_grouped(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
+        sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
+        self._cx(x).quantize_grouped_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), data, torch_to_piquant_dtype(qdtype), x.numel(), group_size, sc, zp,
+                                         False, self._mode(round_mode), _device_ptrs=True)
+
+    def decode_grouped(self, buf: torch.Tensor, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
+        from . import ReduceOp
+
+        sc, zp, data = self._record(buf, out.numel(), qdtype, group_size)
+        self._cx(out).dequantize_grouped_ptr(data, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype), out.numel(), group_size,
+                                             sc, zp, ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+
+    def encode_batch_grouped(self, xs, bufs, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
+        """encode_grouped(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_grouped_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r[2] for r in recs],
+                                                       torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
+                                                       [r[1] for r in recs], False, self._mode(round_mode), _device_ptrs=True)
+
+    def decode_batch_grouped(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
+        """decode_grouped(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
+        from . import ReduceOp
+
+        if bufs:
+            recs = [self._record(b, o.numel(), qdtype, group_size) for b, o in zip(bufs, outs)]
+            self._cx(outs[0]).dequantize_grouped_batch_ptr([r[2] for r in recs], torch_to_piquant_dtype(qdtype), [o.data_ptr() for o in outs],
+                                                           torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], group_size, [r[0] for r in recs],
+                                                           [r[1] for r in recs], ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+
+    def reduce_encode_grouped(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
+        """encode_grouped(acc + the wire buffers, added in order) into ``buf`` as one launch (``acc`` is scratch afterwards)."""
+        n = acc.numel()
+        recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+        sc, zp, data = self._record(buf, n, qdtype, group_size)
+        self._cx(acc).reduce_quantize_grouped_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [r[2] for r in recs], [r[0] for r in recs],
+                                                  [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp, self._mode(round_mode),
+                                                  _device_ptrs=True)
 
 
 def _exchange(send: torch.Tensor, recv: torch.Tensor, nxt: int, prv: int, group) -> None:
@@ -602,10 +667,21 @@ def quantized_all_reduce(
     algorithm: str = 'direct',
     transport: str = 'collective',
     timeout: Optional[float] = None,
+    group_size: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
     """In-place SUM all-reduce of a contiguous float32/bfloat16 tensor whose wire format is quantized.
+
+    ``group_size`` (None, or a power of two in [32, 4096]; 128 is the usual choice): None quantizes every chunk of the wire with one
+    (scale, zero point) in a 16-byte header.  An int quantizes group-wise -- one (scale, zero point) per run of ``group_size`` elements, so
+    that an outlier stretches the range of its own group only -- and a chunk's record becomes ``float32 scales[ng] | uint8 zero_points[ng] |
+    pad to 16 | packed bytes`` (``grouped_wire_layout``; 5 bytes more per group).  ``ring_chunks`` puts every interior chunk boundary on a
+    multiple of 4096 elements, so no group straddles two chunks: the wire groups are exactly the groups ``quantize_grouped`` forms on the
+    whole tensor.  Every encode is ``quantize_grouped`` (the mesh's: one batched launch), every re-quantization of a partial sum is ONE
+    ``reduce_quantize_grouped`` launch, every decode ``dequantize_grouped`` (the mesh's: one batched launch); the schedules, the launches
+    per all-reduce and the bit-identity of all ranks are those of the per-chunk path.  ``transport='p2p'`` does not take grouped
+    parameters.  (Unmeasured on more than one GPU, like the rest of this module's multi-GPU paths.)
 
     ``transport='p2p'`` (``algorithm='direct'`` only, one node; EXPERIMENTAL until it has run between two GPUs): no collective at all -- the
     encode kernels store into the peers' receive buffers over xGMI and flags order the steps (``quantized_all_reduce_direct``).  ``timeout``
@@ -640,9 +716,10 @@ def quantized_all_reduce(
         raise ValueError(f"algorithm must be 'ring' or 'direct', got {algorithm!r}")
     if transport not in ('collective', 'p2p'):
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
+    _check_all_reduce_group_size(group_size, transport)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
-                                           _ops=_ops, _single_rank_collectives=_single_rank_collectives)
+                                           group_size=group_size, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
@@ -655,6 +732,8 @@ def quantized_all_reduce(
     chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
     nxt = dist.get_global_rank(group, (rank + 1) % world) if group is not None else (rank + 1) % world
     prv = dist.get_global_rank(group, (rank - 1) % world) if group is not None else (rank - 1) % world
+    if group_size is not None:
+        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size)
     max_bytes = max(qdt.packed_nbytes(e - b) for b, e in chunks) + _HEADER_BYTES
     send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
@@ -707,6 +786,7 @@ def quantized_all_reduce_direct(
     ctx: Optional[Context] = None,
     transport: str = 'collective',
     timeout: Optional[float] = None,
+    group_size: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -731,9 +811,14 @@ def quantized_all_reduce_direct(
     chunks from their owners.  Against the collective transport that is one HBM write and one read of the wire bytes less per phase on every
     rank, no staging copy inside RCCL and no RCCL launch: 4 kernel launches + 2 flag stores + 2 flag waits per all-reduce.  One node only
     (IPC-mapped device memory); results are bit-identical to the collective transport (tests/test_gpu_distributed.py).
+
+    ``group_size``: group-wise parameters on the wire (``quantized_all_reduce``); step 1 is one batched ``quantize_grouped`` launch, steps 3-4
+    one ``reduce_quantize_grouped`` launch over the G-1 received chunks in increasing rank order, the decode one batched ``dequantize_grouped``
+    launch.  Collective transport only.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
+    _check_all_reduce_group_size(group_size, transport)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
@@ -750,6 +835,8 @@ def quantized_all_reduce_direct(
         return _all_reduce_direct_p2p(tensor, flat, chunks, slot, quant_dtype, qdt, round_mode, group, ctx, ops, world, rank, _p2p_timeout_us(timeout))
     if transport != 'collective':
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
+    if group_size is not None:
+        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size)
     send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
 
@@ -774,6 +861,85 @@ def quantized_all_reduce_direct(
     recv = gathered
     full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
     ops.decode_batch([recv[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set')
+    return tensor
+
+
+def _check_all_reduce_group_size(group_size, transport: str) -> None:
+    """ValueError before anything moves: an invalid group size, or grouped parameters over the peer-to-peer transport."""
+    if group_size is None:
+        return
+    from .torch import _check_group_size
+
+    _check_group_size(group_size)
+    if transport == 'p2p':
+        raise ValueError("group_size= is not supported with transport='p2p' (its peer-mapped slots carry the per-chunk record); use transport='collective'")
+
+
+def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size):
+    """The ring of ``quantized_all_reduce`` on the grouped wire: the same hops with quantize_grouped / reduce_quantize_grouped (one term) /
+    dequantize_grouped (SET) in place of the per-chunk calls."""
+    def wire(idx):
+        b, e = chunks[idx]
+        return flat[b:e], grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
+
+    max_bytes = max(wire(i)[1] for i in range(world))
+    send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
+    recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
+    nxt_send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
+    # ---- reduce-scatter ----
+    x_first, n_cur = wire(rank)
+    if x_first.numel():
+        ops.encode_grouped(x_first, send[:n_cur], quant_dtype, round_mode, group_size)
+    for step in range(world - 1):
+        x_recv, n_recv = wire((rank - step - 1) % world)
+        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
+        if x_recv.numel():
+            ops.reduce_encode_grouped([recv[:n_recv]], x_recv, nxt_send[:n_recv], quant_dtype, round_mode, group_size)
+        send, nxt_send = nxt_send, send
+        n_cur = n_recv
+    if world == 1 and n_cur:   # test hook only: the encoded chunk makes one trip through the transport, to this rank itself
+        _exchange(send[:n_cur], recv[:n_cur], nxt, prv, group)
+        send, recv = recv, send
+    # ---- all-gather ----
+    x_own, n_own = wire((rank + 1) % world)
+    if x_own.numel():
+        ops.decode_grouped(send[:n_own], x_own, quant_dtype, 'set', group_size)
+    for step in range(world - 1):
+        x_recv, n_recv = wire((rank - step) % world)
+        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
+        if x_recv.numel():
+            ops.decode_grouped(recv[:n_recv], x_recv, quant_dtype, 'set', group_size)
+        send, recv = recv, send
+        n_cur = n_recv
+    return tensor
+
+
+def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size):
+    """The mesh schedule of ``quantized_all_reduce_direct`` on the grouped wire: one batched quantize_grouped, the all-to-all, ONE
+    reduce_quantize_grouped over the G-1 received chunks (increasing rank order), the all-gather, one batched dequantize_grouped."""
+    def wire_len(idx):
+        b, e = chunks[idx]
+        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
+
+    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16   # every slot starts on a 16-byte boundary (vector kernels on both sides)
+    send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
+    recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
+    peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
+    ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
+                             round_mode, group_size)
+    _all_to_all(send, recv, group)
+    b_own, e_own = chunks[rank]
+    x_own = flat[b_own:e_own]
+    n_own = wire_len(rank)
+    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
+    if x_own.numel():
+        ops.reduce_encode_grouped([recv[i * slot: i * slot + n_own] for i in range(world) if i != rank], x_own, mine[:n_own], quant_dtype, round_mode,
+                                  group_size)
+    gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)   # not `recv`: the launch above is still reading it
+    _all_gather(mine, gathered, group)
+    full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
+    ops.decode_batch_grouped([gathered[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set',
+                             group_size)
     return tensor
 
 

@@ -478,6 +478,131 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
                                zero_points.data_ptr(), _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return out
 
+def reduce_quantize_grouped(acc: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
+                            ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
+                            out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``quantize_grouped(acc + dequantize_grouped(tensors[0]) + ... + dequantize_grouped(tensors[k - 1]))`` in one launch (up to 16 terms) that
+    never stores the sum.  Term i is a packed tensor of ``dtype`` (or the raw uint8 buffer of its bytes) with ``acc.numel()`` elements and its
+    own per-group ``scales[i]`` / ``zero_points[i]`` (same ``group_size``).  The bytes, scales and zero points are exactly those of
+    ``dequantize_grouped(tensors[i], ..., reduce_op='add', out=acc)`` for every i in order followed by ``quantize_grouped(acc)``.  Returns
+    (out, out_scales, out_zero_points) as ``quantize_grouped`` does; ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
+    piquant_hip_reduce_quantize_grouped)."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
+             f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
+    _check_float_input(acc, 'acc')
+    _require(acc.is_contiguous(), 'acc must be contiguous (it is the accumulator)')
+    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    numel = acc.numel()
+    ngroups = num_groups(numel, group_size)
+    qdt = torch_to_piquant_dtype(dtype)
+    for i, (t, sc, zp) in enumerate(zip(tensors, scales, zero_points)):
+        _check_packed_in(t, qdt, numel, acc.device, f'tensors[{i}]')
+        _check_group_params(sc, zp, ngroups)
+        _require(sc.device == acc.device and zp.device == acc.device, f'scales[{i}] and zero_points[{i}] must live on {acc.device}')
+    if out is None:
+        out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
+    else:
+        _check_packed_out(out, qdt, numel, acc.device)
+    if out_scales is None:
+        out_scales = torch.empty(ngroups, dtype=torch.float32, device=acc.device)
+        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=acc.device)
+    else:
+        _check_group_params(out_scales, out_zero_points, ngroups)
+        _require(out_scales.device == acc.device and out_zero_points.device == acc.device, f'out_scales and out_zero_points must live on {acc.device}')
+    ctx = _ctx_for(acc, ctx)
+    ctx.reduce_quantize_grouped_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [t.data_ptr() for t in tensors], [sc.data_ptr() for sc in scales],
+                                    [zp.data_ptr() for zp in zero_points], out.data_ptr(), qdt, numel, group_size, out_scales.data_ptr(),
+                                    out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, out_scales, out_zero_points
+
+
+def _check_batch_lists(*lists) -> None:
+    _require(len(lists[0]) > 0, 'the batch is empty')
+    _require(all(len(x) == len(lists[0]) for x in lists), f'the lists of a batch must have the same length, got {[len(x) for x in lists]}')
+
+
+def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
+                           outs=None, scales=None, zero_points=None):
+    """``quantize_grouped`` of several independent tensors (one dtype pair, group size and round mode) with one kernel launch per 16 tensors.
+    Returns (outs, scales, zero_points) as lists; tensor i's entries equal ``quantize_grouped(tensors[i])`` (a stochastic batch draws one
+    threshold).  Passing ``scales`` and ``zero_points`` (lists) quantizes with those parameters instead of computing them."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
+    tensors = list(tensors)
+    given = scales is not None
+    lists = [tensors] + ([list(outs)] if outs is not None else []) + ([list(scales), list(zero_points)] if given else [])
+    _check_batch_lists(*lists)
+    for i, t in enumerate(tensors):
+        _check_float_input(t, f'tensors[{i}]')
+        _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
+    device = tensors[0].device
+    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    qdt = torch_to_piquant_dtype(dtype)
+    if given:
+        scales, zero_points = list(scales), list(zero_points)
+        for sc, zp, t in zip(scales, zero_points, tensors):
+            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
+            _require(sc.device == device and zp.device == device, f'scales and zero_points must live on {device}')
+    else:
+        scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
+        zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
+    if outs is None:
+        outs = [torch.empty(t.shape, dtype=dtype, device=device) for t in tensors]
+    else:
+        outs = list(outs)
+        for i, (o, t) in enumerate(zip(outs, tensors)):
+            _check_packed_out(o, qdt, t.numel(), device, f'outs[{i}]')
+    ctx = _ctx_for(tensors[0], ctx)
+    ctx.quantize_grouped_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [o.data_ptr() for o in outs], qdt,
+                                   [t.numel() for t in tensors], group_size, [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], given,
+                                   _ROUND_MODES[round_mode], _device_ptrs=True)
+    return outs, scales, zero_points
+
+
+def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, reduce_op: str = 'set', ctx: Optional[Context] = None,
+                             outs=None, quant_dtype: Optional[torch.dtype] = None, shapes=None):
+    """``dequantize_grouped`` of several independent tensors with one kernel launch per 16 tensors; returns the list of outputs.  Raw uint8
+    buffers of packed bytes need ``quant_dtype=`` and ``shapes=`` (one shape per tensor); ``reduce_op='add'`` accumulates into ``outs``."""
+    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
+    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
+    _check_group_size(group_size)
+    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    lists = [tensors, scales, zero_points] + ([list(outs)] if outs is not None else []) + ([list(shapes)] if shapes is not None else [])
+    _check_batch_lists(*lists)
+    if reduce_op == 'add':
+        _require(outs is not None, "reduce_op='add' accumulates into outs=; pass the accumulator tensors")
+    metas = []
+    for i, t in enumerate(tensors):
+        _require(isinstance(t, torch.Tensor) and (t.dtype in _QUANT_TYPES or quant_dtype is not None), f'tensors[{i}] must be a quantized tensor')
+        _require(t.is_cuda, 'dequantize_grouped_batch needs ROCm device tensors')
+        metas.append(_quant_meta(t, quant_dtype, shapes[i] if shapes is not None else None))
+    device = tensors[0].device
+    _require(all(t.device == device for t in tensors) and all(m[0] == metas[0][0] for m in metas), 'the tensors of a batch must share one device and one dtype')
+    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    numels = [_numel_of(shape) for _, shape in metas]
+    for i, (t, sc, zp, (dt_in, _), n) in enumerate(zip(tensors, scales, zero_points, metas, numels)):
+        _check_packed_in(t, dt_in, n, device, f'tensors[{i}]')
+        _check_group_params(sc, zp, num_groups(n, group_size))
+        _require(sc.device == device and zp.device == device, f'scales and zero_points must live on {device}')
+    if outs is None:
+        outs = [torch.empty(shape, dtype=dtype, device=device) for _, shape in metas]
+    else:
+        outs = list(outs)
+        for i, (o, n) in enumerate(zip(outs, numels)):
+            _check_float_out(o, dtype, n, device, f'outs[{i}]')
+    ctx = _ctx_for(tensors[0], ctx)
+    ctx.dequantize_grouped_batch_ptr([t.data_ptr() for t in tensors], metas[0][0], [o.data_ptr() for o in outs], torch_to_piquant_dtype(dtype), numels,
+                                     group_size, [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], _REDUCE_OPS[reduce_op],
+                                     _device_ptrs=True)
+    return outs
+
+
 def dequantize_sum(tensors, params, *, dtype: torch.dtype, reduce_op: str = 'set', ctx: Optional[Context] = None,
                    out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
     """out (op)= sum_i dequantize(tensors[i]) with (scale, zero_point) of input i read from the device record ``params[i]``: one pass

@@ -2,8 +2,10 @@
 """Per-rank KERNEL time of a quantized all-reduce (no wire): the sequence of encode / decode / dequantize_sum calls one rank
 issues for a `world`-way all-reduce of an fp32 tensor, replayed on one GPU with stand-in receive buffers.  Shows what the
 schedules cost in HBM time next to the xGMI transfer time they overlap with (per-link ~153 GB/s, guides/MI355X_MICROARCH.md).
+With --group-size G the same rank's schedules on the grouped wire (quantized_all_reduce(group_size=G): quantize_grouped, reduce_quantize_grouped,
+dequantize_grouped and their batches) are replayed in the same run, next to the per-chunk-parameter ones.
 
-  python tools/all_reduce_compute_cost.py [--numel 27264000] [--world 8]
+  python tools/all_reduce_compute_cost.py [--numel 27264000] [--world 8] [--group-size 128] [--out FILE]
 """
 import argparse
 import json
@@ -25,6 +27,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--numel", type=int, default=27_264_000)
     ap.add_argument("--world", type=int, default=8)
+    ap.add_argument("--group-size", type=int, default=None)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     W, n = args.world, args.numel
     dev = torch.device("cuda")
@@ -55,35 +59,69 @@ def main():
             ops.reduce_encode([bufs[i * slot: i * slot + nbytes[0]] for i in range(1, W)], x[chunks[0][0]:chunks[0][1]], mine[: nbytes[0]], qdt, "nearest")
             ops.decode_batch([bufs[j * slot: j * slot + nbytes[j]] for j in range(W)], [x[chunks[j][0]:chunks[j][1]] for j in range(W)], qdt, "set")
 
+        schedules = [("", ring, direct, max(nbytes))]
+        G = args.group_size
+        if G is not None:
+            gbytes = [D.grouped_wire_layout(e - b, G, bits).nbytes for b, e in chunks]
+            gslot = -(-max(gbytes) // 16) * 16
+            gbufs = torch.zeros(W * gslot, dtype=torch.uint8, device=dev)
+            gmine = torch.zeros(gslot, dtype=torch.uint8, device=dev)
+            for j, (b, e) in enumerate(chunks):
+                ops.encode_grouped(x[b:e], gbufs[j * gslot: j * gslot + gbytes[j]], qdt, "nearest", G)
+
+            def ring_grouped():
+                ops.encode_grouped(x[chunks[0][0]:chunks[0][1]], gbufs[0: gbytes[0]], qdt, "nearest", G)
+                for step in range(W - 1):
+                    r = (0 - step - 1) % W
+                    ops.reduce_encode_grouped([gbufs[r * gslot: r * gslot + gbytes[r]]], x[chunks[r][0]:chunks[r][1]], gmine[: gbytes[r]], qdt, "nearest", G)
+                for j in range(W):
+                    ops.decode_grouped(gbufs[j * gslot: j * gslot + gbytes[j]], x[chunks[j][0]:chunks[j][1]], qdt, "set", G)
+
+            def direct_grouped():
+                peers = list(range(1, W))
+                ops.encode_batch_grouped([x[chunks[j][0]:chunks[j][1]] for j in peers], [gbufs[j * gslot: j * gslot + gbytes[j]] for j in peers], qdt,
+                                         "nearest", G)
+                ops.reduce_encode_grouped([gbufs[i * gslot: i * gslot + gbytes[0]] for i in range(1, W)], x[chunks[0][0]:chunks[0][1]], gmine[: gbytes[0]],
+                                          qdt, "nearest", G)
+                ops.decode_batch_grouped([gbufs[j * gslot: j * gslot + gbytes[j]] for j in range(W)], [x[chunks[j][0]:chunks[j][1]] for j in range(W)],
+                                         qdt, "set", G)
+
+            schedules.append((f"grouped{G}_", ring_grouped, direct_grouped, max(gbytes)))
+
         row = {}
-        for name, fn in (("ring", ring), ("direct", direct)):
-            x.uniform_(-1, 1)
-            for _ in range(3):
-                fn()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream()
-            with torch.cuda.stream(s):
-                fn()
-                torch.cuda.synchronize()
-                with torch.cuda.graph(g, stream=s):
+        for prefix, ring_fn, direct_fn, chunk_wire in schedules:
+            for name, fn in (("ring", ring_fn), ("direct", direct_fn)):
+                x.uniform_(-1, 1)
+                for _ in range(3):
                     fn()
-                g.replay()
                 torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(20):
+                g = torch.cuda.CUDAGraph()
+                s = torch.cuda.Stream()
+                with torch.cuda.stream(s):
+                    fn()
+                    torch.cuda.synchronize()
+                    with torch.cuda.graph(g, stream=s):
+                        fn()
                     g.replay()
-                e1.record()
-                torch.cuda.synchronize()
-            row[name + "_kernel_us_per_all_reduce"] = round(e0.elapsed_time(e1) * 1e3 / 20, 1)
-            x.uniform_(-1, 1)                        # values drift under repeated accumulation; irrelevant for timing
-        chunk_wire = max(nbytes)
-        row["wire_bytes_per_rank"] = 2 * (W - 1) * chunk_wire
-        row["xgmi_us_ring_one_link_153GBps"] = round(2 * (W - 1) * chunk_wire / 153e9 * 1e6, 1)
-        row["xgmi_us_mesh_all_links"] = round(2 * chunk_wire / 153e9 * 1e6, 1)
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(20):
+                        g.replay()
+                    e1.record()
+                    torch.cuda.synchronize()
+                row[prefix + name + "_kernel_us_per_all_reduce"] = round(e0.elapsed_time(e1) * 1e3 / 20, 1)
+                x.uniform_(-1, 1)                        # values drift under repeated accumulation; irrelevant for timing
+            row[prefix + "wire_bytes_per_rank"] = 2 * (W - 1) * chunk_wire
+            row[prefix + "xgmi_us_ring_one_link_153GBps"] = round(2 * (W - 1) * chunk_wire / 153e9 * 1e6, 1)
+            row[prefix + "xgmi_us_mesh_all_links"] = round(2 * chunk_wire / 153e9 * 1e6, 1)
+        if G is not None:
+            row["grouped_direct_over_per_chunk"] = round(row[f"grouped{G}_direct_kernel_us_per_all_reduce"] / row["direct_kernel_us_per_all_reduce"], 3)
+            row["grouped_wire_over_per_chunk"] = round(row[f"grouped{G}_wire_bytes_per_rank"] / row["wire_bytes_per_rank"], 4)
         out[qname] = row
     print(json.dumps(out, indent=1))
+    if args.out:
+        Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
 
 
 if __name__ == "__main__":

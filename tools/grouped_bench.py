@@ -6,7 +6,11 @@ windows of back-to-back calls, the median of several windows.  Rows: every quant
 against scan + quantize (compute_quant_params_device -> quantize_dp, two launches); every dequantize pair at G = 128 against dequantize_uniform.
 Each row gives us per call, algorithmic bytes (the 5 bytes per group included) and the fraction of 8 TB/s.  Writes profiles/grouped_bench.json.
 
-    python tools/grouped_bench.py [--windows 7] [--rotate-gb 3.3] [--out profiles/grouped_bench.json]
+--rows reduce: the fused reduce_quantize_grouped (fp32 acc, uint8 and uint4 terms, k = 1 and k = 7, G = 128) next to its two-step composition
+(k grouped dequantize ADD launches + quantize_grouped) in the same run, and the batched grouped quantize (7 chunks) / dequantize (8 chunks) of
+an 8-way mesh next to as many single calls.  Writes profiles/grouped_reduce_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -54,12 +58,98 @@ def row(kind, pair, g, us, nbytes, samples):
     return r
 
 
+def reduce_rows(ctx, dev, stream, args, G=128, world=8):
+    """fused reduce + quantize against its two-step composition, batched calls against single calls (fp32, G = 128)"""
+    fdt, esize = piquant.DataType.F32, 4
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(2)
+    for qname in ("uint8", "uint4"):
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(NUMEL)
+        for k in (1, 7):
+            per_call = NUMEL * esize + k * (nq + 5 * ng) + nq + 5 * ng
+            nbuf = max(3, int(args.rotate_gb * 1e9 / per_call) + 1)
+            accs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g) for _ in range(nbuf)]
+            terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+            tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+            tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+            outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+            zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            per_window = max(2 * nbuf, 32)
+
+            def fused(i):
+                ctx.reduce_quantize_grouped_ptr(accs[i].data_ptr(), fdt, [t.data_ptr() for t in terms[i]], [t.data_ptr() for t in tsc[i]],
+                                                [t.data_ptr() for t in tzp[i]], outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                                piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            def two_step(i):
+                for t, s_, z_ in zip(terms[i], tsc[i], tzp[i]):
+                    ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, accs[i].data_ptr(), fdt, NUMEL, G, s_.data_ptr(), z_.data_ptr(), piquant.ReduceOp.ADD,
+                                               _device_ptrs=True)
+                ctx.quantize_grouped_ptr(accs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                         piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            pair = f"f32+{k}x{qname}"
+            us_t, s_t = timed(two_step, nbuf, args.windows, per_window, stream)
+            two = row("reduce_two_step", pair, G, us_t, NUMEL * esize * (2 * k + 1) + k * (nq + 5 * ng) + nq + 5 * ng, s_t)
+            us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+            fr = row("reduce_quantize_grouped", pair, G, us_f, per_call, s_f)
+            fr["over_two_step"] = round(us_f / us_t, 3)
+            print(f"    fused / two-step = {fr['over_two_step']:.3f}", flush=True)
+            rows += [two, fr]
+            del accs, terms, tsc, tzp, outs, sc, zs
+            torch.cuda.empty_cache()
+        # the mesh's batches: world - 1 chunks quantized, world chunks dequantized, each of NUMEL / world elements
+        per = NUMEL // world
+        xs = [torch.empty(per, device=dev).uniform_(-1, 1, generator=g) for _ in range(world)]
+        qs = [torch.empty(qdt.packed_nbytes(per), dtype=torch.uint8, device=dev) for _ in range(world)]
+        gs = pt.num_groups(per, G)
+        sc = [torch.empty(gs, dtype=torch.float32, device=dev) for _ in range(world)]
+        zs = [torch.empty(gs, dtype=torch.uint8, device=dev) for _ in range(world)]
+        ys = [torch.empty(per, device=dev) for _ in range(world)]
+        m = world - 1
+
+        def qbatch(_):
+            ctx.quantize_grouped_batch_ptr([x.data_ptr() for x in xs[:m]], fdt, [q.data_ptr() for q in qs[:m]], qdt, [per] * m, G,
+                                           [t.data_ptr() for t in sc[:m]], [t.data_ptr() for t in zs[:m]], False, piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def qsingles(_):
+            for j in range(m):
+                ctx.quantize_grouped_ptr(xs[j].data_ptr(), fdt, qs[j].data_ptr(), qdt, per, G, sc[j].data_ptr(), zs[j].data_ptr(), False,
+                                         piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def dbatch(_):
+            ctx.dequantize_grouped_batch_ptr([q.data_ptr() for q in qs], qdt, [y.data_ptr() for y in ys], fdt, [per] * world, G, [t.data_ptr() for t in sc],
+                                             [t.data_ptr() for t in zs], piquant.ReduceOp.SET, _device_ptrs=True)
+
+        def dsingles(_):
+            for j in range(world):
+                ctx.dequantize_grouped_ptr(qs[j].data_ptr(), qdt, ys[j].data_ptr(), fdt, per, G, sc[j].data_ptr(), zs[j].data_ptr(), piquant.ReduceOp.SET,
+                                           _device_ptrs=True)
+
+        qb = m * (per * esize + qdt.packed_nbytes(per) + 5 * gs)
+        db = world * (per * esize + qdt.packed_nbytes(per) + 5 * gs)
+        for kind, fn, nbytes in ((f"quantize_grouped x{m} single", qsingles, qb), (f"quantize_grouped_batch {m}", qbatch, qb),
+                                 (f"dequantize_grouped x{world} single", dsingles, db), (f"dequantize_grouped_batch {world}", dbatch, db)):
+            us, s_ = timed(fn, 1, args.windows, 32, stream)
+            rows.append(row(kind, f"f32<->{qname}", G, us, nbytes, s_))
+        del xs, qs, sc, zs, ys
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "grouped_bench.json"))
+    ap.add_argument("--rows", choices=("all", "reduce"), default="all")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("grouped_bench.json" if args.rows == "all" else "grouped_reduce_bench.json"))
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -69,7 +159,9 @@ def main():
     ctx.set_blocking(False)
     ctx.assume_device_pointers(True)
     rows = []
-    for fname, (fdt, tdt, esize) in FLOAT.items():
+    if args.rows == "reduce":
+        rows = reduce_rows(ctx, dev, stream, args)
+    for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
         g.manual_seed(1)
