@@ -204,6 +204,36 @@ PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, 
                                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
                                                         piquant_round_mode_t mode);
 
+/* Error feedback for the group-wise wire: a lossy gradient / pseudo-gradient all-reduce keeps the rounding error of every step and adds it to the
+ * next step's input instead of throwing it away.  `residual` has the input's type (dtype_in: float32 or bfloat16) and numel elements; it is read
+ * AND written.  With T that type, for every element i < numel:
+ *   1. y[i] = x[i] + residual[i], rounded to nearest in T (bfloat16: both widened to float32, added, rounded to nearest even);
+ *   2. (out, scales, zero_points) = piquant_hip_quantize_grouped(y) with computed parameters (params_given == 0), bit for bit: every group size,
+ *      every dtype pair, nearest and stochastic (ONE threshold per call; per-element mode indexes the global element), the NaN rule and the
+ *      degenerate groups included;
+ *   3. d[i] = element i of piquant_hip_dequantize_grouped(out, scales, zero_points, dtype T, PIQUANT_REDUCE_OP_SET), bit for bit (for
+ *      bfloat16 the value that call stores: rounded to bfloat16 before step 4);
+ *   4. residual[i] = y[i] - d[i], rounded to nearest in T (a subtraction of its own, never contracted with step 3 into an fma).
+ * The bytes of add -> quantize_grouped -> dequantize_grouped -> subtract (four launches, 34 bytes of memory traffic per float32 element with a
+ * uint8 wire) in ONE launch that moves 13: the sum never leaves the registers (no scan, no atomics, no grid barrier).  `in` is not written;
+ * nothing at or past the tensor's end is touched in any buffer.  A NaN in y stays a NaN in the residual (its payload and sign are not
+ * specified).  Two properties of the parameter epilogue carry over: a constant group gets the degenerate (1.0, qmax >> 1), and a group whose
+ * range lies far from zero has its zero point clamped, so most of its mass goes to the residual -- error feedback conserves that mass, it does
+ * not make such a group representable.  `in`, `residual` and `out` must not overlap.
+ * piquant_hip_quantize_grouped_ef_batch: tensor i has its own input, residual, output, scales, zero_points and numels[i]; the rules of
+ * piquant_hip_quantize_grouped_batch (one threshold per batch, up to 16 tensors per launch and one launch per 16 beyond, empty tensors skipped,
+ * a tensor whose input, residual or output is not 16-byte aligned goes through a guarded element-by-element launch that writes the same bytes).
+ * Device (or pinned) buffers only; stream-ordered on the context's stream (always behind the previous call,
+ * whatever piquant_hip_set_independent_calls says: the residual is the previous step's output), no host synchronisation, no allocation
+ * (hipGraph-capturable).  numel == 0 is a no-op. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, void* out,
+                                                    piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                                    piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                          void* const* residuals, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                          size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                          piquant_round_mode_t mode);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

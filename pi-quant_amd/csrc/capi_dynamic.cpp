@@ -706,4 +706,64 @@ void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piqu
     if (ctx->blocking) wait_stream(ctx);
 }
 
+// Error feedback (include/piquant_hip.h, piquant_hip_quantize_grouped_ef).  The single call goes through the batch entry with one tensor, which
+// launches the single-tensor kernel.
+void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
+                                           void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                           uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_ef_batch: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_ef_batch: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
+    GroupedEfBatchLaunch b {};
+    b.group_size = static_cast<int64_t>(group_size);
+    b.dt_in = dtype_in;
+    b.dt_out = dtype_out;
+    b.round_mode = rm.round_mode;
+    b.threshold = rm.threshold;
+    b.seed = rm.seed;
+    b.index_base = rm.index_base;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        if (!inputs[i] || !residuals[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_ef: NULL buffer %zu", i);
+        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_ef: scales %zu must be 4-byte aligned", i);
+        const Resolved rin = ctx->resolve_ptr(inputs[i]), rres = ctx->resolve_ptr(residuals[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]),
+                       rz = resolve(zero_points[i]);
+        if (rin.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped_ef needs device (or pinned) buffers");
+        const int t = b.count;
+        b.in[t] = rin.dev;
+        b.residual[t] = rres.dev;
+        b.out[t] = rout.dev;
+        b.scales[t] = static_cast<float*>(rs.dev);
+        b.zero_points[t] = static_cast<uint8_t*>(rz.dev);
+        b.numel[t] = static_cast<int64_t>(numels[i]);
+        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rres.dev) || !grouped_aligned16(rout.dev)) {   // the guarded kernel, same bytes
+            launch_quantize_grouped_ef_guarded(b, t, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        if (++b.count == kGroupedBatchMaxTensors) {
+            launch_quantize_grouped_ef_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_quantize_grouped_ef_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, void* out, piquant_dtype_t dtype_out,
+                                     size_t numel, size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_ef: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    piquant_hip_quantize_grouped_ef_batch(ctx, &in, dtype_in, &residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1, mode);
+}
+
 }  // extern "C"

@@ -119,11 +119,13 @@ __device__ __forceinline__ void grouped_load(const void* in, int64_t numel, int6
 // Quantize of one chunk whose NV rows are in `raw` (grouped_load: elements at or past numel are quiet NaNs): parameters, quantization, staged
 // stores.  GIVEN: scales / zero_points are inputs ("quantize with these per-group parameters", no reduction); otherwise they are written.
 // p0 carries what is per call (threshold, seed, index base); its inv_scale / zero point are replaced per group.  The wave's LDS
-// slices (stage: OUT_BYTES bytes; s_a, s_b: NG floats each).
-template <int DT_IN, int BITS, int MODE, int G, bool GIVEN, int NV_ = GroupedQuantTile<DT_IN, BITS, G>::NV>
+// slices (stage: OUT_BYTES bytes; s_a, s_b: NG floats each).  KEEP (the error-feedback kernels): the chunk stays readable after the call --
+// `stage` holds its packed bytes, s_a / s_b the groups' {1/scale, zero point} and s_scale (NG floats) their scales; nothing else changes.
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN, int NV_ = GroupedQuantTile<DT_IN, BITS, G>::NV, bool KEEP = false>
 __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_t* __restrict__ out, int64_t numel,
                                                        float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
-                                                       int64_t g0, bool full, int lane, uint8_t* stage, float* s_a, float* s_b) {
+                                                       int64_t g0, bool full, int lane, uint8_t* stage, float* s_a, float* s_b,
+                                                       float* s_scale = nullptr) {
     using T = GroupedQuantTile<DT_IN, BITS, G>;
     constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR, NG = T::NG;
     constexpr int WORDS = OB > 4 ? 2 : 1, PACK = 8 / BITS;
@@ -168,6 +170,7 @@ __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_
             bounded = __fmul_rn(__builtin_fmaxf(__builtin_fabsf(glo), __builtin_fabsf(ghi)), inv) < 1.0e9f;
             s_a[lane] = inv;
             s_b[lane] = __int_as_float(static_cast<int32_t>(zp));
+            if constexpr (KEEP) s_scale[lane] = scale;
         }
     }
     wave_lds_sync();
@@ -678,6 +681,232 @@ dequantize_grouped_scalar_kernel(const uint8_t* __restrict__ in, void* __restric
         } else {
             uint16_t* o = static_cast<uint16_t*>(out);
             o[i] = static_cast<uint16_t>(f32_to_bf16_bits(OP == OP_ADD ? __fadd_rn(f, bf16_bits_to_f32(o[i])) : f));
+        }
+    }
+}
+
+// ---- Error feedback (piquant_hip_quantize_grouped_ef): y = x + r rounded to the tensor's type, (q, scales, zero_points) = quantize_grouped(y),
+// r <- y - dequantize_grouped(q) rounded to the tensor's type, in ONE launch.  The wave loads its NV rows of x and of r (all loads issued before
+// the first add), forms y in the resident rows, runs the quantize chunk body (KEEP), then reads its own packed words back from the wave's LDS
+// slice, dequantizes them with its groups' parameters in the pair's own form (the value a grouped dequantize SET stores: for bf16 rounded to
+// bf16 BEFORE the subtraction), subtracts with a separately rounded __fsub_rn and stores the residual rows with 16-byte write-through stores.
+// No scan, no atomics, no grid barrier; waves never wait for one another.
+
+// raw[r] = rn(raw[r] + res[r]) element by element in the tensor's type
+template <int DT, int NV>
+__device__ __forceinline__ void grouped_add_residual(u32x4 (&raw)[NV], const u32x4 (&res)[NV]) {
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (DT == DT_F32) {
+                raw[r][e] = __float_as_uint(__fadd_rn(__uint_as_float(raw[r][e]), __uint_as_float(res[r][e])));
+            } else {
+                raw[r][e] = f32x2_to_bf16x2_bits(__fadd_rn(__uint_as_float(raw[r][e] << 16), __uint_as_float(res[r][e] << 16)),
+                                                 __fadd_rn(__uint_as_float(raw[r][e] & 0xffff0000u), __uint_as_float(res[r][e] & 0xffff0000u)));
+            }
+        }
+    }
+}
+
+// y - d of one element in the tensor's type: d is what a dequantize SET stores (bf16: rounded first), the difference is rounded once more
+template <int DT>
+__device__ __forceinline__ float residual_one(float y, float d) {
+    if constexpr (DT == DT_BF16) d = bf16_bits_to_f32(f32_to_bf16_bits(d));
+    return __fsub_rn(y, d);
+}
+
+// raw[r] <- y - dequantize(the chunk's packed bytes in `stage`), then the residual rows to memory (elements at or past numel are not written)
+template <int DT, int BITS, int G, int NV_ = GroupedQuantTile<DT, BITS, G>::NV>
+__device__ __forceinline__ void grouped_residual_store(u32x4 (&raw)[NV_], void* __restrict__ residual, int64_t numel, int64_t v0, bool full, int lane,
+                                                       const uint8_t* stage, const float* s_scale, const float* s_zp) {
+    using T = GroupedQuantTile<DT, BITS, G>;
+    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
+    constexpr int FORM = DequantForm<BITS, DT>::value;
+    DequantParams p[SETS];
+#pragma unroll
+    for (int s = 0; s < SETS; ++s) {
+        const int slot = s * GPR + lane / LPG;
+        p[s] = DequantParams {};
+        p[s].scale = s_scale[slot];
+        p[s].zp32 = __float_as_int(s_zp[slot]);
+        p[s].zp64 = p[s].zp32;
+        p[s].bias = __fmul_rn(-static_cast<float>(p[s].zp32), p[s].scale);   // as resolved(DequantParams) forms it
+    }
+    u32x4* r16 = static_cast<u32x4*>(residual);
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const uint8_t* src = stage + (r * 64 + lane) * OB;
+        uint32_t w[OB > 4 ? 2 : 1];
+        if constexpr (OB == 1) w[0] = *src;
+        else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
+        else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
+        else {
+            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
+            w[0] = t[0];
+            w[1] = t[1];
+        }
+        float f[EPV];
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p[r / RPG]);
+        u32x4 o;
+        if constexpr (DT == DT_F32) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = __float_as_uint(residual_one<DT>(__uint_as_float(raw[r][e]), f[e]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                o[e] = f32x2_to_bf16x2_bits(residual_one<DT>(__uint_as_float(raw[r][e] << 16), f[2 * e]),
+                                            residual_one<DT>(__uint_as_float(raw[r][e] & 0xffff0000u), f[2 * e + 1]));
+        }
+        const int64_t vec = v0 + r * 64 + lane;
+        if (full || (vec + 1) * EPV <= numel) {
+            st<ST_WT>(r16 + vec, o);
+        } else {   // the tensor ends inside this vector, or in front of it
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) {
+                const int64_t i = vec * EPV + e;
+                if (i >= numel) continue;
+                if constexpr (DT == DT_F32) static_cast<uint32_t*>(residual)[i] = o[e];
+                else static_cast<uint16_t*>(residual)[i] = static_cast<uint16_t>(o[e >> 1] >> ((e & 1) * 16));
+            }
+        }
+    }
+}
+
+// one wave's chunk (NG groups from group g0 on) of one (tensor, residual) pair; the wave's LDS slices as in grouped_quantize_chunk plus s_c (NG floats)
+template <int DT_IN, int BITS, int MODE, int G>
+__device__ __forceinline__ void grouped_ef_chunk(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel,
+                                                 float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
+                                                 int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b, float* s_c) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+
+    u32x4 raw[NV];
+    {
+        u32x4 res[NV];
+        grouped_load<DT_IN, NV>(in, numel, v0, lane, full, raw);
+        grouped_load<DT_IN, NV>(residual, numel, v0, lane, full, res);
+        grouped_add_residual<DT_IN, NV>(raw, res);
+    }
+    grouped_quantize_chunk<DT_IN, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
+    grouped_residual_store<DT_IN, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
+}
+
+template <int DT_IN, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                           uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // {min, max}, then {1/scale, zero point, scale} of the chunk's groups
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t g0 = (static_cast<int64_t>(blockIdx.x) * WAVES + wave) * NG;
+    if (g0 >= ngroups) return;
+    grouped_ef_chunk<DT_IN, BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+}
+
+// Up to kGroupedBatchMax independent (tensor, residual) pairs in ONE launch, found through the prefix table of quantize_grouped_batch_kernel.
+struct GroupedEfBatchArgs {
+    const void* in[kGroupedBatchMax];
+    void* residual[kGroupedBatchMax];
+    uint8_t* out[kGroupedBatchMax];
+    float* scales[kGroupedBatchMax];
+    uint8_t* zero_points[kGroupedBatchMax];
+    int64_t numel[kGroupedBatchMax];
+    int64_t chunk_begin[kGroupedBatchMax + 1];
+    int count;
+};
+
+template <int DT_IN, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_batch_kernel(GroupedEfBatchArgs a, QuantParams p0) {
+    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (c >= a.chunk_begin[a.count]) return;
+    int t = 0;
+    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    const int64_t numel = a.numel[t];
+    grouped_ef_chunk<DT_IN, BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
+                                           (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+}
+
+// Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element, the same bytes.  Correct, not fast.
+template <int DT_IN, int BITS, int MODE>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
+                                  float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, float threshold, uint32_t seed_lo,
+                                  uint32_t seed_hi, uint64_t index_base) {
+    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1, FORM = DequantForm<BITS, DT_IN>::value;
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the group loop is wave-uniform
+    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
+        const int64_t b = g * group_size;
+        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);   // <= 4096: 32-bit offsets inside the group
+        auto y_of = [&](int o) {
+            const float y = __fadd_rn(InVec<DT_IN>::load_scalar(in, b + o), InVec<DT_IN>::load_scalar(residual, b + o));
+            if constexpr (DT_IN == DT_BF16) return bf16_bits_to_f32(f32_to_bf16_bits(y));
+            else return y;
+        };
+        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
+        for (int o0 = 0; o0 < len; o0 += 64) {   // wave-uniform trip counts: a lane past the group's end sits the step out
+            if (o0 + lane < len) {
+                const float x = quieted(y_of(o0 + lane));
+                lo = __builtin_fminf(lo, x);
+                hi = __builtin_fmaxf(hi, x);
+            }
+        }
+        lo = wave_min(lo);   // every lane's loads of the group are complete here: the residual is overwritten below
+        hi = wave_max(hi);
+        float scale;
+        int64_t zp;
+        quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
+        if (lane == 0) {
+            scales[g] = scale;
+            zero_points[g] = static_cast<uint8_t>(zp);
+        }
+        QuantParams p {};   // what is per call, and the group's parameters
+        p.threshold = threshold;
+        p.seed_lo = seed_lo;
+        p.seed_hi = seed_hi;
+        p.index_base = index_base;
+        p.inv_scale = __fdiv_rn(1.0f, scale);
+        p.zp64 = zp;
+        p.zp32 = static_cast<int32_t>(zp);
+        DequantParams d {};
+        d.scale = scale;
+        d.zp32 = p.zp32;
+        d.zp64 = zp;
+        d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);
+        uint8_t* og = out + b / PACK;   // a group starts on a whole packed byte
+        for (int by0 = 0; by0 * PACK < len; by0 += 64) {
+            const int by = by0 + lane;
+            if (by * PACK >= len) continue;
+            uint32_t acc = 0;
+#pragma unroll
+            for (int k = 0; k < PACK; ++k) {
+                const int o = by * PACK + k;
+                if (o >= len) continue;
+                const float y = y_of(o);
+                const uint32_t q = quant_one<MODE, QMAX>(y, p, static_cast<uint64_t>(b + o));
+                acc |= q << (k * BITS);
+                const float nr = residual_one<DT_IN>(y, dequant_one<FORM>(q, d));
+                if constexpr (DT_IN == DT_F32) static_cast<float*>(residual)[b + o] = nr;
+                else static_cast<uint16_t*>(residual)[b + o] = static_cast<uint16_t>(f32_to_bf16_bits(nr));
+            }
+            og[by] = static_cast<uint8_t>(acc);
         }
     }
 }

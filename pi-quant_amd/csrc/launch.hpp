@@ -177,6 +177,27 @@ struct GroupedReduceLaunch {
     uint64_t index_base;
 };
 
+// Error feedback (grouped_kernels.hpp, quantize_grouped_ef_batch_kernel): per tensor y = in + residual, (out, scales, zero_points) =
+// quantize_grouped(y) with computed parameters, residual <- y - dequantize_grouped(out), in ONE launch for up to kGroupedBatchMaxTensors tensors
+// (every buffer 16-byte aligned, every tensor non-empty; a batch of one launches quantize_grouped_ef_kernel, whose arguments are leading scalars).  launch_quantize_grouped_ef_guarded runs tensor t of the batch alone through the
+// element-by-element kernel: the same bytes for buffers of any alignment.
+struct GroupedEfBatchLaunch {
+    const void* in[kGroupedBatchMaxTensors];
+    void* residual[kGroupedBatchMaxTensors];
+    void* out[kGroupedBatchMaxTensors];
+    float* scales[kGroupedBatchMaxTensors];
+    uint8_t* zero_points[kGroupedBatchMaxTensors];
+    int64_t numel[kGroupedBatchMaxTensors];
+    int count;
+    int64_t group_size;
+    int dt_in;
+    int dt_out;
+    int round_mode;
+    float threshold;
+    uint64_t seed;
+    uint64_t index_base;
+};
+
 // All launches are asynchronous on `stream`; num_cu sizes capped grids.
 void launch_quantize(const QuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize(const DequantLaunch& d, hipStream_t stream, int num_cu);
@@ -186,6 +207,8 @@ void launch_dequantize_grouped(const GroupedDequantLaunch& d, hipStream_t stream
 void launch_quantize_grouped_batch(const GroupedQuantBatchLaunch& b, hipStream_t stream);
 void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStream_t stream);
 void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream);
+void launch_quantize_grouped_ef_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
+void launch_quantize_grouped_ef_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -476,6 +476,29 @@ class Context:
                                               (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
                                               round_mode.value)
 
+    def quantize_grouped_ef_ptr(self, ptr_in: int, dtype_in: DataType, ptr_residual: int, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                                scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """Group-wise quantize with error feedback (``piquant_hip_quantize_grouped_ef``): quantizes ``in + residual`` with computed per-group
+        parameters and leaves ``(in + residual) - dequantize(quantized)`` in ``residual`` (``numel`` elements of ``dtype_in``), one launch."""
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_ef(self._ctx, ptr_in, dtype_in.value, ptr_residual, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                          zero_points_ptr, round_mode.value)
+
+    def quantize_grouped_ef_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_residual, ptrs_out, dtype_out: DataType, numels, group_size: int,
+                                      scales_ptrs, zero_points_ptrs, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_ef_ptr`` for several independent (tensor, residual) pairs, up to 16 per kernel launch
+        (``piquant_hip_quantize_grouped_ef_batch``); one stochastic threshold for the batch."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        assert n == len(ptrs_residual) == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_ef_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_residual),
+                                                (_C.c_void_p * n)(*ptrs_out), dtype_out.value, (_C.c_size_t * n)(*numels), group_size,
+                                                (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n, round_mode.value)
+
     def compute_quant_params_dist_ptr(self, ptr: int, dtype: DataType, numel: int, target_quant_dtype: DataType, nccl_comm: int,
                                       _device_ptrs: bool = False) -> Tuple[float, int]:
         """Sharded ``compute_quant_params`` with the all-reduce done natively: ``nccl_comm`` is an ``ncclComm_t`` (RCCL)."""

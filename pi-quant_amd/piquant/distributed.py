@@ -512,6 +512,20 @@ class _DeviceOps:
                                                        torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
                                                        [r[1] for r in recs], False, self._mode(round_mode), _device_ptrs=True)
 
+    def encode_grouped_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
+        """encode_grouped(x + residual) with residual <- (x + residual) - what the record decodes to, one launch."""
+        sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
+        self._cx(x).quantize_grouped_ef_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), residual.data_ptr(), data, torch_to_piquant_dtype(qdtype),
+                                            x.numel(), group_size, sc, zp, self._mode(round_mode), _device_ptrs=True)
+
+    def encode_batch_grouped_ef(self, xs, residuals, bufs, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
+        """encode_grouped_ef(xs[i], residuals[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_grouped_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r.data_ptr() for r in residuals],
+                                                          [r[2] for r in recs], torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size,
+                                                          [r[0] for r in recs], [r[1] for r in recs], self._mode(round_mode), _device_ptrs=True)
+
     def decode_batch_grouped(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
         """decode_grouped(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
         from . import ReduceOp
@@ -668,6 +682,7 @@ def quantized_all_reduce(
     transport: str = 'collective',
     timeout: Optional[float] = None,
     group_size: Optional[int] = None,
+    error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -682,6 +697,16 @@ def quantized_all_reduce(
     ``reduce_quantize_grouped`` launch, every decode ``dequantize_grouped`` (the mesh's: one batched launch); the schedules, the launches
     per all-reduce and the bit-identity of all ranks are those of the per-chunk path.  ``transport='p2p'`` does not take grouped
     parameters.  (Unmeasured on more than one GPU, like the rest of this module's multi-GPU paths.)
+
+    ``error_feedback`` (``group_size`` only): a contiguous tensor of the all-reduced tensor's dtype, device and numel that the caller keeps between
+    steps (zeros before the first).  Every quantization this rank applies to ITS OWN contribution becomes ``quantize_grouped_ef`` on the matching
+    slice: the slice of the residual is added to the values before they are quantized and then holds what the quantization lost, so that the loss
+    is part of the next step's contribution instead of being thrown away.  In the mesh schedule that is the one batched encode of the peers' chunks
+    (still one launch per 16 chunks); in the ring the first encode of chunk ``rank``.  Slices the schedule contributes unquantized -- the mesh's own
+    chunk, the ring's other chunks -- are neither read nor written, and the re-quantizations of partial sums stay as they are.  A residual
+    therefore belongs to one (world size, rank, algorithm): carry it over only between all-reduces of the same shape in the same group with the
+    same schedule.  Without ``group_size``, or with ``transport='p2p'``, ``error_feedback`` raises ValueError before anything moves; ``None``
+    (the default) leaves every byte and every launch as it was.  A one-rank group returns at once and leaves the residual alone.
 
     ``transport='p2p'`` (``algorithm='direct'`` only, one node; EXPERIMENTAL until it has run between two GPUs): no collective at all -- the
     encode kernels store into the peers' receive buffers over xGMI and flags order the steps (``quantized_all_reduce_direct``).  ``timeout``
@@ -717,9 +742,11 @@ def quantized_all_reduce(
     if transport not in ('collective', 'p2p'):
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     _check_all_reduce_group_size(group_size, transport)
+    _check_error_feedback(error_feedback, tensor, group_size, transport)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
-                                           group_size=group_size, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
+                                           group_size=group_size, error_feedback=error_feedback, _ops=_ops,
+                                           _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
@@ -733,7 +760,7 @@ def quantized_all_reduce(
     nxt = dist.get_global_rank(group, (rank + 1) % world) if group is not None else (rank + 1) % world
     prv = dist.get_global_rank(group, (rank - 1) % world) if group is not None else (rank - 1) % world
     if group_size is not None:
-        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size)
+        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, error_feedback)
     max_bytes = max(qdt.packed_nbytes(e - b) for b, e in chunks) + _HEADER_BYTES
     send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
@@ -787,6 +814,7 @@ def quantized_all_reduce_direct(
     transport: str = 'collective',
     timeout: Optional[float] = None,
     group_size: Optional[int] = None,
+    error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -815,10 +843,14 @@ def quantized_all_reduce_direct(
     ``group_size``: group-wise parameters on the wire (``quantized_all_reduce``); step 1 is one batched ``quantize_grouped`` launch, steps 3-4
     one ``reduce_quantize_grouped`` launch over the G-1 received chunks in increasing rank order, the decode one batched ``dequantize_grouped``
     launch.  Collective transport only.
+
+    ``error_feedback``: the residual of ``quantized_all_reduce`` -- step 1 becomes one batched ``quantize_grouped_ef`` launch on the peers'
+    chunks of the tensor and of the residual; the rank's own chunk of the residual is neither read nor written.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_all_reduce_group_size(group_size, transport)
+    _check_error_feedback(error_feedback, tensor, group_size, transport)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
@@ -836,7 +868,7 @@ def quantized_all_reduce_direct(
     if transport != 'collective':
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     if group_size is not None:
-        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size)
+        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, error_feedback)
     send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
 
@@ -875,9 +907,24 @@ def _check_all_reduce_group_size(group_size, transport: str) -> None:
         raise ValueError("group_size= is not supported with transport='p2p' (its peer-mapped slots carry the per-chunk record); use transport='collective'")
 
 
-def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size):
+def _check_error_feedback(residual, tensor: torch.Tensor, group_size, transport: str) -> None:
+    """ValueError before anything moves: a residual without the grouped wire or over the peer-to-peer transport, or one that does not match the
+    tensor (it is written by raw pointer)."""
+    if residual is None:
+        return
+    if group_size is None:
+        raise ValueError('error_feedback= needs the grouped wire: pass group_size= (the per-chunk wire has no error-feedback quantize)')
+    if transport == 'p2p':
+        raise ValueError("error_feedback= is not supported with transport='p2p'; use transport='collective'")
+    from .torch import _check_residual
+
+    _check_residual(residual, tensor, 'error_feedback')
+
+
+def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, residual=None):
     """The ring of ``quantized_all_reduce`` on the grouped wire: the same hops with quantize_grouped / reduce_quantize_grouped (one term) /
-    dequantize_grouped (SET) in place of the per-chunk calls."""
+    dequantize_grouped (SET) in place of the per-chunk calls.  ``residual``: the first encode (chunk ``rank``, this rank's own values) is
+    quantize_grouped_ef on that chunk of the residual; no other chunk of it is touched."""
     def wire(idx):
         b, e = chunks[idx]
         return flat[b:e], grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
@@ -889,7 +936,11 @@ def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops
     # ---- reduce-scatter ----
     x_first, n_cur = wire(rank)
     if x_first.numel():
-        ops.encode_grouped(x_first, send[:n_cur], quant_dtype, round_mode, group_size)
+        if residual is None:
+            ops.encode_grouped(x_first, send[:n_cur], quant_dtype, round_mode, group_size)
+        else:
+            b, e = chunks[rank]
+            ops.encode_grouped_ef(x_first, residual.view(-1)[b:e], send[:n_cur], quant_dtype, round_mode, group_size)
     for step in range(world - 1):
         x_recv, n_recv = wire((rank - step - 1) % world)
         _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
@@ -914,9 +965,10 @@ def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops
     return tensor
 
 
-def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size):
+def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, residual=None):
     """The mesh schedule of ``quantized_all_reduce_direct`` on the grouped wire: one batched quantize_grouped, the all-to-all, ONE
-    reduce_quantize_grouped over the G-1 received chunks (increasing rank order), the all-gather, one batched dequantize_grouped."""
+    reduce_quantize_grouped over the G-1 received chunks (increasing rank order), the all-gather, one batched dequantize_grouped.
+    ``residual``: the batched encode is quantize_grouped_ef on the peers' chunks of the residual; the rank's own chunk of it is not touched."""
     def wire_len(idx):
         b, e = chunks[idx]
         return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
@@ -925,8 +977,13 @@ def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, o
     send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
     peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
-    ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
-                             round_mode, group_size)
+    if residual is None:
+        ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
+                                 round_mode, group_size)
+    else:
+        rflat = residual.view(-1)
+        ops.encode_batch_grouped_ef([flat[chunks[j][0]:chunks[j][1]] for j in peers], [rflat[chunks[j][0]:chunks[j][1]] for j in peers],
+                                    [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype, round_mode, group_size)
     _all_to_all(send, recv, group)
     b_own, e_own = chunks[rank]
     x_own = flat[b_own:e_own]

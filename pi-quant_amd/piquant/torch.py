@@ -565,6 +565,94 @@ def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128
     return outs, scales, zero_points
 
 
+def _check_residual(residual, tensor: torch.Tensor, what: str = 'residual') -> None:
+    """The residual of an error-feedback call is written by raw pointer: a contiguous device tensor of the input's dtype, device and numel."""
+    _require(isinstance(residual, torch.Tensor), f'{what} must be a torch.Tensor')
+    _require(residual.dtype == tensor.dtype, f'{what} must have the dtype of the tensor ({tensor.dtype}), got {residual.dtype}')
+    _require(residual.numel() == tensor.numel(), f'{what} must have the numel of the tensor ({tensor.numel()}), got {residual.numel()}')
+    _require(residual.device == tensor.device, f'{what} must live on the device of the tensor ({tensor.device}), got {residual.device}')
+    _require(residual.is_contiguous(), f'{what} must be contiguous (it is updated in place)')
+
+
+def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
+                        ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
+                        out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``quantize_grouped`` with error feedback, in one launch: quantizes ``y = tensor + residual`` (rounded to the tensor's dtype) with computed
+    per-group parameters and replaces ``residual`` by ``y - dequantize_grouped(quantized)`` (rounded to the tensor's dtype), so that the rounding
+    error of this step is part of the next step's input.  Bit for bit ``torch.add`` -> ``quantize_grouped`` -> ``dequantize_grouped`` ->
+    ``torch.sub``.  ``residual`` is a contiguous tensor of the tensor's dtype, device and numel that the caller keeps between steps (zeros before
+    the first); ``tensor`` is not written.  Returns (quantized, scales, zero_points) as ``quantize_grouped`` does.  A constant group gets the
+    degenerate (1.0, qmax >> 1) and a group whose range lies far from zero has its zero point clamped: most of such a group goes to the residual,
+    which conserves it but does not make it representable (``include/piquant_hip.h``, piquant_hip_quantize_grouped_ef)."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    _check_residual(residual, tensor)
+    _check_float_input(tensor)
+    ngroups = num_groups(tensor.numel(), group_size)
+    if out_scales is None:
+        out_scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
+        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    else:
+        _check_group_params(out_scales, out_zero_points, ngroups)
+        _require(out_scales.device == tensor.device and out_zero_points.device == tensor.device, f'out_scales and out_zero_points must live on {tensor.device}')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    qdt = torch_to_piquant_dtype(dtype)
+    if out is None:
+        out = torch.empty(tensor.shape, dtype=dtype, device=tensor.device)
+    else:
+        _check_packed_out(out, qdt, tensor.numel(), tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_grouped_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), out.data_ptr(), qdt, tensor.numel(), group_size,
+                                out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, out_scales, out_zero_points
+
+
+def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
+                              outs=None, out_scales=None, out_zero_points=None):
+    """``quantize_grouped_ef`` of several independent (tensor, residual) pairs (one dtype pair, group size and round mode) with one kernel launch
+    per 16 pairs.  Returns (outs, scales, zero_points) as lists; pair i's entries and its updated residual equal
+    ``quantize_grouped_ef(tensors[i], residuals[i])`` (a stochastic batch draws one threshold)."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    tensors, residuals = list(tensors), list(residuals)
+    lists = [tensors, residuals] + ([list(outs)] if outs is not None else []) + ([list(out_scales), list(out_zero_points)] if out_scales is not None else [])
+    _check_batch_lists(*lists)
+    for i, (t, r) in enumerate(zip(tensors, residuals)):
+        _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, f'tensors[{i}] must be a float32 or bfloat16 tensor')
+        _check_residual(r, t, f'residuals[{i}]')
+    for i, t in enumerate(tensors):
+        _check_float_input(t, f'tensors[{i}]')
+        _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
+    device = tensors[0].device
+    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    qdt = torch_to_piquant_dtype(dtype)
+    if out_scales is None:
+        out_scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
+        out_zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
+    else:
+        out_scales, out_zero_points = list(out_scales), list(out_zero_points)
+        for sc, zp, t in zip(out_scales, out_zero_points, tensors):
+            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
+            _require(sc.device == device and zp.device == device, f'out_scales and out_zero_points must live on {device}')
+    if outs is None:
+        outs = [torch.empty(t.shape, dtype=dtype, device=device) for t in tensors]
+    else:
+        outs = list(outs)
+        for i, (o, t) in enumerate(zip(outs, tensors)):
+            _check_packed_out(o, qdt, t.numel(), device, f'outs[{i}]')
+    ctx = _ctx_for(tensors[0], ctx)
+    ctx.quantize_grouped_ef_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [r.data_ptr() for r in residuals],
+                                      [o.data_ptr() for o in outs], qdt, [t.numel() for t in tensors], group_size, [sc.data_ptr() for sc in out_scales],
+                                      [zp.data_ptr() for zp in out_zero_points], _ROUND_MODES[round_mode], _device_ptrs=True)
+    return outs, out_scales, out_zero_points
+
+
 def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, reduce_op: str = 'set', ctx: Optional[Context] = None,
                              outs=None, quant_dtype: Optional[torch.dtype] = None, shapes=None):
     """``dequantize_grouped`` of several independent tensors with one kernel launch per 16 tensors; returns the list of outputs.  Raw uint8

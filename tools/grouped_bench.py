@@ -10,7 +10,12 @@ Each row gives us per call, algorithmic bytes (the 5 bytes per group included) a
 (k grouped dequantize ADD launches + quantize_grouped) in the same run, and the batched grouped quantize (7 chunks) / dequantize (8 chunks) of
 an 8-way mesh next to as many single calls.  Writes profiles/grouped_reduce_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows ef: the error-feedback quantize (quantize_grouped_ef, G = 128, every pair) next to the four launches it replaces (torch.add ->
+quantize_grouped -> dequantize_grouped -> torch.sub), to quantize_grouped alone and to torch.add / torch.sub alone, all in the same run; a batch
+of one next to the single quantize_grouped call (the error-feedback single call is a batch of one); and the kernel time of one rank's replayed
+8-way grouped mesh all-reduce with and without error feedback.  Writes profiles/grouped_ef_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -141,15 +146,138 @@ def reduce_rows(ctx, dev, stream, args, G=128, world=8):
     return rows
 
 
+def ef_rows(ctx, dev, stream, args, G=128, world=8):
+    """quantize_grouped_ef against the composition it replaces and against quantize_grouped alone, every pair; the mesh with and without it"""
+    import piquant.distributed as D
+
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(3)
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (2 * NUMEL * esize)) + 1)
+        xs = [torch.empty(NUMEL, dtype=tdt, device=dev).normal_(generator=g) for _ in range(nbuf)]
+        rs = [(torch.empty(NUMEL, dtype=torch.float32, device=dev).normal_(generator=g) * 0.01).to(tdt) for _ in range(nbuf)]
+        ys = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        ds = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+        fbytes = NUMEL * esize
+        us_add, s_add = timed(lambda i: torch.add(xs[i], rs[i], out=ys[i]), nbuf, args.windows, per_window, stream)
+        rows.append(row("torch.add", fname, 0, us_add, 3 * fbytes, s_add))
+        us_sub, s_sub = timed(lambda i: torch.sub(ys[i], ds[i], out=rs[i]), nbuf, args.windows, per_window, stream)
+        rows.append(row("torch.sub", fname, 0, us_sub, 3 * fbytes, s_sub))
+        for qname, (qdt, bits) in QUANT.items():
+            pair = f"{fname}->{qname}"
+            nq = qdt.packed_nbytes(NUMEL)
+            outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+            def quant(i):
+                ctx.quantize_grouped_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                         piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            def composition(i):
+                torch.add(xs[i], rs[i], out=ys[i])
+                ctx.quantize_grouped_ptr(ys[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                         piquant.RoundMode.NEAREST, _device_ptrs=True)
+                ctx.dequantize_grouped_ptr(outs[i].data_ptr(), qdt, ds[i].data_ptr(), fdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), piquant.ReduceOp.SET,
+                                           _device_ptrs=True)
+                torch.sub(ys[i], ds[i], out=rs[i])
+
+            def fused(i):
+                ctx.quantize_grouped_ef_ptr(xs[i].data_ptr(), fdt, rs[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                            piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            us_q, s_q = timed(quant, nbuf, args.windows, per_window, stream)
+            qr = row("quantize_grouped", pair, G, us_q, fbytes + nq + 5 * ng, s_q)
+            us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+            cr = row("ef_composition", pair, G, us_c, 8 * fbytes + 2 * (nq + 5 * ng), s_c)
+            us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+            fr = row("quantize_grouped_ef", pair, G, us_f, 3 * fbytes + nq + 5 * ng, s_f)
+            fr["over_composition"] = round(us_f / us_c, 3)
+            fr["bytes_over_composition"] = round(fr["bytes"] / cr["bytes"], 3)
+            fr["over_quantize_grouped"] = round(us_f / us_q, 3)
+            fr["bytes_over_quantize_grouped"] = round(fr["bytes"] / qr["bytes"], 3)
+            fr["target_0.5x_composition"] = "met" if fr["over_composition"] <= 0.5 else "missed"
+            print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}), fused / quantize_grouped = "
+                  f"{fr['over_quantize_grouped']:.3f} (bytes {fr['bytes_over_quantize_grouped']:.3f})", flush=True)
+            rows += [qr, cr, fr]
+            if pair == "f32->uint8":   # what a batch of one costs against the single kernel (the error-feedback single call is a batch of one)
+                us_b, s_b = timed(lambda i: ctx.quantize_grouped_batch_ptr([xs[i].data_ptr()], fdt, [outs[i].data_ptr()], qdt, [NUMEL], G, [sc[i].data_ptr()],
+                                                                           [zs[i].data_ptr()], False, piquant.RoundMode.NEAREST, _device_ptrs=True),
+                                  nbuf, args.windows, per_window, stream)
+                br = row("quantize_grouped_batch 1", pair, G, us_b, fbytes + nq + 5 * ng, s_b)
+                br["over_single"] = round(us_b / us_q, 3)
+                rows.append(br)
+            del outs
+        del xs, rs, ys, ds, sc, zs
+        torch.cuda.empty_cache()
+
+    # one rank's kernels of an 8-way grouped mesh all-reduce (no wire: stand-in receive buffers), replayed from a graph, with and without the residual
+    ops = D._DeviceOps(ctx)
+    x = torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g)
+    res = torch.zeros(NUMEL, device=dev)
+    for qname, bits in (("uint8", 8), ("quint4x2", 4)):
+        qdt = getattr(torch, qname)
+        chunks = D.ring_chunks(NUMEL, world, bits)
+        gbytes = [D.grouped_wire_layout(e - b, G, bits).nbytes for b, e in chunks]
+        slot = -(-max(gbytes) // 16) * 16
+        bufs = torch.zeros(world * slot, dtype=torch.uint8, device=dev)
+        mine = torch.zeros(slot, dtype=torch.uint8, device=dev)
+        for j, (b, e) in enumerate(chunks):
+            ops.encode_grouped(x[b:e], bufs[j * slot: j * slot + gbytes[j]], qdt, "nearest", G)
+        peers = list(range(1, world))
+
+        def mesh(ef):
+            vals = [x[chunks[j][0]:chunks[j][1]] for j in peers]
+            wire = [bufs[j * slot: j * slot + gbytes[j]] for j in peers]
+            if ef:
+                ops.encode_batch_grouped_ef(vals, [res[chunks[j][0]:chunks[j][1]] for j in peers], wire, qdt, "nearest", G)
+            else:
+                ops.encode_batch_grouped(vals, wire, qdt, "nearest", G)
+            ops.reduce_encode_grouped([bufs[i * slot: i * slot + gbytes[0]] for i in peers], x[chunks[0][0]:chunks[0][1]], mine[: gbytes[0]], qdt, "nearest", G)
+            ops.decode_batch_grouped([bufs[j * slot: j * slot + gbytes[j]] for j in range(world)], [x[chunks[j][0]:chunks[j][1]] for j in range(world)], qdt,
+                                     "set", G)
+
+        r = {"kind": "mesh_kernels_per_rank", "pair": f"f32->{qname}", "group_size": G, "world": world, "launches_per_all_reduce": 3}
+        for name, ef in (("without_error_feedback_us", False), ("with_error_feedback_us", True)):
+            x.uniform_(-1, 1, generator=g)
+            for _ in range(3):
+                mesh(ef)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream()
+            with torch.cuda.stream(side):
+                mesh(ef)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(graph, stream=side):
+                    mesh(ef)
+                graph.replay()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+            r[name] = round(e0.elapsed_time(e1) * 1e3 / 20, 1)
+        r["with_over_without"] = round(r["with_error_feedback_us"] / r["without_error_feedback_us"], 3)
+        print(f"mesh f32->{qname}: {r['without_error_feedback_us']} us without, {r['with_error_feedback_us']} us with error feedback", flush=True)
+        rows.append(r)
+    ctx.set_stream(stream.cuda_stream)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / ("grouped_bench.json" if args.rows == "all" else "grouped_reduce_bench.json"))
+        args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -161,6 +289,8 @@ def main():
     rows = []
     if args.rows == "reduce":
         rows = reduce_rows(ctx, dev, stream, args)
+    if args.rows == "ef":
+        rows = ef_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
