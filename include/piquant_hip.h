@@ -203,6 +203,27 @@ PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, 
                                                         const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
                                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
                                                         piquant_round_mode_t mode);
+/* piquant_hip_reduce_quantize_grouped with error feedback (piquant_hip_quantize_grouped_ef below) on the re-quantization: the owner's step of a
+ * grouped mesh all-reduce and every hop of a grouped ring, compensated.  T is dtype_acc (float32 or bfloat16); `residual` has type T and numel
+ * elements and is read AND written.  The call writes exactly the bytes that this composition of two public calls writes to out, scales,
+ * zero_points and residual:
+ *   1. for i = 0 .. count - 1 in order: piquant_hip_dequantize_grouped(inputs[i], ..., input_scales[i], input_zero_points[i],
+ *      PIQUANT_REDUCE_OP_ADD) into acc -- the running sum is rounded to T after each term;
+ *   2. piquant_hip_quantize_grouped_ef(acc, residual, out, ..., scales, zero_points, mode): y = rn_T(acc + residual), quantize_grouped(y) with
+ *      computed parameters, residual <- rn_T(y - d) with d the value a grouped dequantize SET stores (bfloat16: rounded first; the subtraction is
+ *      never contracted).
+ * The residual is added AFTER the terms.  Every buffer 16-byte aligned: ONE launch for up to 16 terms (no scan, no atomics, no grid barrier; the
+ * sum never leaves the registers); with more than 16 the surplus is first added into acc by grouped dequantize ADD launches and the last 16 are
+ * fused.  If acc, residual, out or a term is not 16-byte aligned the call runs as the composition above (same bytes).  count == 0 is
+ * piquant_hip_quantize_grouped_ef(acc, residual).  The contents of acc afterwards are unspecified; nothing at or past the tensor's end is
+ * touched in any buffer; acc, residual, out and the terms must not overlap.  Stochastic rounding draws ONE threshold per call; per-element mode
+ * indexes the global element.  Device (or pinned) buffers only; stream-ordered on the context's stream, always behind the previous call whatever
+ * piquant_hip_set_independent_calls says; no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op. */
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_ef(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual,
+                                                           const void* const* inputs, const float* const* input_scales,
+                                                           const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out,
+                                                           size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                                           piquant_round_mode_t mode);
 
 /* Error feedback for the group-wise wire: a lossy gradient / pseudo-gradient all-reduce keeps the rounding error of every step and adds it to the
  * next step's input instead of throwing it away.  `residual` has the input's type (dtype_in: float32 or bfloat16) and numel elements; it is read

@@ -766,4 +766,103 @@ void piquant_hip_quantize_grouped_ef(piquant_context_t* ctx, const void* in, piq
     piquant_hip_quantize_grouped_ef_batch(ctx, &in, dtype_in, &residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1, mode);
 }
 
+// Error feedback on a re-quantized partial sum (include/piquant_hip.h).  Every buffer 16-byte aligned: the surplus over kGroupedReduceMaxInputs terms
+// goes into acc by grouped dequantize ADD launches and the last terms are fused with the residual in ONE launch.  Anything else: the two-step
+// composition that defines the call -- every term by grouped dequantize ADD, then quantize_grouped_ef(acc, residual) -- with the call's one threshold.
+void piquant_hip_reduce_quantize_grouped_ef(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual, const void* const* inputs,
+                                            const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                            piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                            piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_reduce_quantize_grouped_ef: context is NULL");
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    if (!acc || !residual || !out || !scales || !zero_points) panic("reduce_quantize_grouped_ef: NULL buffer");
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped_ef: NULL argument");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped_ef: scales must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const Resolved racc = ctx->resolve_ptr(acc), rres = ctx->resolve_ptr(residual), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
+    if (racc.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
+        panic("piquant_hip_reduce_quantize_grouped_ef needs device (or pinned) buffers");
+    std::vector<const void*> tin(count);
+    std::vector<const float*> tsc(count);
+    std::vector<const uint8_t*> tzp(count);
+    bool aligned = grouped_aligned16(racc.dev) && grouped_aligned16(rres.dev) && grouped_aligned16(rout.dev);
+    for (size_t i = 0; i < count; ++i) {
+        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped_ef: NULL input %zu", i);
+        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped_ef: input scales %zu must be 4-byte aligned", i);
+        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
+        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped_ef needs device (or pinned) buffers");
+        tin[i] = ri.dev;
+        tsc[i] = static_cast<const float*>(rsi.dev);
+        tzp[i] = static_cast<const uint8_t*>(rzi.dev);
+        aligned = aligned && grouped_aligned16(ri.dev);
+    }
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // the call's one threshold, whichever form runs
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
+    const size_t fused_from = aligned ? (count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0) : count;
+    for (size_t i = 0; i < fused_from; ++i) {
+        GroupedDequantLaunch d {};
+        d.in = tin[i];
+        d.out = racc.dev;
+        d.numel = static_cast<int64_t>(numel);
+        d.group_size = static_cast<int64_t>(group_size);
+        d.scales = tsc[i];
+        d.zero_points = tzp[i];
+        d.dt_in = dtype_out;
+        d.dt_out = dtype_acc;
+        d.op = OP_ADD;
+        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+    }
+    if (aligned && count > 0) {
+        GroupedReduceEfLaunch e {};
+        GroupedReduceLaunch& r = e.r;
+        e.residual = rres.dev;
+        r.acc = racc.dev;
+        r.out = rout.dev;
+        r.numel = static_cast<int64_t>(numel);
+        r.group_size = static_cast<int64_t>(group_size);
+        r.scales = static_cast<float*>(rs.dev);
+        r.zero_points = static_cast<uint8_t*>(rz.dev);
+        for (size_t i = fused_from; i < count; ++i) {
+            r.in[r.count] = tin[i];
+            r.in_scales[r.count] = tsc[i];
+            r.in_zero_points[r.count] = tzp[i];
+            ++r.count;
+        }
+        r.dt_acc = dtype_acc;
+        r.dt_out = dtype_out;
+        r.round_mode = rm.round_mode;
+        r.threshold = rm.threshold;
+        r.seed = rm.seed;
+        r.index_base = rm.index_base;
+        launch_reduce_quantize_grouped_ef(e, ctx->stream);
+    } else {   // k == 0, or the two-step form: quantize_grouped_ef(acc, residual), streaming or guarded by its own alignment rule
+        GroupedEfBatchLaunch b {};
+        b.in[0] = racc.dev;
+        b.residual[0] = rres.dev;
+        b.out[0] = rout.dev;
+        b.scales[0] = static_cast<float*>(rs.dev);
+        b.zero_points[0] = static_cast<uint8_t*>(rz.dev);
+        b.numel[0] = static_cast<int64_t>(numel);
+        b.group_size = static_cast<int64_t>(group_size);
+        b.dt_in = dtype_acc;
+        b.dt_out = dtype_out;
+        b.round_mode = rm.round_mode;
+        b.threshold = rm.threshold;
+        b.seed = rm.seed;
+        b.index_base = rm.index_base;
+        if (grouped_aligned16(racc.dev) && grouped_aligned16(rres.dev) && grouped_aligned16(rout.dev)) {
+            b.count = 1;
+            launch_quantize_grouped_ef_batch(b, ctx->stream);
+        } else {
+            launch_quantize_grouped_ef_guarded(b, 0, ctx->stream, ctx->num_cu);
+        }
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Compile-time dispatch shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip):
+// Compile-time dispatch shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip, kernels_grouped_reduce_ef.hip):
 // runtime group size / types / rounding mode -> std::integral_constant, and the per-call QuantParams.
 #pragma once
 

@@ -842,6 +842,98 @@ quantize_grouped_ef_batch_kernel(GroupedEfBatchArgs a, QuantParams p0) {
                                            (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
 }
 
+// ---- Error feedback on a re-quantized partial sum (piquant_hip_reduce_quantize_grouped_ef): the owner's step of a mesh all-reduce and every hop of
+// a ring, compensated.  y = rn(rn(..rn(acc + d(term_0)).. + d(term_{k-1})) + residual), (q, scales, zero_points) = quantize_grouped(y),
+// residual <- rn(y - d(q)), in ONE launch: the bytes of k grouped dequantize ADD calls into acc followed by quantize_grouped_ef(acc, residual).
+// The tile and the term staging are reduce_quantize_grouped_kernel's, the tail is grouped_ef_chunk's.  The last term is peeled out of the loop so
+// that the residual rows need not be live across it: their loads are issued either with the acc rows (RES_EARLY: NV more vectors per lane through
+// the whole term loop) or right after the last term has been parked in LDS, where they fly during that term's dequantize and add
+// (profiles/EXPERIMENTS.md has the comparison; DESIGN.md 4c the choice).  No scan, no atomics, no grid barrier; waves never wait for one another.
+#ifndef PQ_REDUCE_EF_RESIDUAL_EARLY
+#define PQ_REDUCE_EF_RESIDUAL_EARLY 0
+#endif
+
+// the term in `t` into the wave's LDS slices: its packed bytes and, from lane j < NG, group j's {scale, bias, zero point}
+template <class L>
+__device__ __forceinline__ void grouped_park_term(const L& t, uint8_t* stage, float* s_scale, float* s_bias, int32_t* s_zp, bool has_group, int lane) {
+    t.park(stage, lane);
+    if (has_group) {
+        s_scale[lane] = t.scale;
+        s_bias[lane] = __fmul_rn(-static_cast<float>(t.zp), t.scale);   // as resolved(DequantParams) forms it
+        s_zp[lane] = t.zp;
+    }
+}
+
+template <int DT_ACC, int BITS, int MODE, int G, bool RES_EARLY = (PQ_REDUCE_EF_RESIDUAL_EARLY != 0)>
+__global__ void __launch_bounds__(kGroupedBlock)
+reduce_quantize_grouped_ef_kernel(const void* __restrict__ acc, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                  uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0, GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_ACC, BITS, G>;
+    using L = GroupedTermLoad<DT_ACC, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // a term's {scale, bias}; then {min, max}, then {1/scale, zero point, scale}
+    __shared__ int32_t s_z[WAVES][NG];                                 // a term's zero point
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_out[wave];
+    const int count = terms.count;
+
+    u32x4 raw[NV], res[NV];
+    if (full) {
+        L next;
+        if (count > 0) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+        grouped_load<DT_ACC, NV>(acc, numel, v0, lane, true, raw);
+        if (RES_EARLY || count == 0) grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
+        for (int i = 0; i + 1 < count; ++i) {
+            const L cur = next;
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+            wave_lds_sync();
+            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+        if (count > 0) {   // the last term: nothing left to prefetch but the residual
+            grouped_park_term(next, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            if constexpr (!RES_EARLY) grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
+            wave_lds_sync();
+            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+    } else {
+        // the tensor ends inside this chunk: acc and residual read as quiet NaNs behind it, a term byte by byte up to its last byte (zeros behind it)
+        grouped_load<DT_ACC, NV>(acc, numel, v0, lane, false, raw);
+        grouped_load<DT_ACC, NV>(residual, numel, v0, lane, false, res);
+        const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
+        for (int i = 0; i < count; ++i) {
+            const uint8_t* c = terms.in[i] + v0 * T::OB;
+            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
+            if (has_group) {
+                const float scale = terms.scales[i][gj];
+                const int32_t zp = terms.zero_points[i][gj];
+                s_a[wave][lane] = scale;
+                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
+                s_z[wave][lane] = zp;
+            }
+            wave_lds_sync();
+            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+    }
+    grouped_add_residual<DT_ACC, NV>(raw, res);
+    grouped_quantize_chunk<DT_ACC, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave],
+                                                                   s_c[wave]);
+    grouped_residual_store<DT_ACC, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c[wave], s_b[wave]);
+}
+
 // Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element, the same bytes.  Correct, not fast.
 template <int DT_IN, int BITS, int MODE>
 __global__ void __launch_bounds__(kGroupedBlock)

@@ -177,6 +177,14 @@ struct GroupedReduceLaunch {
     uint64_t index_base;
 };
 
+// Error feedback on a re-quantized partial sum (grouped_kernels.hpp, reduce_quantize_grouped_ef_kernel): `r` as for launch_reduce_quantize_grouped
+// (every buffer 16-byte aligned, at most kGroupedReduceMaxInputs terms) plus the residual, of r.dt_acc and r.numel elements, 16-byte aligned:
+// y = acc + terms + residual, (out, scales, zero_points) = quantize_grouped(y), residual <- y - dequantize_grouped(out), in ONE launch.
+struct GroupedReduceEfLaunch {
+    GroupedReduceLaunch r;
+    void* residual;
+};
+
 // Error feedback (grouped_kernels.hpp, quantize_grouped_ef_batch_kernel): per tensor y = in + residual, (out, scales, zero_points) =
 // quantize_grouped(y) with computed parameters, residual <- y - dequantize_grouped(out), in ONE launch for up to kGroupedBatchMaxTensors tensors
 // (every buffer 16-byte aligned, every tensor non-empty; a batch of one launches quantize_grouped_ef_kernel, whose arguments are leading scalars).  launch_quantize_grouped_ef_guarded runs tensor t of the batch alone through the
@@ -208,6 +216,7 @@ void launch_quantize_grouped_batch(const GroupedQuantBatchLaunch& b, hipStream_t
 void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStream_t stream);
 void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream);
 void launch_quantize_grouped_ef_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
+void launch_reduce_quantize_grouped_ef(const GroupedReduceEfLaunch& e, hipStream_t stream);
 void launch_quantize_grouped_ef_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate

@@ -476,6 +476,21 @@ class Context:
                                               (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
                                               round_mode.value)
 
+    def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
+                                       dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
+                                       _device_ptrs: bool = False) -> None:
+        """``reduce_quantize_grouped_ptr`` with error feedback on the re-quantization (``piquant_hip_reduce_quantize_grouped_ef``: one launch for up to
+        16 terms): quantizes ``acc + sum_i dequantize_grouped(input i) + residual`` and leaves what the quantization lost in ``residual`` (``numel``
+        elements of ``dtype_acc``).  The bytes of grouped dequantize ADD per term into ``acc`` followed by ``quantize_grouped_ef_ptr(acc, residual)``;
+        ``acc`` is unspecified afterwards."""
+        n = len(ptrs_in)
+        assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
+        self.assume_device_pointers(_device_ptrs)
+        m = max(n, 1)
+        C.piquant_hip_reduce_quantize_grouped_ef(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, (_C.c_void_p * m)(*ptrs_in), (_C.c_void_p * m)(*scales_in),
+                                                 (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                                 zero_points_ptr, round_mode.value)
+
     def quantize_grouped_ef_ptr(self, ptr_in: int, dtype_in: DataType, ptr_residual: int, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
                                 scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         """Group-wise quantize with error feedback (``piquant_hip_quantize_grouped_ef``): quantizes ``in + residual`` with computed per-group

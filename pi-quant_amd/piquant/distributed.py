@@ -545,6 +545,17 @@ class _DeviceOps:
                                                   [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp, self._mode(round_mode),
                                                   _device_ptrs=True)
 
+    def reduce_encode_grouped_ef(self, bufs, acc: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str,
+                                 group_size: int) -> None:
+        """reduce_encode_grouped(acc + residual) with residual <- what that quantization lost, one launch: the terms are added first, then the
+        residual (``acc`` is scratch afterwards)."""
+        n = acc.numel()
+        recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+        sc, zp, data = self._record(buf, n, qdtype, group_size)
+        self._cx(acc).reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[2] for r in recs],
+                                                     [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp,
+                                                     self._mode(round_mode), _device_ptrs=True)
+
 
 def _exchange(send: torch.Tensor, recv: torch.Tensor, nxt: int, prv: int, group) -> None:
     """Send `send` to the next rank of the ring while receiving `recv` from the previous one.  RCCL (backend nccl)
@@ -683,6 +694,7 @@ def quantized_all_reduce(
     timeout: Optional[float] = None,
     group_size: Optional[int] = None,
     error_feedback: Optional[torch.Tensor] = None,
+    error_feedback_requantize: bool = False,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -704,9 +716,19 @@ def quantized_all_reduce(
     is part of the next step's contribution instead of being thrown away.  In the mesh schedule that is the one batched encode of the peers' chunks
     (still one launch per 16 chunks); in the ring the first encode of chunk ``rank``.  Slices the schedule contributes unquantized -- the mesh's own
     chunk, the ring's other chunks -- are neither read nor written, and the re-quantizations of partial sums stay as they are.  A residual
-    therefore belongs to one (world size, rank, algorithm): carry it over only between all-reduces of the same shape in the same group with the
-    same schedule.  Without ``group_size``, or with ``transport='p2p'``, ``error_feedback`` raises ValueError before anything moves; ``None``
-    (the default) leaves every byte and every launch as it was.  A one-rank group returns at once and leaves the residual alone.
+    therefore belongs to one (world size, rank, algorithm, ``error_feedback_requantize``): carry it over only between all-reduces of the same
+    shape in the same group with the same schedule and the same flag.  Without ``group_size``, or with ``transport='p2p'``, ``error_feedback``
+    raises ValueError before anything moves; ``None`` (the default) leaves every byte and every launch as it was.  A one-rank group returns at
+    once and leaves the residual alone.
+
+    ``error_feedback_requantize`` (``error_feedback`` only; default False: every byte and every launch as without it): the residual also covers
+    the SECOND quantization every value meets, the re-quantization of a partial sum, whose rounding error is otherwise thrown away identically on
+    every rank.  The mesh owner's ``reduce_quantize_grouped`` becomes ``reduce_quantize_grouped_ef`` on the rank's OWN chunk of the residual
+    (still three launches per all-reduce, and every slice of the residual is now used); every hop of the ring becomes
+    ``reduce_quantize_grouped_ef`` on chunk ``(rank - step - 1) % world`` of the residual, so that with the first encode each rank touches each
+    chunk of its residual exactly once per all-reduce.  The residual is added after the received terms.  With it the sum over steps of the
+    results differs from the sum of the inputs by what the ranks' residuals hold (up to roundings in the tensor's dtype): the all-reduce is
+    conservative over steps.  ValueError before anything moves without ``error_feedback``, without ``group_size`` or with ``transport='p2p'``.
 
     ``transport='p2p'`` (``algorithm='direct'`` only, one node; EXPERIMENTAL until it has run between two GPUs): no collective at all -- the
     encode kernels store into the peers' receive buffers over xGMI and flags order the steps (``quantized_all_reduce_direct``).  ``timeout``
@@ -743,9 +765,10 @@ def quantized_all_reduce(
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
+    _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
-                                           group_size=group_size, error_feedback=error_feedback, _ops=_ops,
+                                           group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize, _ops=_ops,
                                            _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
@@ -760,7 +783,7 @@ def quantized_all_reduce(
     nxt = dist.get_global_rank(group, (rank + 1) % world) if group is not None else (rank + 1) % world
     prv = dist.get_global_rank(group, (rank - 1) % world) if group is not None else (rank - 1) % world
     if group_size is not None:
-        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, error_feedback)
+        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, error_feedback, error_feedback_requantize)
     max_bytes = max(qdt.packed_nbytes(e - b) for b, e in chunks) + _HEADER_BYTES
     send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
@@ -815,6 +838,7 @@ def quantized_all_reduce_direct(
     timeout: Optional[float] = None,
     group_size: Optional[int] = None,
     error_feedback: Optional[torch.Tensor] = None,
+    error_feedback_requantize: bool = False,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -846,11 +870,16 @@ def quantized_all_reduce_direct(
 
     ``error_feedback``: the residual of ``quantized_all_reduce`` -- step 1 becomes one batched ``quantize_grouped_ef`` launch on the peers'
     chunks of the tensor and of the residual; the rank's own chunk of the residual is neither read nor written.
+
+    ``error_feedback_requantize``: steps 3-4 become one ``reduce_quantize_grouped_ef`` launch on the rank's own chunk of the residual (added
+    after the G-1 received chunks), which then holds what the owner's quantization lost; every slice of the residual is used.  A residual
+    belongs to one (world size, rank, algorithm, ``error_feedback_requantize``).
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
+    _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
@@ -868,7 +897,7 @@ def quantized_all_reduce_direct(
     if transport != 'collective':
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     if group_size is not None:
-        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, error_feedback)
+        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, error_feedback, error_feedback_requantize)
     send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
     recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
 
@@ -921,10 +950,24 @@ def _check_error_feedback(residual, tensor: torch.Tensor, group_size, transport:
     _check_residual(residual, tensor, 'error_feedback')
 
 
-def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, residual=None):
+def _check_error_feedback_requantize(requantize: bool, residual, group_size, transport: str) -> None:
+    """ValueError before anything moves: error feedback on the re-quantizations without a residual, without the grouped wire or over the
+    peer-to-peer transport."""
+    if not requantize:
+        return
+    if residual is None:
+        raise ValueError('error_feedback_requantize=True needs error_feedback= (the residual that takes what the re-quantizations lose)')
+    if group_size is None:
+        raise ValueError('error_feedback_requantize=True needs the grouped wire: pass group_size=')
+    if transport == 'p2p':
+        raise ValueError("error_feedback_requantize=True is not supported with transport='p2p'; use transport='collective'")
+
+
+def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, residual=None, requantize=False):
     """The ring of ``quantized_all_reduce`` on the grouped wire: the same hops with quantize_grouped / reduce_quantize_grouped (one term) /
     dequantize_grouped (SET) in place of the per-chunk calls.  ``residual``: the first encode (chunk ``rank``, this rank's own values) is
-    quantize_grouped_ef on that chunk of the residual; no other chunk of it is touched."""
+    quantize_grouped_ef on that chunk of the residual; no other chunk of it is touched -- unless ``requantize``: then every hop is
+    reduce_quantize_grouped_ef on its chunk of the residual, and each chunk of it is used exactly once."""
     def wire(idx):
         b, e = chunks[idx]
         return flat[b:e], grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
@@ -945,7 +988,11 @@ def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops
         x_recv, n_recv = wire((rank - step - 1) % world)
         _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
         if x_recv.numel():
-            ops.reduce_encode_grouped([recv[:n_recv]], x_recv, nxt_send[:n_recv], quant_dtype, round_mode, group_size)
+            if requantize:
+                b, e = chunks[(rank - step - 1) % world]
+                ops.reduce_encode_grouped_ef([recv[:n_recv]], x_recv, residual.view(-1)[b:e], nxt_send[:n_recv], quant_dtype, round_mode, group_size)
+            else:
+                ops.reduce_encode_grouped([recv[:n_recv]], x_recv, nxt_send[:n_recv], quant_dtype, round_mode, group_size)
         send, nxt_send = nxt_send, send
         n_cur = n_recv
     if world == 1 and n_cur:   # test hook only: the encoded chunk makes one trip through the transport, to this rank itself
@@ -965,10 +1012,11 @@ def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops
     return tensor
 
 
-def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, residual=None):
+def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, residual=None, requantize=False):
     """The mesh schedule of ``quantized_all_reduce_direct`` on the grouped wire: one batched quantize_grouped, the all-to-all, ONE
     reduce_quantize_grouped over the G-1 received chunks (increasing rank order), the all-gather, one batched dequantize_grouped.
-    ``residual``: the batched encode is quantize_grouped_ef on the peers' chunks of the residual; the rank's own chunk of it is not touched."""
+    ``residual``: the batched encode is quantize_grouped_ef on the peers' chunks of the residual; the rank's own chunk of it is not touched --
+    unless ``requantize``: then the owner's launch is reduce_quantize_grouped_ef on that chunk."""
     def wire_len(idx):
         b, e = chunks[idx]
         return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
@@ -990,8 +1038,11 @@ def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, o
     n_own = wire_len(rank)
     mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
     if x_own.numel():
-        ops.reduce_encode_grouped([recv[i * slot: i * slot + n_own] for i in range(world) if i != rank], x_own, mine[:n_own], quant_dtype, round_mode,
-                                  group_size)
+        terms = [recv[i * slot: i * slot + n_own] for i in range(world) if i != rank]
+        if requantize:
+            ops.reduce_encode_grouped_ef(terms, x_own, residual.view(-1)[b_own:e_own], mine[:n_own], quant_dtype, round_mode, group_size)
+        else:
+            ops.reduce_encode_grouped(terms, x_own, mine[:n_own], quant_dtype, round_mode, group_size)
     gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)   # not `recv`: the launch above is still reading it
     _all_gather(mine, gathered, group)
     full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]

@@ -611,6 +611,53 @@ def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: 
     return out, out_scales, out_zero_points
 
 
+def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int = 128,
+                               round_mode: str = 'nearest', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                               out_scales: Optional[torch.Tensor] = None,
+                               out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``reduce_quantize_grouped`` with error feedback on the re-quantization, in one launch (up to 16 terms): quantizes
+    ``y = acc + dequantize_grouped(tensors[0]) + ... + dequantize_grouped(tensors[k - 1]) + residual`` with computed per-group parameters and
+    replaces ``residual`` by ``y - dequantize_grouped(quantized)``.  The two-call identity: the bytes, scales, zero points and residual are exactly
+    those of ``dequantize_grouped(tensors[i], ..., reduce_op='add', out=acc)`` for every i in order (the running sum rounded to ``acc``'s dtype after
+    each term) followed by ``quantize_grouped_ef(acc, residual)`` -- the residual is added AFTER the terms.  ``residual`` is a contiguous tensor of
+    ``acc``'s dtype, device and numel that the caller keeps between steps (zeros before the first); the terms are as for
+    ``reduce_quantize_grouped``.  Returns (out, out_scales, out_zero_points); ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
+    piquant_hip_reduce_quantize_grouped_ef)."""
+    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _check_group_size(group_size)
+    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
+             f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
+    _require(isinstance(acc, torch.Tensor) and acc.dtype in _DEQUANT_TYPES, 'acc must be a float32 or bfloat16 tensor')
+    _check_residual(residual, acc)
+    _check_float_input(acc, 'acc')
+    _require(acc.is_contiguous(), 'acc must be contiguous (it is the accumulator)')
+    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    numel = acc.numel()
+    ngroups = num_groups(numel, group_size)
+    qdt = torch_to_piquant_dtype(dtype)
+    for i, (t, sc, zp) in enumerate(zip(tensors, scales, zero_points)):
+        _check_packed_in(t, qdt, numel, acc.device, f'tensors[{i}]')
+        _check_group_params(sc, zp, ngroups)
+        _require(sc.device == acc.device and zp.device == acc.device, f'scales[{i}] and zero_points[{i}] must live on {acc.device}')
+    if out is None:
+        out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
+    else:
+        _check_packed_out(out, qdt, numel, acc.device)
+    if out_scales is None:
+        out_scales = torch.empty(ngroups, dtype=torch.float32, device=acc.device)
+        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=acc.device)
+    else:
+        _check_group_params(out_scales, out_zero_points, ngroups)
+        _require(out_scales.device == acc.device and out_zero_points.device == acc.device, f'out_scales and out_zero_points must live on {acc.device}')
+    ctx = _ctx_for(acc, ctx)
+    ctx.reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [t.data_ptr() for t in tensors],
+                                       [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], out.data_ptr(), qdt, numel, group_size,
+                                       out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, out_scales, out_zero_points
+
+
 def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
                               outs=None, out_scales=None, out_zero_points=None):
     """``quantize_grouped_ef`` of several independent (tensor, residual) pairs (one dtype pair, group size and round mode) with one kernel launch

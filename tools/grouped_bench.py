@@ -15,7 +15,12 @@ quantize_grouped -> dequantize_grouped -> torch.sub), to quantize_grouped alone 
 of one next to the single quantize_grouped call (the error-feedback single call is a batch of one); and the kernel time of one rank's replayed
 8-way grouped mesh all-reduce with and without error feedback.  Writes profiles/grouped_ef_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows reduce_ef: the fused reduce_quantize_grouped_ef (fp32 acc with uint8 and uint4 terms, k = 1 and k = 7; bf16 acc with uint4 terms, k = 1;
+G = 128) next to the two-step composition that defines it (k grouped dequantize ADD launches + quantize_grouped_ef) in the same run, with the
+byte ratio of each row and the target fused / composition <= 1.15 x that ratio; and the kernel time of one rank's replayed 8-way grouped mesh
+all-reduce with error feedback, with error_feedback_requantize off and on.  Writes profiles/grouped_reduce_ef_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -269,15 +274,126 @@ def ef_rows(ctx, dev, stream, args, G=128, world=8):
     return rows
 
 
+def reduce_ef_rows(ctx, dev, stream, args, G=128, world=8):
+    """fused reduce + error-feedback quantize against the two-step composition that defines it; the mesh with the flag off and on"""
+    import piquant.distributed as D
+
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(4)
+    for fname, qname, k in (("f32", "uint8", 1), ("f32", "uint8", 7), ("f32", "uint4", 1), ("f32", "uint4", 7), ("bf16", "uint4", 1)):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(NUMEL)
+        fbytes = NUMEL * esize
+        fused_bytes = 3 * fbytes + (k + 1) * (nq + 5 * ng)                    # acc, residual in and out; k terms in, one record out
+        comp_bytes = (2 * k + 3) * fbytes + (k + 1) * (nq + 5 * ng)           # acc in and out per term; then acc, residual in and out
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        accs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g).to(tdt) for _ in range(nbuf)]
+        ress = [(torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g) * 0.01).to(tdt) for _ in range(nbuf)]
+        terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.reduce_quantize_grouped_ef_ptr(accs[i].data_ptr(), fdt, ress[i].data_ptr(), [t.data_ptr() for t in terms[i]], [t.data_ptr() for t in tsc[i]],
+                                               [t.data_ptr() for t in tzp[i]], outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                               piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def two_step(i):
+            for t, s_, z_ in zip(terms[i], tsc[i], tzp[i]):
+                ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, accs[i].data_ptr(), fdt, NUMEL, G, s_.data_ptr(), z_.data_ptr(), piquant.ReduceOp.ADD,
+                                           _device_ptrs=True)
+            ctx.quantize_grouped_ef_ptr(accs[i].data_ptr(), fdt, ress[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        pair = f"{fname}+{k}x{qname}"
+        us_t, s_t = timed(two_step, nbuf, args.windows, per_window, stream)
+        two = row("reduce_ef_two_step", pair, G, us_t, comp_bytes, s_t)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("reduce_quantize_grouped_ef", pair, G, us_f, fused_bytes, s_f)
+        fr["over_two_step"] = round(us_f / us_t, 3)
+        fr["bytes_over_two_step"] = round(fused_bytes / comp_bytes, 3)
+        fr["over_byte_ratio"] = round(fr["over_two_step"] / fr["bytes_over_two_step"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / two-step = {fr['over_two_step']:.3f} (bytes {fr['bytes_over_two_step']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}", flush=True)
+        rows += [two, fr]
+        del accs, ress, terms, tsc, tzp, outs, sc, zs
+        torch.cuda.empty_cache()
+
+    # one rank's three kernels of an 8-way grouped mesh all-reduce with error feedback (no wire: stand-in receive buffers), replayed from a graph
+    ops = D._DeviceOps(ctx)
+    x = torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g)
+    res = torch.zeros(NUMEL, device=dev)
+    for qname, bits in (("uint8", 8), ("quint4x2", 4)):
+        qdt = getattr(torch, qname)
+        chunks = D.ring_chunks(NUMEL, world, bits)
+        gbytes = [D.grouped_wire_layout(e - b, G, bits).nbytes for b, e in chunks]
+        slot = -(-max(gbytes) // 16) * 16
+        bufs = torch.zeros(world * slot, dtype=torch.uint8, device=dev)
+        mine = torch.zeros(slot, dtype=torch.uint8, device=dev)
+        for j, (b, e) in enumerate(chunks):
+            ops.encode_grouped(x[b:e], bufs[j * slot: j * slot + gbytes[j]], qdt, "nearest", G)
+        peers = list(range(1, world))
+
+        def mesh(requantize):
+            ops.encode_batch_grouped_ef([x[chunks[j][0]:chunks[j][1]] for j in peers], [res[chunks[j][0]:chunks[j][1]] for j in peers],
+                                        [bufs[j * slot: j * slot + gbytes[j]] for j in peers], qdt, "nearest", G)
+            recv = [bufs[i * slot: i * slot + gbytes[0]] for i in peers]
+            own = x[chunks[0][0]:chunks[0][1]]
+            if requantize:
+                ops.reduce_encode_grouped_ef(recv, own, res[chunks[0][0]:chunks[0][1]], mine[: gbytes[0]], qdt, "nearest", G)
+            else:
+                ops.reduce_encode_grouped(recv, own, mine[: gbytes[0]], qdt, "nearest", G)
+            ops.decode_batch_grouped([bufs[j * slot: j * slot + gbytes[j]] for j in range(world)], [x[chunks[j][0]:chunks[j][1]] for j in range(world)], qdt,
+                                     "set", G)
+
+        r = {"kind": "mesh_kernels_per_rank", "pair": f"f32->{qname}", "group_size": G, "world": world, "launches_per_all_reduce": 3}
+        for name, requantize in (("requantize_off_us", False), ("requantize_on_us", True)):
+            x.uniform_(-1, 1, generator=g)
+            res.zero_()
+            for _ in range(3):
+                mesh(requantize)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream()
+            with torch.cuda.stream(side):
+                mesh(requantize)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(graph, stream=side):
+                    mesh(requantize)
+                graph.replay()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+            r[name] = round(e0.elapsed_time(e1) * 1e3 / 20, 1)
+        r["on_over_off"] = round(r["requantize_on_us"] / r["requantize_off_us"], 3)
+        print(f"mesh f32->{qname}: {r['requantize_off_us']} us with error_feedback_requantize off, {r['requantize_on_us']} us with it on", flush=True)
+        rows.append(r)
+    ctx.set_stream(stream.cuda_stream)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json"}[args.rows])
+        args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
+                                                   "reduce_ef": "grouped_reduce_ef_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -291,6 +407,8 @@ def main():
         rows = reduce_rows(ctx, dev, stream, args)
     if args.rows == "ef":
         rows = ef_rows(ctx, dev, stream, args)
+    if args.rows == "reduce_ef":
+        rows = reduce_ef_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
