@@ -255,6 +255,41 @@ PIQUANT_EXPORT void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx
                                                           size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
                                                           piquant_round_mode_t mode);
 
+/* The three error-feedback calls with the residual's type named: a FLOAT32 residual for a BFLOAT16 tensor.  A bfloat16 residual rounds y = x + r
+ * and r <- y - d to bfloat16, each by up to 2^-9 |y| -- as much as the half step of a uint8 wire it is there to keep; a float32 residual keeps
+ * what the wire loses to float32 precision while the tensor (and the wire, and what receivers decode into) stay as they are.
+ * dtype_residual == dtype_in (dtype_acc): the call IS its counterpart above.  (dtype_in, dtype_residual) == (BF16, F32): `residual` holds numel
+ * float32 elements and the call writes exactly the bytes of piquant_hip_quantize_grouped_ef(widen(x), F32, residual, ...), widen(x) being x
+ * converted to float32 (exact):
+ *   1. y[i] = rn_f32(widen(x[i]) + residual[i]);
+ *   2. (out, scales, zero_points) = piquant_hip_quantize_grouped(y) in the float32 pipeline with computed parameters;
+ *   3. d[i] = element i of piquant_hip_dequantize_grouped(out, scales, zero_points, dtype F32, PIQUANT_REDUCE_OP_SET);
+ *   4. residual[i] = rn_f32(y[i] - d[i]), a subtraction of its own, never contracted into an fma.
+ * The NaN rule, degenerate and clamped groups, one stochastic threshold per call (per batch) and the per-element mode indexing the global element
+ * are the float32 call's.  x is never written; nothing at or past the tensor's end is touched.  ONE launch per call and per 16 tensors of a batch,
+ * 11 bytes of memory traffic per element with a uint8 wire, against 19 for the widened copy plus the float32 call.  The streaming kernels need
+ * residual and out 16-byte aligned and x 8-byte aligned; anything else goes through a guarded element-by-element launch that writes the same bytes.
+ * A receiver that decodes the wire into bfloat16 forms d in the bfloat16 dequantize form, which before its rounding to bfloat16 may differ from
+ * the sender's float32-form d by at most one float32 ulp.
+ * piquant_hip_reduce_quantize_grouped_ef_mixed with (BF16, F32) runs as the composition that defines it: piquant_hip_dequantize_grouped(...,
+ * PIQUANT_REDUCE_OP_ADD) of every term into the bfloat16 acc, in order, then piquant_hip_quantize_grouped_ef_mixed(acc, residual) with the
+ * call's one threshold: count + 1 launches.
+ * Any other pair of types aborts.  Device (or pinned) buffers only; stream-ordered on the context's stream, always behind the previous call; no
+ * host synchronisation, no allocation (hipGraph-capturable); empty tensors are skipped. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_ef_mixed(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual,
+                                                          piquant_dtype_t dtype_residual, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                                          size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_ef_mixed_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                                void* const* residuals, piquant_dtype_t dtype_residual, void* const* outputs,
+                                                                piquant_dtype_t dtype_out, const size_t* numels, size_t group_size,
+                                                                float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                                piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual,
+                                                                 piquant_dtype_t dtype_residual, const void* const* inputs,
+                                                                 const float* const* input_scales, const uint8_t* const* input_zero_points,
+                                                                 size_t count, void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size,
+                                                                 float* scales, uint8_t* zero_points, piquant_round_mode_t mode);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

@@ -865,4 +865,160 @@ void piquant_hip_reduce_quantize_grouped_ef(piquant_context_t* ctx, void* acc, p
     if (ctx->blocking) wait_stream(ctx);
 }
 
+// Error feedback with the residual's type named (include/piquant_hip.h, piquant_hip_quantize_grouped_ef_mixed): the residual's type equal to the
+// tensor's forwards to the calls above; a bfloat16 tensor with a float32 residual runs the kernels of kernels_grouped_ef_f32r.hip.
+static bool grouped_ef_f32_residual(const char* what, piquant_dtype_t dtype_in, piquant_dtype_t dtype_residual) {
+    if (dtype_residual == dtype_in) return false;
+    if (dtype_in == PIQUANT_DTYPE_BF16 && dtype_residual == PIQUANT_DTYPE_F32) return true;
+    panic("%s: a %s residual for a %s tensor (the tensor's type, or float32 for a bfloat16 tensor, is needed)", what, dtype_of(dtype_residual).name,
+          dtype_of(dtype_in).name);
+}
+
+// the streaming kernels' rule: 16-byte residual and output, 8-byte tensor (its lane-row is four bfloat16 elements)
+static inline bool grouped_f32r_aligned(const void* in, const void* residual, const void* out) {
+    return (reinterpret_cast<uintptr_t>(in) & 7u) == 0 && grouped_aligned16(residual) && grouped_aligned16(out);
+}
+
+void piquant_hip_quantize_grouped_ef_mixed_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
+                                                 piquant_dtype_t dtype_residual, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                 size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                 piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_ef_mixed_batch: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    if (!grouped_ef_f32_residual("piquant_hip_quantize_grouped_ef_mixed_batch", dtype_in, dtype_residual)) {
+        piquant_hip_quantize_grouped_ef_batch(ctx, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, mode);
+        return;
+    }
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_ef_mixed_batch: NULL argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
+    GroupedEfBatchLaunch b {};
+    b.group_size = static_cast<int64_t>(group_size);
+    b.dt_in = dtype_in;
+    b.dt_out = dtype_out;
+    b.round_mode = rm.round_mode;
+    b.threshold = rm.threshold;
+    b.seed = rm.seed;
+    b.index_base = rm.index_base;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        if (!inputs[i] || !residuals[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_ef_mixed: NULL buffer %zu", i);
+        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_ef_mixed: scales %zu must be 4-byte aligned", i);
+        const Resolved rin = ctx->resolve_ptr(inputs[i]), rres = ctx->resolve_ptr(residuals[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]),
+                       rz = resolve(zero_points[i]);
+        if (rin.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
+            panic("piquant_hip_quantize_grouped_ef_mixed needs device (or pinned) buffers");
+        if (reinterpret_cast<uintptr_t>(rin.dev) % 2 != 0 || reinterpret_cast<uintptr_t>(rres.dev) % 4 != 0)
+            panic("quantize_grouped_ef_mixed: tensor %zu or its residual is not aligned to its element size", i);
+        const int t = b.count;
+        b.in[t] = rin.dev;
+        b.residual[t] = rres.dev;
+        b.out[t] = rout.dev;
+        b.scales[t] = static_cast<float*>(rs.dev);
+        b.zero_points[t] = static_cast<uint8_t*>(rz.dev);
+        b.numel[t] = static_cast<int64_t>(numels[i]);
+        if (!grouped_f32r_aligned(rin.dev, rres.dev, rout.dev)) {   // the guarded kernel, same bytes
+            launch_quantize_grouped_ef_f32r_guarded(b, t, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        if (++b.count == kGroupedBatchMaxTensors) {
+            launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_ef_mixed(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, piquant_dtype_t dtype_residual,
+                                           void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                           piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_ef_mixed: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    if (!grouped_ef_f32_residual("piquant_hip_quantize_grouped_ef_mixed", dtype_in, dtype_residual)) {
+        piquant_hip_quantize_grouped_ef(ctx, in, dtype_in, residual, out, dtype_out, numel, group_size, scales, zero_points, mode);
+        return;
+    }
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    piquant_hip_quantize_grouped_ef_mixed_batch(ctx, &in, dtype_in, &residual, dtype_residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1,
+                                                mode);
+}
+
+// A bfloat16 accumulator with a float32 residual runs as the composition that defines the call: every term by grouped dequantize ADD into acc, in
+// order, then the mixed single call on (acc, residual) with the call's one threshold (a fused mixed reduce kernel: DESIGN.md 10).
+void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual,
+                                                  piquant_dtype_t dtype_residual, const void* const* inputs, const float* const* input_scales,
+                                                  const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                                  size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_reduce_quantize_grouped_ef_mixed: context is NULL");
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    if (!grouped_ef_f32_residual("piquant_hip_reduce_quantize_grouped_ef_mixed", dtype_acc, dtype_residual)) {
+        piquant_hip_reduce_quantize_grouped_ef(ctx, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel, group_size,
+                                               scales, zero_points, mode);
+        return;
+    }
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    if (!acc || !residual || !out || !scales || !zero_points) panic("reduce_quantize_grouped_ef_mixed: NULL buffer");
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped_ef_mixed: NULL argument");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped_ef_mixed: scales must be 4-byte aligned");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const Resolved racc = ctx->resolve_ptr(acc), rres = ctx->resolve_ptr(residual), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
+    if (racc.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
+        panic("piquant_hip_reduce_quantize_grouped_ef_mixed needs device (or pinned) buffers");
+    if (reinterpret_cast<uintptr_t>(racc.dev) % 2 != 0 || reinterpret_cast<uintptr_t>(rres.dev) % 4 != 0)
+        panic("reduce_quantize_grouped_ef_mixed: acc or the residual is not aligned to its element size");
+    std::vector<GroupedDequantLaunch> adds(count);
+    for (size_t i = 0; i < count; ++i) {
+        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped_ef_mixed: NULL input %zu", i);
+        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped_ef_mixed: input scales %zu must be 4-byte aligned", i);
+        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
+        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped_ef_mixed needs device (or pinned) buffers");
+        GroupedDequantLaunch& d = adds[i];
+        d.in = ri.dev;
+        d.out = racc.dev;
+        d.numel = static_cast<int64_t>(numel);
+        d.group_size = static_cast<int64_t>(group_size);
+        d.scales = static_cast<const float*>(rsi.dev);
+        d.zero_points = static_cast<const uint8_t*>(rzi.dev);
+        d.dt_in = dtype_out;
+        d.dt_out = dtype_acc;
+        d.op = OP_ADD;
+    }
+    QuantLaunch rm {};
+    fill_round_mode(ctx, rm, mode);   // the call's one threshold
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
+    for (size_t i = 0; i < count; ++i) launch_dequantize_grouped(adds[i], ctx->stream, ctx->num_cu);
+    GroupedEfBatchLaunch b {};
+    b.in[0] = racc.dev;
+    b.residual[0] = rres.dev;
+    b.out[0] = rout.dev;
+    b.scales[0] = static_cast<float*>(rs.dev);
+    b.zero_points[0] = static_cast<uint8_t*>(rz.dev);
+    b.numel[0] = static_cast<int64_t>(numel);
+    b.group_size = static_cast<int64_t>(group_size);
+    b.dt_in = dtype_acc;
+    b.dt_out = dtype_out;
+    b.round_mode = rm.round_mode;
+    b.threshold = rm.threshold;
+    b.seed = rm.seed;
+    b.index_base = rm.index_base;
+    if (grouped_f32r_aligned(racc.dev, rres.dev, rout.dev)) {
+        b.count = 1;
+        launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
+    } else {
+        launch_quantize_grouped_ef_f32r_guarded(b, 0, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
 }  // extern "C"

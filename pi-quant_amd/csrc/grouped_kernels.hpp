@@ -1003,4 +1003,167 @@ quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, u
     }
 }
 
+// ---- Error feedback with a float32 residual for a bfloat16 tensor (piquant_hip_quantize_grouped_ef_mixed): the bytes of
+// quantize_grouped_ef(widen(x), residual) in the float32 pipeline, without the widened copy of x ever reaching memory.  The tile is the float32
+// one, GroupedQuantTile<DT_F32, BITS, G>: a lane-row is four elements, which of x are 8 bytes (one global_load_dwordx2, 512 contiguous bytes per
+// wave-row) widened into raw[r][e] = bits << 16, and of the residual one 16-byte vector.  From there on everything is grouped_ef_chunk<DT_F32>'s:
+// y = rn_f32(widen(x) + r), the float32 quantize chunk body (KEEP), r <- rn_f32(y - d) with d the float32 dequantize form.  x is never written.
+
+// one wave's chunk of the bfloat16 tensor `in` as NV rows of four elements, still packed (8 bytes a lane-row); elements at or past numel read as
+// quiet NaNs.  Load only: nothing here uses what it loads, so that the residual's loads can be issued behind these without a wait between them.
+template <int NV>
+__device__ __forceinline__ void grouped_load_bf16x4(const void* in, int64_t numel, int64_t v0, int lane, bool full, u32x2 (&t)[NV]) {
+    const u32x2* in8 = static_cast<const u32x2*>(in);
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < NV; ++r) t[r] = ld<true>(in8 + v0 + r * 64 + lane);
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const int64_t vec = v0 + r * 64 + lane;
+        if ((vec + 1) * 4 <= numel) {
+            t[r] = ld<true>(in8 + vec);
+        } else {
+            t[r] = u32x2 {0x7fc07fc0u, 0x7fc07fc0u};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {   // unrolled: constant register indices
+                const int64_t i = vec * 4 + e;
+                if (i >= numel) continue;
+                t[r][e >> 1] = (t[r][e >> 1] & ((e & 1) ? 0x0000ffffu : 0xffff0000u)) |
+                               (static_cast<uint32_t>(static_cast<const uint16_t*>(in)[i]) << ((e & 1) * 16));
+            }
+        }
+    }
+}
+
+// the packed rows widened to float32 bits: raw[r][e] = bits << 16
+template <int NV>
+__device__ __forceinline__ void grouped_widen_bf16x4(const u32x2 (&t)[NV], u32x4 (&raw)[NV]) {
+#pragma unroll
+    for (int r = 0; r < NV; ++r) raw[r] = u32x4 {t[r][0] << 16, t[r][0] & 0xffff0000u, t[r][1] << 16, t[r][1] & 0xffff0000u};
+}
+
+// one wave's chunk (NG groups of the float32 tile from group g0 on) of one (bfloat16 tensor, float32 residual) pair; LDS slices as grouped_ef_chunk
+template <int BITS, int MODE, int G>
+__device__ __forceinline__ void grouped_ef_f32r_chunk(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel,
+                                                      float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
+                                                      int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b, float* s_c) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+
+    u32x4 raw[NV];
+    {
+        u32x2 t[NV];
+        u32x4 res[NV];
+        grouped_load_bf16x4<NV>(in, numel, v0, lane, full, t);   // every load of x and of the residual is issued before the first use
+        grouped_load<DT_F32, NV>(residual, numel, v0, lane, full, res);
+        grouped_widen_bf16x4<NV>(t, raw);
+        grouped_add_residual<DT_F32, NV>(raw, res);
+    }
+    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
+    grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
+}
+
+template <int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_f32r_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // {min, max}, then {1/scale, zero point, scale} of the chunk's groups
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t g0 = (static_cast<int64_t>(blockIdx.x) * WAVES + wave) * NG;
+    if (g0 >= ngroups) return;
+    grouped_ef_f32r_chunk<BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+}
+
+// up to kGroupedBatchMax independent pairs in ONE launch, found through the prefix table of quantize_grouped_batch_kernel
+template <int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_f32r_batch_kernel(GroupedEfBatchArgs a, QuantParams p0) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (c >= a.chunk_begin[a.count]) return;
+    int t = 0;
+    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    const int64_t numel = a.numel[t];
+    grouped_ef_f32r_chunk<BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
+                                         (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+}
+
+// Guarded form for buffers of any (element) alignment: one wave per group, element by element, the same bytes.  Correct, not fast.
+template <int BITS, int MODE>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_f32r_scalar_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
+                                       float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, float threshold, uint32_t seed_lo,
+                                       uint32_t seed_hi, uint64_t index_base) {
+    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1, FORM = DequantForm<BITS, DT_F32>::value;
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the group loop is wave-uniform
+    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
+        const int64_t b = g * group_size;
+        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);   // <= 4096: 32-bit offsets inside the group
+        auto y_of = [&](int o) { return __fadd_rn(InVec<DT_BF16>::load_scalar(in, b + o), static_cast<const float*>(residual)[b + o]); };
+        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
+        for (int o0 = 0; o0 < len; o0 += 64) {   // wave-uniform trip counts: a lane past the group's end sits the step out
+            if (o0 + lane < len) {
+                const float x = quieted(y_of(o0 + lane));
+                lo = __builtin_fminf(lo, x);
+                hi = __builtin_fmaxf(hi, x);
+            }
+        }
+        lo = wave_min(lo);   // every lane's loads of the group are complete here: the residual is overwritten below
+        hi = wave_max(hi);
+        float scale;
+        int64_t zp;
+        quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
+        if (lane == 0) {
+            scales[g] = scale;
+            zero_points[g] = static_cast<uint8_t>(zp);
+        }
+        QuantParams p {};   // what is per call, and the group's parameters
+        p.threshold = threshold;
+        p.seed_lo = seed_lo;
+        p.seed_hi = seed_hi;
+        p.index_base = index_base;
+        p.inv_scale = __fdiv_rn(1.0f, scale);
+        p.zp64 = zp;
+        p.zp32 = static_cast<int32_t>(zp);
+        DequantParams d {};
+        d.scale = scale;
+        d.zp32 = p.zp32;
+        d.zp64 = zp;
+        d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);
+        uint8_t* og = out + b / PACK;   // a group starts on a whole packed byte
+        for (int by0 = 0; by0 * PACK < len; by0 += 64) {
+            const int by = by0 + lane;
+            if (by * PACK >= len) continue;
+            uint32_t acc = 0;
+#pragma unroll
+            for (int k = 0; k < PACK; ++k) {
+                const int o = by * PACK + k;
+                if (o >= len) continue;
+                const float y = y_of(o);
+                const uint32_t q = quant_one<MODE, QMAX>(y, p, static_cast<uint64_t>(b + o));
+                acc |= q << (k * BITS);
+                static_cast<float*>(residual)[b + o] = residual_one<DT_F32>(y, dequant_one<FORM>(q, d));
+            }
+            og[by] = static_cast<uint8_t>(acc);
+        }
+    }
+}
+
 }  // namespace pq

@@ -218,6 +218,10 @@ void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t st
 void launch_quantize_grouped_ef_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
 void launch_reduce_quantize_grouped_ef(const GroupedReduceEfLaunch& e, hipStream_t stream);
 void launch_quantize_grouped_ef_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
+// The same two for bfloat16 tensors (b.dt_in == DT_BF16) whose residuals are float32 (kernels_grouped_ef_f32r.hip): the bytes of the float32 call
+// on the widened tensor.  The streaming launch needs residual and out 16-byte aligned and the tensor 8-byte aligned; the guarded one takes anything.
+void launch_quantize_grouped_ef_f32r_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
+void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -478,38 +478,59 @@ class Context:
 
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
-                                       _device_ptrs: bool = False) -> None:
+                                       _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:
         """``reduce_quantize_grouped_ptr`` with error feedback on the re-quantization (``piquant_hip_reduce_quantize_grouped_ef``: one launch for up to
         16 terms): quantizes ``acc + sum_i dequantize_grouped(input i) + residual`` and leaves what the quantization lost in ``residual`` (``numel``
         elements of ``dtype_acc``).  The bytes of grouped dequantize ADD per term into ``acc`` followed by ``quantize_grouped_ef_ptr(acc, residual)``;
-        ``acc`` is unspecified afterwards."""
+        ``acc`` is unspecified afterwards.  ``residual_dtype`` (``None``: ``dtype_acc``) names the residual's type: ``F32`` for a ``BF16`` ``acc`` runs
+        the grouped dequantize ADD calls followed by the mixed ``quantize_grouped_ef_ptr`` (``piquant_hip_reduce_quantize_grouped_ef_mixed``)."""
         n = len(ptrs_in)
         assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
         self.assume_device_pointers(_device_ptrs)
         m = max(n, 1)
+        if residual_dtype is not None:
+            C.piquant_hip_reduce_quantize_grouped_ef_mixed(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, residual_dtype.value, (_C.c_void_p * m)(*ptrs_in),
+                                                           (_C.c_void_p * m)(*scales_in), (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value,
+                                                           numel, group_size, scales_ptr, zero_points_ptr, round_mode.value)
+            return
         C.piquant_hip_reduce_quantize_grouped_ef(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, (_C.c_void_p * m)(*ptrs_in), (_C.c_void_p * m)(*scales_in),
                                                  (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
                                                  zero_points_ptr, round_mode.value)
 
     def quantize_grouped_ef_ptr(self, ptr_in: int, dtype_in: DataType, ptr_residual: int, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
-                                scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+                                scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False,
+                                residual_dtype: Optional[DataType] = None) -> None:
         """Group-wise quantize with error feedback (``piquant_hip_quantize_grouped_ef``): quantizes ``in + residual`` with computed per-group
-        parameters and leaves ``(in + residual) - dequantize(quantized)`` in ``residual`` (``numel`` elements of ``dtype_in``), one launch."""
+        parameters and leaves ``(in + residual) - dequantize(quantized)`` in ``residual`` (``numel`` elements of ``dtype_in``), one launch.
+        ``residual_dtype`` (``None``: ``dtype_in``) names the residual's type: ``F32`` for a ``BF16`` tensor writes the bytes of the float32 call on
+        the widened tensor (``piquant_hip_quantize_grouped_ef_mixed``), still in one launch."""
         assert dtype_in.is_dequantized and dtype_out.is_quantized
         self.assume_device_pointers(_device_ptrs)
+        if residual_dtype is not None:
+            C.piquant_hip_quantize_grouped_ef_mixed(self._ctx, ptr_in, dtype_in.value, ptr_residual, residual_dtype.value, ptr_out, dtype_out.value, numel,
+                                                    group_size, scales_ptr, zero_points_ptr, round_mode.value)
+            return
         C.piquant_hip_quantize_grouped_ef(self._ctx, ptr_in, dtype_in.value, ptr_residual, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
                                           zero_points_ptr, round_mode.value)
 
     def quantize_grouped_ef_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_residual, ptrs_out, dtype_out: DataType, numels, group_size: int,
-                                      scales_ptrs, zero_points_ptrs, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+                                      scales_ptrs, zero_points_ptrs, round_mode: RoundMode, _device_ptrs: bool = False,
+                                      residual_dtype: Optional[DataType] = None) -> None:
         """``quantize_grouped_ef_ptr`` for several independent (tensor, residual) pairs, up to 16 per kernel launch
-        (``piquant_hip_quantize_grouped_ef_batch``); one stochastic threshold for the batch."""
+        (``piquant_hip_quantize_grouped_ef_batch``); one stochastic threshold for the batch and one ``residual_dtype`` (``None``: ``dtype_in``;
+        otherwise ``piquant_hip_quantize_grouped_ef_mixed_batch``)."""
         n = len(ptrs_in)
         assert dtype_in.is_dequantized and dtype_out.is_quantized
         assert n == len(ptrs_residual) == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
+        if residual_dtype is not None:
+            C.piquant_hip_quantize_grouped_ef_mixed_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_residual),
+                                                          residual_dtype.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value, (_C.c_size_t * n)(*numels),
+                                                          group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
+                                                          round_mode.value)
+            return
         C.piquant_hip_quantize_grouped_ef_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_residual),
                                                 (_C.c_void_p * n)(*ptrs_out), dtype_out.value, (_C.c_size_t * n)(*numels), group_size,
                                                 (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n, round_mode.value)

@@ -66,6 +66,11 @@ _DECLS = [
     ('piquant_hip_quantize_grouped_ef', None, [_vp, _vp, _int, _vp, _vp, _int, _sz, _sz, _vp, _vp, _int]),
     ('piquant_hip_quantize_grouped_ef_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _int, C.POINTER(_sz), _sz,
                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _int]),
+    ('piquant_hip_reduce_quantize_grouped_ef_mixed', None, [_vp, _vp, _int, _vp, _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                            _sz, _vp, _int, _sz, _sz, _vp, _vp, _int]),
+    ('piquant_hip_quantize_grouped_ef_mixed', None, [_vp, _vp, _int, _vp, _int, _vp, _int, _sz, _sz, _vp, _vp, _int]),
+    ('piquant_hip_quantize_grouped_ef_mixed_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int,
+                                                           C.POINTER(_sz), _sz, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _int]),
     ('piquant_hip_compute_quant_params_dist', None, [_vp, _vp, _int, _sz, _int, _vp, C.POINTER(_f32), C.POINTER(_i64)]),
     ('piquant_hip_minmax_keys', None, [_vp, _vp, _int, _sz, _vp, _int]),
     ('piquant_hip_peer_alloc', _vp, [_vp, _sz, _int, C.c_uint32, _vp]),

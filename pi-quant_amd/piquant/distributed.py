@@ -512,11 +512,18 @@ class _DeviceOps:
                                                        torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
                                                        [r[1] for r in recs], False, self._mode(round_mode), _device_ptrs=True)
 
+    @staticmethod
+    def _residual_dtype(residual: torch.Tensor, x: torch.Tensor):
+        """``residual_dtype=`` of the ``*_ef*_ptr`` methods: None (the same-dtype symbol) unless the residual's dtype differs from the tensor's."""
+        return None if residual.dtype == x.dtype else torch_to_piquant_dtype(residual.dtype)
+
     def encode_grouped_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
-        """encode_grouped(x + residual) with residual <- (x + residual) - what the record decodes to, one launch."""
+        """encode_grouped(x + residual) with residual <- (x + residual) - what the record decodes to, one launch.  The residual's dtype goes down
+        with it: float32 for a bfloat16 ``x`` is the float32 pipeline on the widened ``x``."""
         sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
         self._cx(x).quantize_grouped_ef_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), residual.data_ptr(), data, torch_to_piquant_dtype(qdtype),
-                                            x.numel(), group_size, sc, zp, self._mode(round_mode), _device_ptrs=True)
+                                            x.numel(), group_size, sc, zp, self._mode(round_mode), _device_ptrs=True,
+                                            residual_dtype=self._residual_dtype(residual, x))
 
     def encode_batch_grouped_ef(self, xs, residuals, bufs, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped_ef(xs[i], residuals[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
@@ -524,7 +531,8 @@ class _DeviceOps:
             recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
             self._cx(xs[0]).quantize_grouped_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r.data_ptr() for r in residuals],
                                                           [r[2] for r in recs], torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size,
-                                                          [r[0] for r in recs], [r[1] for r in recs], self._mode(round_mode), _device_ptrs=True)
+                                                          [r[0] for r in recs], [r[1] for r in recs], self._mode(round_mode), _device_ptrs=True,
+                                                          residual_dtype=self._residual_dtype(residuals[0], xs[0]))
 
     def decode_batch_grouped(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
         """decode_grouped(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
@@ -548,13 +556,13 @@ class _DeviceOps:
     def reduce_encode_grouped_ef(self, bufs, acc: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str,
                                  group_size: int) -> None:
         """reduce_encode_grouped(acc + residual) with residual <- what that quantization lost, one launch: the terms are added first, then the
-        residual (``acc`` is scratch afterwards)."""
+        residual (``acc`` is scratch afterwards).  A float32 residual for a bfloat16 ``acc``: the decode ADD launches, then the mixed encode."""
         n = acc.numel()
         recs = [self._record(b, n, qdtype, group_size) for b in bufs]
         sc, zp, data = self._record(buf, n, qdtype, group_size)
         self._cx(acc).reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[2] for r in recs],
                                                      [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp,
-                                                     self._mode(round_mode), _device_ptrs=True)
+                                                     self._mode(round_mode), _device_ptrs=True, residual_dtype=self._residual_dtype(residual, acc))
 
 
 def _exchange(send: torch.Tensor, recv: torch.Tensor, nxt: int, prv: int, group) -> None:
@@ -719,7 +727,10 @@ def quantized_all_reduce(
     therefore belongs to one (world size, rank, algorithm, ``error_feedback_requantize``): carry it over only between all-reduces of the same
     shape in the same group with the same schedule and the same flag.  Without ``group_size``, or with ``transport='p2p'``, ``error_feedback``
     raises ValueError before anything moves; ``None`` (the default) leaves every byte and every launch as it was.  A one-rank group returns at
-    once and leaves the residual alone.
+    once and leaves the residual alone.  A bfloat16 tensor also takes a FLOAT32 residual (same device and numel), in both schedules and with
+    ``error_feedback_requantize``: the encodes then run in float32 on the widened values and the residual keeps what the wire loses to float32
+    precision instead of rounding it to bfloat16 twice per step (each up to 2^-9 |y|, as much as a uint8 half step); the wire and what receivers
+    decode into stay as they are.  No other pair of dtypes is accepted.
 
     ``error_feedback_requantize`` (``error_feedback`` only; default False: every byte and every launch as without it): the residual also covers
     the SECOND quantization every value meets, the re-quantization of a partial sum, whose rounding error is otherwise thrown away identically on
@@ -868,7 +879,7 @@ def quantized_all_reduce_direct(
     one ``reduce_quantize_grouped`` launch over the G-1 received chunks in increasing rank order, the decode one batched ``dequantize_grouped``
     launch.  Collective transport only.
 
-    ``error_feedback``: the residual of ``quantized_all_reduce`` -- step 1 becomes one batched ``quantize_grouped_ef`` launch on the peers'
+    ``error_feedback``: the residual of ``quantized_all_reduce`` (the tensor's dtype, or float32 for a bfloat16 tensor) -- step 1 becomes one batched ``quantize_grouped_ef`` launch on the peers'
     chunks of the tensor and of the residual; the rank's own chunk of the residual is neither read nor written.
 
     ``error_feedback_requantize``: steps 3-4 become one ``reduce_quantize_grouped_ef`` launch on the rank's own chunk of the residual (added

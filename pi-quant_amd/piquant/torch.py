@@ -566,12 +566,19 @@ def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128
 
 
 def _check_residual(residual, tensor: torch.Tensor, what: str = 'residual') -> None:
-    """The residual of an error-feedback call is written by raw pointer: a contiguous device tensor of the input's dtype, device and numel."""
+    """The residual of an error-feedback call is written by raw pointer: a contiguous device tensor of the input's device and numel, and of the
+    input's dtype -- or float32 for a bfloat16 input (the float32 residual, ``piquant_hip_quantize_grouped_ef_mixed``); no other pair."""
     _require(isinstance(residual, torch.Tensor), f'{what} must be a torch.Tensor')
-    _require(residual.dtype == tensor.dtype, f'{what} must have the dtype of the tensor ({tensor.dtype}), got {residual.dtype}')
+    _require(residual.dtype == tensor.dtype or (tensor.dtype == torch.bfloat16 and residual.dtype == torch.float32),
+             f'{what} must have the dtype of the tensor ({tensor.dtype}), or torch.float32 for a torch.bfloat16 tensor, got {residual.dtype}')
     _require(residual.numel() == tensor.numel(), f'{what} must have the numel of the tensor ({tensor.numel()}), got {residual.numel()}')
     _require(residual.device == tensor.device, f'{what} must live on the device of the tensor ({tensor.device}), got {residual.device}')
     _require(residual.is_contiguous(), f'{what} must be contiguous (it is updated in place)')
+
+
+def _residual_dtype(residual: torch.Tensor, tensor: torch.Tensor):
+    """``residual_dtype=`` of the ``*_ef*_ptr`` methods: None (the old symbol) unless the residual's dtype differs from the tensor's."""
+    return None if residual.dtype == tensor.dtype else torch_to_piquant_dtype(residual.dtype)
 
 
 def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
@@ -583,7 +590,10 @@ def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: 
     ``torch.sub``.  ``residual`` is a contiguous tensor of the tensor's dtype, device and numel that the caller keeps between steps (zeros before
     the first); ``tensor`` is not written.  Returns (quantized, scales, zero_points) as ``quantize_grouped`` does.  A constant group gets the
     degenerate (1.0, qmax >> 1) and a group whose range lies far from zero has its zero point clamped: most of such a group goes to the residual,
-    which conserves it but does not make it representable (``include/piquant_hip.h``, piquant_hip_quantize_grouped_ef)."""
+    which conserves it but does not make it representable (``include/piquant_hip.h``, piquant_hip_quantize_grouped_ef).
+    A bfloat16 ``tensor`` also takes a float32 ``residual``: then ``y`` and the new residual are float32 and the call writes exactly what
+    ``quantize_grouped_ef(tensor.float(), residual)`` writes, still in one launch -- the residual no longer loses up to 2^-9 |y| per rounding,
+    as much as the half step of a uint8 wire (piquant_hip_quantize_grouped_ef_mixed).  No other pair of dtypes is accepted."""
     _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
     _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
     _check_group_size(group_size)
@@ -607,7 +617,8 @@ def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: 
         _check_packed_out(out, qdt, tensor.numel(), tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.quantize_grouped_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), out.data_ptr(), qdt, tensor.numel(), group_size,
-                                out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+                                out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True,
+                                residual_dtype=_residual_dtype(residual, tensor))
     return out, out_scales, out_zero_points
 
 
@@ -622,7 +633,8 @@ def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensor
     each term) followed by ``quantize_grouped_ef(acc, residual)`` -- the residual is added AFTER the terms.  ``residual`` is a contiguous tensor of
     ``acc``'s dtype, device and numel that the caller keeps between steps (zeros before the first); the terms are as for
     ``reduce_quantize_grouped``.  Returns (out, out_scales, out_zero_points); ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
-    piquant_hip_reduce_quantize_grouped_ef)."""
+    piquant_hip_reduce_quantize_grouped_ef).  A bfloat16 ``acc`` also takes a float32 ``residual``: the same two-call identity with the mixed
+    ``quantize_grouped_ef(acc, residual)`` as its second call, and run as that composition (k + 1 launches; no fused kernel for this pair)."""
     _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
     _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
     _check_group_size(group_size)
@@ -654,7 +666,8 @@ def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensor
     ctx = _ctx_for(acc, ctx)
     ctx.reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [t.data_ptr() for t in tensors],
                                        [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], out.data_ptr(), qdt, numel, group_size,
-                                       out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+                                       out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True,
+                                       residual_dtype=_residual_dtype(residual, acc))
     return out, out_scales, out_zero_points
 
 
@@ -662,7 +675,8 @@ def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_s
                               outs=None, out_scales=None, out_zero_points=None):
     """``quantize_grouped_ef`` of several independent (tensor, residual) pairs (one dtype pair, group size and round mode) with one kernel launch
     per 16 pairs.  Returns (outs, scales, zero_points) as lists; pair i's entries and its updated residual equal
-    ``quantize_grouped_ef(tensors[i], residuals[i])`` (a stochastic batch draws one threshold)."""
+    ``quantize_grouped_ef(tensors[i], residuals[i])`` (a stochastic batch draws one threshold).  The residuals of a batch share one dtype: the
+    tensors', or float32 for bfloat16 tensors."""
     _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
     _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
     _check_group_size(group_size)
@@ -673,6 +687,7 @@ def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_s
     for i, (t, r) in enumerate(zip(tensors, residuals)):
         _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, f'tensors[{i}] must be a float32 or bfloat16 tensor')
         _check_residual(r, t, f'residuals[{i}]')
+        _require(r.dtype == residuals[0].dtype, f'the residuals of a batch must share one dtype, got {residuals[0].dtype} and {r.dtype}')
     for i, t in enumerate(tensors):
         _check_float_input(t, f'tensors[{i}]')
         _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
@@ -696,7 +711,8 @@ def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_s
     ctx = _ctx_for(tensors[0], ctx)
     ctx.quantize_grouped_ef_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [r.data_ptr() for r in residuals],
                                       [o.data_ptr() for o in outs], qdt, [t.numel() for t in tensors], group_size, [sc.data_ptr() for sc in out_scales],
-                                      [zp.data_ptr() for zp in out_zero_points], _ROUND_MODES[round_mode], _device_ptrs=True)
+                                      [zp.data_ptr() for zp in out_zero_points], _ROUND_MODES[round_mode], _device_ptrs=True,
+                                      residual_dtype=_residual_dtype(residuals[0], tensors[0]))
     return outs, out_scales, out_zero_points
 
 

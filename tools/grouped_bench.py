@@ -20,7 +20,12 @@ G = 128) next to the two-step composition that defines it (k grouped dequantize 
 byte ratio of each row and the target fused / composition <= 1.15 x that ratio; and the kernel time of one rank's replayed 8-way grouped mesh
 all-reduce with error feedback, with error_feedback_requantize off and on.  Writes profiles/grouped_reduce_ef_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows ef_f32r: the error-feedback quantize of a bfloat16 tensor with a FLOAT32 residual (G = 128, uint8 / uint4 / uint2 wire) next to the
+composition that defines it (the tensor widened to float32, then the float32 quantize_grouped_ef) and to the existing bfloat16-residual call, all
+in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
+profiles/grouped_ef_f32r_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -384,16 +389,69 @@ def reduce_ef_rows(ctx, dev, stream, args, G=128, world=8):
     return rows
 
 
+def ef_f32r_rows(ctx, dev, stream, args, G=128):
+    """quantize_grouped_ef of a bf16 tensor with an fp32 residual against widen + the fp32 call, and against the bf16-residual call"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    bf16, f32 = piquant.DataType.BF16, piquant.DataType.F32
+    nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * 6)) + 1)
+    xs = [torch.empty(NUMEL, dtype=torch.bfloat16, device=dev).normal_(generator=g) for _ in range(nbuf)]
+    rs = [torch.empty(NUMEL, dtype=torch.float32, device=dev).normal_(generator=g) * 0.01 for _ in range(nbuf)]
+    r16 = [r.to(torch.bfloat16) for r in rs]
+    wide = [torch.empty(NUMEL, dtype=torch.float32, device=dev) for _ in range(nbuf)]   # where the composition's widened copy goes
+    sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+    zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+    per_window = max(2 * nbuf, 32)
+    for qname, (qdt, bits) in QUANT.items():
+        pair = f"bf16->{qname}"
+        nq = qdt.packed_nbytes(NUMEL)
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+        def composition(i):
+            wide[i].copy_(xs[i])   # x.float() into a buffer that exists: no allocation in the timed window
+            ctx.quantize_grouped_ef_ptr(wide[i].data_ptr(), f32, rs[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def fused(i):
+            ctx.quantize_grouped_ef_ptr(xs[i].data_ptr(), bf16, rs[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True, residual_dtype=f32)
+
+        def same_dtype(i):
+            ctx.quantize_grouped_ef_ptr(xs[i].data_ptr(), bf16, r16[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("ef_f32r_composition", pair, G, us_c, NUMEL * (2 + 4) + NUMEL * 12 + nq + 5 * ng, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("quantize_grouped_ef_f32r", pair, G, us_f, NUMEL * (2 + 4 + 4) + nq + 5 * ng, s_f)
+        us_b, s_b = timed(same_dtype, nbuf, args.windows, per_window, stream)
+        br = row("quantize_grouped_ef", pair, G, us_b, NUMEL * (2 + 2 + 2) + nq + 5 * ng, s_b)
+        fr["over_composition"] = round(us_f / us_c, 3)
+        fr["bytes_over_composition"] = round(fr["bytes"] / cr["bytes"], 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        fr["over_bf16_residual"] = round(us_f / us_b, 3)
+        fr["bytes_over_bf16_residual"] = round(fr["bytes"] / br["bytes"], 3)
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}; fused / bf16-residual call = {fr['over_bf16_residual']:.3f} (bytes "
+              f"{fr['bytes_over_bf16_residual']:.3f})", flush=True)
+        rows += [cr, fr, br]
+        del outs
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
-                                                   "reduce_ef": "grouped_reduce_ef_bench.json"}[args.rows])
+                                                   "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -409,6 +467,8 @@ def main():
         rows = ef_rows(ctx, dev, stream, args)
     if args.rows == "reduce_ef":
         rows = reduce_ef_rows(ctx, dev, stream, args)
+    if args.rows == "ef_f32r":
+        rows = ef_f32r_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
