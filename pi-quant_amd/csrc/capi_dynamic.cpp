@@ -37,11 +37,7 @@ extern "C" {
 void piquant_hip_dequantize_sum(piquant_context_t* ctx, const void* const* inputs, const piquant_hip_params_t* const* device_params, size_t count,
                                 piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel, piquant_reduce_op_t op) {
     if (!ctx) panic("piquant_hip_dequantize_sum: context is NULL");
-    const dtype_row& dti = dtype_of(dtype_in);
-    const dtype_row& dto = dtype_of(dtype_out);
-    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
-    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
+    check_dequant_types(dtype_in, dtype_out, op);
     if (count == 0 || numel == 0) return;
     if (!inputs || !device_params || !out) panic("dequantize_sum: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -54,11 +50,7 @@ void piquant_hip_dequantize_dp_batch(piquant_context_t* ctx, const void* const* 
                                      piquant_dtype_t dtype_out, const size_t* numels, const piquant_hip_params_t* const* device_params, size_t count,
                                      piquant_reduce_op_t op) {
     if (!ctx) panic("piquant_hip_dequantize_dp_batch: context is NULL");
-    const dtype_row& dti = dtype_of(dtype_in);
-    const dtype_row& dto = dtype_of(dtype_out);
-    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
-    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
+    check_dequant_types(dtype_in, dtype_out, op);
     if (count == 0) return;
     if (!inputs || !outputs || !numels || !device_params) panic("piquant_hip_dequantize_dp_batch: NULL argument");
     std::lock_guard<std::mutex> lock(ctx->mu);
@@ -161,14 +153,6 @@ static void quantize_dynamic_one(piquant_context_t* ctx, QuantLaunch q, const vo
         q.dyn_params = params_dev;
         launch_quantize(q, ctx->stream, ctx->num_cu);
     }
-}
-
-static void check_dynamic_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_round_mode_t mode) {
-    const dtype_row& dti = dtype_of(dtype_in);
-    const dtype_row& dto = dtype_of(dtype_out);
-    if (dti.quant) panic("quantize: input dtype (%s) must be a dequantized type", dti.name);
-    if (!dto.quant) panic("quantize: output dtype (%s) must be a quantized type", dto.name);
-    if (mode != PIQUANT_NEAREST && mode != PIQUANT_STOCHASTIC) panic("quantize: invalid round mode %d", static_cast<int>(mode));
 }
 
 void piquant_hip_quantize_dynamic(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
@@ -411,614 +395,6 @@ int piquant_hip_peer_timeout(piquant_context_t* ctx, uint32_t* out_rank, uint32_
     if (out_seen) *out_seen = rec[3];
     __atomic_store_n(rec + 0, static_cast<uint32_t>(kPeerTimeoutNone), __ATOMIC_RELEASE);   // reported: cleared
     return static_cast<int>(kind);
-}
-
-}  // extern "C"
-
-extern "C" {
-
-// Group-wise quantization (include/piquant_hip.h): one launch each, stream-ordered, device (or pinned) buffers only.
-static void check_group_size(size_t group_size) {
-    if (group_size < static_cast<size_t>(kGroupedMinG) || group_size > static_cast<size_t>(kGroupedMaxG) || (group_size & (group_size - 1)) != 0)
-        panic("group size %zu is not a power of two in [%d, %d]", group_size, kGroupedMinG, kGroupedMaxG);
-}
-
-void piquant_hip_quantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
-                                  size_t group_size, float* scales, uint8_t* zero_points, int params_given, piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    check_group_size(group_size);
-    if (numel == 0) return;
-    if (!in || !out || !scales || !zero_points) panic("quantize_grouped: NULL buffer");
-    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("quantize_grouped: scales must be 4-byte aligned");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const Resolved rin = ctx->resolve_ptr(in), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
-    if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped needs device (or pinned) buffers");
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // the call's one threshold (or the per-element seed and base), as quantize_uniform draws it
-    GroupedQuantLaunch q {};
-    q.in = rin.dev;
-    q.out = rout.dev;
-    q.numel = static_cast<int64_t>(numel);
-    q.group_size = static_cast<int64_t>(group_size);
-    q.scales = static_cast<float*>(rs.dev);
-    q.zero_points = static_cast<uint8_t*>(rz.dev);
-    q.params_given = params_given != 0;
-    q.dt_in = dtype_in;
-    q.dt_out = dtype_out;
-    q.round_mode = rm.round_mode;
-    q.threshold = rm.threshold;
-    q.seed = rm.seed;
-    q.index_base = rm.index_base;
-    {
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, q.params_given);
-        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
-                                    size_t group_size, const float* scales, const uint8_t* zero_points, piquant_reduce_op_t op) {
-    if (!ctx) panic("piquant_hip_dequantize_grouped: context is NULL");
-    const dtype_row& dti = dtype_of(dtype_in);
-    const dtype_row& dto = dtype_of(dtype_out);
-    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
-    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
-    check_group_size(group_size);
-    if (numel == 0) return;
-    if (!in || !out || !scales || !zero_points) panic("dequantize_grouped: NULL buffer");
-    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("dequantize_grouped: scales must be 4-byte aligned");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const Resolved rin = ctx->resolve_ptr(in), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
-    if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_dequantize_grouped needs device (or pinned) buffers");
-    GroupedDequantLaunch d {};
-    d.in = rin.dev;
-    d.out = rout.dev;
-    d.numel = static_cast<int64_t>(numel);
-    d.group_size = static_cast<int64_t>(group_size);
-    d.scales = static_cast<const float*>(rs.dev);
-    d.zero_points = static_cast<const uint8_t*>(rz.dev);
-    d.dt_in = dtype_in;
-    d.dt_out = dtype_out;
-    d.op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
-    {
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-}  // extern "C"
-
-extern "C" {
-
-// Batches and the fused reduce of the group-wise calls (include/piquant_hip.h): stream-ordered, device (or pinned) buffers only, no allocation.
-static inline bool grouped_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
-                                        piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
-                                        uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped_batch: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_batch: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
-    GroupedQuantBatchLaunch b {};
-    b.group_size = static_cast<int64_t>(group_size);
-    b.params_given = params_given != 0;
-    b.dt_in = dtype_in;
-    b.dt_out = dtype_out;
-    b.round_mode = rm.round_mode;
-    b.threshold = rm.threshold;
-    b.seed = rm.seed;
-    b.index_base = rm.index_base;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, b.params_given);
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        if (!inputs[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_batch: NULL buffer %zu", i);
-        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_batch: scales %zu must be 4-byte aligned", i);
-        const Resolved rin = ctx->resolve_ptr(inputs[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]), rz = resolve(zero_points[i]);
-        if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped_batch needs device (or pinned) buffers");
-        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rout.dev)) {   // the single call's guarded kernel, same bytes
-            GroupedQuantLaunch q {};
-            q.in = rin.dev;
-            q.out = rout.dev;
-            q.numel = static_cast<int64_t>(numels[i]);
-            q.group_size = b.group_size;
-            q.scales = static_cast<float*>(rs.dev);
-            q.zero_points = static_cast<uint8_t*>(rz.dev);
-            q.params_given = b.params_given;
-            q.dt_in = dtype_in;
-            q.dt_out = dtype_out;
-            q.round_mode = b.round_mode;
-            q.threshold = b.threshold;
-            q.seed = b.seed;
-            q.index_base = b.index_base;
-            launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        b.in[b.count] = rin.dev;
-        b.out[b.count] = rout.dev;
-        b.scales[b.count] = static_cast<float*>(rs.dev);
-        b.zero_points[b.count] = static_cast<uint8_t*>(rz.dev);
-        b.numel[b.count] = static_cast<int64_t>(numels[i]);
-        if (++b.count == kGroupedBatchMaxTensors) {
-            launch_quantize_grouped_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_quantize_grouped_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
-                                          piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales,
-                                          const uint8_t* const* zero_points, size_t count, piquant_reduce_op_t op) {
-    if (!ctx) panic("piquant_hip_dequantize_grouped_batch: context is NULL");
-    const dtype_row& dti = dtype_of(dtype_in);
-    const dtype_row& dto = dtype_of(dtype_out);
-    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
-    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
-    check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_dequantize_grouped_batch: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    GroupedDequantBatchLaunch b {};
-    b.group_size = static_cast<int64_t>(group_size);
-    b.dt_in = dtype_in;
-    b.dt_out = dtype_out;
-    b.op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        if (!inputs[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("dequantize_grouped_batch: NULL buffer %zu", i);
-        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("dequantize_grouped_batch: scales %zu must be 4-byte aligned", i);
-        const Resolved rin = ctx->resolve_ptr(inputs[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]), rz = resolve(zero_points[i]);
-        if (rin.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_dequantize_grouped_batch needs device (or pinned) buffers");
-        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rout.dev)) {
-            GroupedDequantLaunch d {};
-            d.in = rin.dev;
-            d.out = rout.dev;
-            d.numel = static_cast<int64_t>(numels[i]);
-            d.group_size = b.group_size;
-            d.scales = static_cast<const float*>(rs.dev);
-            d.zero_points = static_cast<const uint8_t*>(rz.dev);
-            d.dt_in = dtype_in;
-            d.dt_out = dtype_out;
-            d.op = b.op;
-            launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        b.in[b.count] = rin.dev;
-        b.out[b.count] = rout.dev;
-        b.scales[b.count] = static_cast<const float*>(rs.dev);
-        b.zero_points[b.count] = static_cast<const uint8_t*>(rz.dev);
-        b.numel[b.count] = static_cast<int64_t>(numels[i]);
-        if (++b.count == kGroupedBatchMaxTensors) {
-            launch_dequantize_grouped_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_dequantize_grouped_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
-                                         const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
-                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
-                                         piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_reduce_quantize_grouped: context is NULL");
-    check_dynamic_types(dtype_acc, dtype_out, mode);
-    check_group_size(group_size);
-    if (numel == 0) return;
-    if (!acc || !out || !scales || !zero_points) panic("reduce_quantize_grouped: NULL buffer");
-    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped: NULL argument");
-    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped: scales must be 4-byte aligned");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const Resolved racc = ctx->resolve_ptr(acc), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
-    if (racc.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_reduce_quantize_grouped needs device (or pinned) buffers");
-    // the terms, resolved; every buffer 16-byte aligned takes the fused kernel, anything else the two-step form (same bytes)
-    std::vector<const void*> tin(count);
-    std::vector<const float*> tsc(count);
-    std::vector<const uint8_t*> tzp(count);
-    bool aligned = grouped_aligned16(racc.dev) && grouped_aligned16(rout.dev);
-    for (size_t i = 0; i < count; ++i) {
-        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped: NULL input %zu", i);
-        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped: input scales %zu must be 4-byte aligned", i);
-        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
-        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped needs device (or pinned) buffers");
-        tin[i] = ri.dev;
-        tsc[i] = static_cast<const float*>(rsi.dev);
-        tzp[i] = static_cast<const uint8_t*>(rzi.dev);
-        aligned = aligned && grouped_aligned16(ri.dev);
-    }
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // the call's one threshold, whichever form runs
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the terms' parameters are written by whatever was enqueued just before
-    // terms that are not fused: grouped dequantize ADD into acc, in order
-    const size_t fused_from = aligned ? (count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0) : count;
-    for (size_t i = 0; i < fused_from; ++i) {
-        GroupedDequantLaunch d {};
-        d.in = tin[i];
-        d.out = racc.dev;
-        d.numel = static_cast<int64_t>(numel);
-        d.group_size = static_cast<int64_t>(group_size);
-        d.scales = tsc[i];
-        d.zero_points = tzp[i];
-        d.dt_in = dtype_out;
-        d.dt_out = dtype_acc;
-        d.op = OP_ADD;
-        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
-    }
-    if (aligned && count > 0) {
-        GroupedReduceLaunch r {};
-        r.acc = racc.dev;
-        r.out = rout.dev;
-        r.numel = static_cast<int64_t>(numel);
-        r.group_size = static_cast<int64_t>(group_size);
-        r.scales = static_cast<float*>(rs.dev);
-        r.zero_points = static_cast<uint8_t*>(rz.dev);
-        for (size_t i = fused_from; i < count; ++i) {
-            r.in[r.count] = tin[i];
-            r.in_scales[r.count] = tsc[i];
-            r.in_zero_points[r.count] = tzp[i];
-            ++r.count;
-        }
-        r.dt_acc = dtype_acc;
-        r.dt_out = dtype_out;
-        r.round_mode = rm.round_mode;
-        r.threshold = rm.threshold;
-        r.seed = rm.seed;
-        r.index_base = rm.index_base;
-        launch_reduce_quantize_grouped(r, ctx->stream);
-    } else {   // k == 0, or the two-step form: quantize_grouped(acc)
-        GroupedQuantLaunch q {};
-        q.in = racc.dev;
-        q.out = rout.dev;
-        q.numel = static_cast<int64_t>(numel);
-        q.group_size = static_cast<int64_t>(group_size);
-        q.scales = static_cast<float*>(rs.dev);
-        q.zero_points = static_cast<uint8_t*>(rz.dev);
-        q.params_given = false;
-        q.dt_in = dtype_acc;
-        q.dt_out = dtype_out;
-        q.round_mode = rm.round_mode;
-        q.threshold = rm.threshold;
-        q.seed = rm.seed;
-        q.index_base = rm.index_base;
-        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// Error feedback (include/piquant_hip.h, piquant_hip_quantize_grouped_ef).  The single call goes through the batch entry with one tensor, which
-// launches the single-tensor kernel.
-void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
-                                           void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
-                                           uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped_ef_batch: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_ef_batch: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
-    GroupedEfBatchLaunch b {};
-    b.group_size = static_cast<int64_t>(group_size);
-    b.dt_in = dtype_in;
-    b.dt_out = dtype_out;
-    b.round_mode = rm.round_mode;
-    b.threshold = rm.threshold;
-    b.seed = rm.seed;
-    b.index_base = rm.index_base;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        if (!inputs[i] || !residuals[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_ef: NULL buffer %zu", i);
-        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_ef: scales %zu must be 4-byte aligned", i);
-        const Resolved rin = ctx->resolve_ptr(inputs[i]), rres = ctx->resolve_ptr(residuals[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]),
-                       rz = resolve(zero_points[i]);
-        if (rin.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable) panic("piquant_hip_quantize_grouped_ef needs device (or pinned) buffers");
-        const int t = b.count;
-        b.in[t] = rin.dev;
-        b.residual[t] = rres.dev;
-        b.out[t] = rout.dev;
-        b.scales[t] = static_cast<float*>(rs.dev);
-        b.zero_points[t] = static_cast<uint8_t*>(rz.dev);
-        b.numel[t] = static_cast<int64_t>(numels[i]);
-        if (!grouped_aligned16(rin.dev) || !grouped_aligned16(rres.dev) || !grouped_aligned16(rout.dev)) {   // the guarded kernel, same bytes
-            launch_quantize_grouped_ef_guarded(b, t, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        if (++b.count == kGroupedBatchMaxTensors) {
-            launch_quantize_grouped_ef_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_quantize_grouped_ef_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_quantize_grouped_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, void* out, piquant_dtype_t dtype_out,
-                                     size_t numel, size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped_ef: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    piquant_hip_quantize_grouped_ef_batch(ctx, &in, dtype_in, &residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1, mode);
-}
-
-// Error feedback on a re-quantized partial sum (include/piquant_hip.h).  Every buffer 16-byte aligned: the surplus over kGroupedReduceMaxInputs terms
-// goes into acc by grouped dequantize ADD launches and the last terms are fused with the residual in ONE launch.  Anything else: the two-step
-// composition that defines the call -- every term by grouped dequantize ADD, then quantize_grouped_ef(acc, residual) -- with the call's one threshold.
-void piquant_hip_reduce_quantize_grouped_ef(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual, const void* const* inputs,
-                                            const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
-                                            piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
-                                            piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_reduce_quantize_grouped_ef: context is NULL");
-    check_dynamic_types(dtype_acc, dtype_out, mode);
-    check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    if (!acc || !residual || !out || !scales || !zero_points) panic("reduce_quantize_grouped_ef: NULL buffer");
-    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped_ef: NULL argument");
-    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped_ef: scales must be 4-byte aligned");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const Resolved racc = ctx->resolve_ptr(acc), rres = ctx->resolve_ptr(residual), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
-    if (racc.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
-        panic("piquant_hip_reduce_quantize_grouped_ef needs device (or pinned) buffers");
-    std::vector<const void*> tin(count);
-    std::vector<const float*> tsc(count);
-    std::vector<const uint8_t*> tzp(count);
-    bool aligned = grouped_aligned16(racc.dev) && grouped_aligned16(rres.dev) && grouped_aligned16(rout.dev);
-    for (size_t i = 0; i < count; ++i) {
-        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped_ef: NULL input %zu", i);
-        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped_ef: input scales %zu must be 4-byte aligned", i);
-        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
-        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped_ef needs device (or pinned) buffers");
-        tin[i] = ri.dev;
-        tsc[i] = static_cast<const float*>(rsi.dev);
-        tzp[i] = static_cast<const uint8_t*>(rzi.dev);
-        aligned = aligned && grouped_aligned16(ri.dev);
-    }
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // the call's one threshold, whichever form runs
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
-    const size_t fused_from = aligned ? (count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0) : count;
-    for (size_t i = 0; i < fused_from; ++i) {
-        GroupedDequantLaunch d {};
-        d.in = tin[i];
-        d.out = racc.dev;
-        d.numel = static_cast<int64_t>(numel);
-        d.group_size = static_cast<int64_t>(group_size);
-        d.scales = tsc[i];
-        d.zero_points = tzp[i];
-        d.dt_in = dtype_out;
-        d.dt_out = dtype_acc;
-        d.op = OP_ADD;
-        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
-    }
-    if (aligned && count > 0) {
-        GroupedReduceEfLaunch e {};
-        GroupedReduceLaunch& r = e.r;
-        e.residual = rres.dev;
-        r.acc = racc.dev;
-        r.out = rout.dev;
-        r.numel = static_cast<int64_t>(numel);
-        r.group_size = static_cast<int64_t>(group_size);
-        r.scales = static_cast<float*>(rs.dev);
-        r.zero_points = static_cast<uint8_t*>(rz.dev);
-        for (size_t i = fused_from; i < count; ++i) {
-            r.in[r.count] = tin[i];
-            r.in_scales[r.count] = tsc[i];
-            r.in_zero_points[r.count] = tzp[i];
-            ++r.count;
-        }
-        r.dt_acc = dtype_acc;
-        r.dt_out = dtype_out;
-        r.round_mode = rm.round_mode;
-        r.threshold = rm.threshold;
-        r.seed = rm.seed;
-        r.index_base = rm.index_base;
-        launch_reduce_quantize_grouped_ef(e, ctx->stream);
-    } else {   // k == 0, or the two-step form: quantize_grouped_ef(acc, residual), streaming or guarded by its own alignment rule
-        GroupedEfBatchLaunch b {};
-        b.in[0] = racc.dev;
-        b.residual[0] = rres.dev;
-        b.out[0] = rout.dev;
-        b.scales[0] = static_cast<float*>(rs.dev);
-        b.zero_points[0] = static_cast<uint8_t*>(rz.dev);
-        b.numel[0] = static_cast<int64_t>(numel);
-        b.group_size = static_cast<int64_t>(group_size);
-        b.dt_in = dtype_acc;
-        b.dt_out = dtype_out;
-        b.round_mode = rm.round_mode;
-        b.threshold = rm.threshold;
-        b.seed = rm.seed;
-        b.index_base = rm.index_base;
-        if (grouped_aligned16(racc.dev) && grouped_aligned16(rres.dev) && grouped_aligned16(rout.dev)) {
-            b.count = 1;
-            launch_quantize_grouped_ef_batch(b, ctx->stream);
-        } else {
-            launch_quantize_grouped_ef_guarded(b, 0, ctx->stream, ctx->num_cu);
-        }
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// Error feedback with the residual's type named (include/piquant_hip.h, piquant_hip_quantize_grouped_ef_mixed): the residual's type equal to the
-// tensor's forwards to the calls above; a bfloat16 tensor with a float32 residual runs the kernels of kernels_grouped_ef_f32r.hip.
-static bool grouped_ef_f32_residual(const char* what, piquant_dtype_t dtype_in, piquant_dtype_t dtype_residual) {
-    if (dtype_residual == dtype_in) return false;
-    if (dtype_in == PIQUANT_DTYPE_BF16 && dtype_residual == PIQUANT_DTYPE_F32) return true;
-    panic("%s: a %s residual for a %s tensor (the tensor's type, or float32 for a bfloat16 tensor, is needed)", what, dtype_of(dtype_residual).name,
-          dtype_of(dtype_in).name);
-}
-
-// the streaming kernels' rule: 16-byte residual and output, 8-byte tensor (its lane-row is four bfloat16 elements)
-static inline bool grouped_f32r_aligned(const void* in, const void* residual, const void* out) {
-    return (reinterpret_cast<uintptr_t>(in) & 7u) == 0 && grouped_aligned16(residual) && grouped_aligned16(out);
-}
-
-void piquant_hip_quantize_grouped_ef_mixed_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
-                                                 piquant_dtype_t dtype_residual, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
-                                                 size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
-                                                 piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped_ef_mixed_batch: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    if (!grouped_ef_f32_residual("piquant_hip_quantize_grouped_ef_mixed_batch", dtype_in, dtype_residual)) {
-        piquant_hip_quantize_grouped_ef_batch(ctx, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, mode);
-        return;
-    }
-    check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("piquant_hip_quantize_grouped_ef_mixed_batch: NULL argument");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // ONE threshold (or per-element seed and base) for the whole batch
-    GroupedEfBatchLaunch b {};
-    b.group_size = static_cast<int64_t>(group_size);
-    b.dt_in = dtype_in;
-    b.dt_out = dtype_out;
-    b.round_mode = rm.round_mode;
-    b.threshold = rm.threshold;
-    b.seed = rm.seed;
-    b.index_base = rm.index_base;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        if (!inputs[i] || !residuals[i] || !outputs[i] || !scales[i] || !zero_points[i]) panic("quantize_grouped_ef_mixed: NULL buffer %zu", i);
-        if (reinterpret_cast<uintptr_t>(scales[i]) % 4 != 0) panic("quantize_grouped_ef_mixed: scales %zu must be 4-byte aligned", i);
-        const Resolved rin = ctx->resolve_ptr(inputs[i]), rres = ctx->resolve_ptr(residuals[i]), rout = ctx->resolve_ptr(outputs[i]), rs = resolve(scales[i]),
-                       rz = resolve(zero_points[i]);
-        if (rin.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
-            panic("piquant_hip_quantize_grouped_ef_mixed needs device (or pinned) buffers");
-        if (reinterpret_cast<uintptr_t>(rin.dev) % 2 != 0 || reinterpret_cast<uintptr_t>(rres.dev) % 4 != 0)
-            panic("quantize_grouped_ef_mixed: tensor %zu or its residual is not aligned to its element size", i);
-        const int t = b.count;
-        b.in[t] = rin.dev;
-        b.residual[t] = rres.dev;
-        b.out[t] = rout.dev;
-        b.scales[t] = static_cast<float*>(rs.dev);
-        b.zero_points[t] = static_cast<uint8_t*>(rz.dev);
-        b.numel[t] = static_cast<int64_t>(numels[i]);
-        if (!grouped_f32r_aligned(rin.dev, rres.dev, rout.dev)) {   // the guarded kernel, same bytes
-            launch_quantize_grouped_ef_f32r_guarded(b, t, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        if (++b.count == kGroupedBatchMaxTensors) {
-            launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_quantize_grouped_ef_mixed(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, piquant_dtype_t dtype_residual,
-                                           void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
-                                           piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_quantize_grouped_ef_mixed: context is NULL");
-    check_dynamic_types(dtype_in, dtype_out, mode);
-    if (!grouped_ef_f32_residual("piquant_hip_quantize_grouped_ef_mixed", dtype_in, dtype_residual)) {
-        piquant_hip_quantize_grouped_ef(ctx, in, dtype_in, residual, out, dtype_out, numel, group_size, scales, zero_points, mode);
-        return;
-    }
-    check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    piquant_hip_quantize_grouped_ef_mixed_batch(ctx, &in, dtype_in, &residual, dtype_residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1,
-                                                mode);
-}
-
-// A bfloat16 accumulator with a float32 residual runs as the composition that defines the call: every term by grouped dequantize ADD into acc, in
-// order, then the mixed single call on (acc, residual) with the call's one threshold (a fused mixed reduce kernel: DESIGN.md 10).
-void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual,
-                                                  piquant_dtype_t dtype_residual, const void* const* inputs, const float* const* input_scales,
-                                                  const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out, size_t numel,
-                                                  size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
-    if (!ctx) panic("piquant_hip_reduce_quantize_grouped_ef_mixed: context is NULL");
-    check_dynamic_types(dtype_acc, dtype_out, mode);
-    if (!grouped_ef_f32_residual("piquant_hip_reduce_quantize_grouped_ef_mixed", dtype_acc, dtype_residual)) {
-        piquant_hip_reduce_quantize_grouped_ef(ctx, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel, group_size,
-                                               scales, zero_points, mode);
-        return;
-    }
-    check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    if (!acc || !residual || !out || !scales || !zero_points) panic("reduce_quantize_grouped_ef_mixed: NULL buffer");
-    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) panic("piquant_hip_reduce_quantize_grouped_ef_mixed: NULL argument");
-    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) panic("reduce_quantize_grouped_ef_mixed: scales must be 4-byte aligned");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const Resolved racc = ctx->resolve_ptr(acc), rres = ctx->resolve_ptr(residual), rout = ctx->resolve_ptr(out), rs = resolve(scales), rz = resolve(zero_points);
-    if (racc.pageable || rres.pageable || rout.pageable || rs.pageable || rz.pageable)
-        panic("piquant_hip_reduce_quantize_grouped_ef_mixed needs device (or pinned) buffers");
-    if (reinterpret_cast<uintptr_t>(racc.dev) % 2 != 0 || reinterpret_cast<uintptr_t>(rres.dev) % 4 != 0)
-        panic("reduce_quantize_grouped_ef_mixed: acc or the residual is not aligned to its element size");
-    std::vector<GroupedDequantLaunch> adds(count);
-    for (size_t i = 0; i < count; ++i) {
-        if (!inputs[i] || !input_scales[i] || !input_zero_points[i]) panic("reduce_quantize_grouped_ef_mixed: NULL input %zu", i);
-        if (reinterpret_cast<uintptr_t>(input_scales[i]) % 4 != 0) panic("reduce_quantize_grouped_ef_mixed: input scales %zu must be 4-byte aligned", i);
-        const Resolved ri = ctx->resolve_ptr(inputs[i]), rsi = resolve(input_scales[i]), rzi = resolve(input_zero_points[i]);
-        if (ri.pageable || rsi.pageable || rzi.pageable) panic("piquant_hip_reduce_quantize_grouped_ef_mixed needs device (or pinned) buffers");
-        GroupedDequantLaunch& d = adds[i];
-        d.in = ri.dev;
-        d.out = racc.dev;
-        d.numel = static_cast<int64_t>(numel);
-        d.group_size = static_cast<int64_t>(group_size);
-        d.scales = static_cast<const float*>(rsi.dev);
-        d.zero_points = static_cast<const uint8_t*>(rzi.dev);
-        d.dt_in = dtype_out;
-        d.dt_out = dtype_acc;
-        d.op = OP_ADD;
-    }
-    QuantLaunch rm {};
-    fill_round_mode(ctx, rm, mode);   // the call's one threshold
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
-    for (size_t i = 0; i < count; ++i) launch_dequantize_grouped(adds[i], ctx->stream, ctx->num_cu);
-    GroupedEfBatchLaunch b {};
-    b.in[0] = racc.dev;
-    b.residual[0] = rres.dev;
-    b.out[0] = rout.dev;
-    b.scales[0] = static_cast<float*>(rs.dev);
-    b.zero_points[0] = static_cast<uint8_t*>(rz.dev);
-    b.numel[0] = static_cast<int64_t>(numel);
-    b.group_size = static_cast<int64_t>(group_size);
-    b.dt_in = dtype_acc;
-    b.dt_out = dtype_out;
-    b.round_mode = rm.round_mode;
-    b.threshold = rm.threshold;
-    b.seed = rm.seed;
-    b.index_base = rm.index_base;
-    if (grouped_f32r_aligned(racc.dev, rres.dev, rout.dev)) {
-        b.count = 1;
-        launch_quantize_grouped_ef_f32r_batch(b, ctx->stream);
-    } else {
-        launch_quantize_grouped_ef_f32r_guarded(b, 0, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
 }
 
 }  // extern "C"

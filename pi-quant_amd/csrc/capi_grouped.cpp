@@ -1,0 +1,402 @@
+// The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, and EF with a float32 residual
+// for a bfloat16 tensor.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
+// owns them.
+#include "context.hpp"
+
+using namespace pq;
+
+namespace {
+
+// An entry point and, for a list argument, the index in the list: what every message names.
+struct Where {
+    const char* entry;
+    long index = -1;
+};
+
+[[noreturn]] void bad(const Where& w, const char* what) {
+    if (w.index < 0) panic("%s: %s", w.entry, what);
+    panic("%s: %s (list index %ld)", w.entry, what, w.index);
+}
+
+void check_group_size(size_t group_size) {
+    if (group_size < static_cast<size_t>(kGroupedMinG) || group_size > static_cast<size_t>(kGroupedMaxG) || (group_size & (group_size - 1)) != 0)
+        panic("group size %zu is not a power of two in [%d, %d]", group_size, kGroupedMinG, kGroupedMaxG);
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// What needs neither the lock nor the device: no NULL among one tensor's buffers (the residual only where the call has one), scales 4-byte aligned.
+void check_tensor(const Where& w, bool ef, const void* in, const void* residual, const void* out, const float* scales, const uint8_t* zero_points) {
+    if (!in || !out || (ef && !residual) || !scales || !zero_points) bad(w, "NULL buffer");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) bad(w, "scales must be 4-byte aligned");
+}
+
+// A buffer as the kernels take it: pageable host memory has no group-wise path.
+void* device_ptr(const Where& w, const Resolved& r) {
+    if (r.pageable) bad(w, "device (or pinned) buffers are needed");
+    return r.dev;
+}
+
+// One tensor's buffers, resolved (caller holds ctx->mu); a NULL residual or out is left out.  The parameter arrays are always classified: the
+// context's assume-device mode speaks for the tensors the caller passes, not for them.
+GroupedTensor resolve_tensor(const piquant_context_t* ctx, const Where& w, const void* in, const void* residual, const void* out, const float* scales,
+                             const uint8_t* zero_points, size_t numel) {
+    GroupedTensor t {};
+    t.in = device_ptr(w, ctx->resolve_ptr(in));
+    if (residual) t.residual = device_ptr(w, ctx->resolve_ptr(residual));
+    if (out) t.out = device_ptr(w, ctx->resolve_ptr(out));
+    t.scales = static_cast<float*>(device_ptr(w, resolve(scales)));
+    t.zero_points = static_cast<uint8_t*>(device_ptr(w, resolve(zero_points)));
+    t.numel = static_cast<int64_t>(numel);
+    return t;
+}
+
+// The members of a batch, in order: an empty one is skipped, one that `streams` turns down runs `alone` in its place in the sequence (the guarded
+// kernel, same bytes), the others collect in `b`, which is flushed every kGroupedBatchMaxTensors members and at the end (the batch launchers return
+// at count == 0).  member(i) checks and resolves member i.
+template <class Batch, class Member, class Streams, class Alone, class Flush>
+void run_batch(Batch& b, const size_t* numels, size_t count, Member member, Streams streams, Alone alone, Flush flush) {
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        const GroupedTensor t = member(i);
+        if (!streams(t)) {
+            alone(t);
+            continue;
+        }
+        b.t[b.count] = t;
+        if (++b.count == kGroupedBatchMaxTensors) {
+            flush();
+            b.count = 0;
+        }
+    }
+    flush();
+}
+
+// The terms of a reduce, each resolved as the grouped dequantize ADD that adds it into acc takes it, and whether all of them are 16-byte aligned.
+// The call's one allocation.
+struct Terms {
+    std::vector<GroupedTensor> term;
+    bool aligned = true;
+};
+
+Terms resolve_terms(const piquant_context_t* ctx, const char* entry, const void* const* inputs, const float* const* scales,
+                    const uint8_t* const* zero_points, size_t count, void* acc_dev, size_t numel) {
+    Terms ts;
+    ts.term.resize(count);
+    for (size_t i = 0; i < count; ++i) {
+        const Where w {entry, static_cast<long>(i)};
+        check_tensor(w, false, inputs[i], nullptr, acc_dev, scales[i], zero_points[i]);
+        ts.term[i] = resolve_tensor(ctx, w, inputs[i], nullptr, nullptr, scales[i], zero_points[i], numel);
+        ts.term[i].out = acc_dev;   // resolved by the caller
+        ts.aligned = ts.aligned && aligned16(ts.term[i].in);
+    }
+    return ts;
+}
+
+// acc += dequantize_grouped(term i) for i in [from, to), in order: one grouped dequantize ADD launch each
+void add_terms(piquant_context_t* ctx, const Terms& ts, size_t from, size_t to, const GroupedDequantCall& add) {
+    for (size_t i = from; i < to; ++i) launch_dequantize_grouped(GroupedDequantLaunch {ts.term[i], add}, ctx->stream, ctx->num_cu);
+}
+
+// Index of the first term the fused reduce kernel takes; the terms in front of it go into acc by grouped dequantize ADD first.  Every buffer of
+// the call 16-byte aligned: the surplus over kGroupedReduceMaxInputs goes first and the last terms are fused.  Anything misaligned: count, i.e.
+// every term is added first and acc is quantized alone -- the two-step form, the same bytes.  (No terms: nothing to fuse either way.)
+size_t fused_from(size_t count, bool all_aligned) {
+    if (!all_aligned) return count;
+    return count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0;
+}
+
+// The residual of an error-feedback call: of the tensor's type, or float32 for a bfloat16 tensor (the kernels of kernels_grouped_ef_f32r.hip).
+enum class Residual { Same, F32 };
+
+Residual residual_kind(const char* entry, piquant_dtype_t dtype_in, piquant_dtype_t dtype_residual) {
+    if (dtype_residual == dtype_in) return Residual::Same;
+    if (dtype_in == PIQUANT_DTYPE_BF16 && dtype_residual == PIQUANT_DTYPE_F32) return Residual::F32;
+    panic("%s: a %s residual for a %s tensor (the tensor's type, or float32 for a bfloat16 tensor, is needed)", entry, dtype_of(dtype_residual).name,
+          dtype_of(dtype_in).name);
+}
+
+// The streaming EF kernels' rule: tensor, residual and output 16-byte aligned; with a float32 residual the bfloat16 tensor needs 8 bytes only
+// (its lane-row is four elements).
+bool ef_streams(Residual k, const GroupedTensor& t) {
+    const bool in_ok = k == Residual::F32 ? (reinterpret_cast<uintptr_t>(t.in) & 7u) == 0 : aligned16(t.in);
+    return in_ok && aligned16(t.residual) && aligned16(t.out);
+}
+
+// Types that differ leave room for a tensor or a residual that is not even aligned to its element: no kernel takes that.
+void check_ef_elements(Residual k, const Where& w, const GroupedTensor& t) {
+    if (k == Residual::F32 && (reinterpret_cast<uintptr_t>(t.in) % 2 != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0))
+        bad(w, "the tensor or its residual is not aligned to its element size");
+}
+
+void launch_ef_batch(Residual k, const GroupedEfBatchLaunch& b, hipStream_t stream) {
+    if (k == Residual::F32) launch_quantize_grouped_ef_f32r_batch(b, stream);
+    else launch_quantize_grouped_ef_batch(b, stream);
+}
+
+void launch_ef_guarded(Residual k, const GroupedEfLaunch& q, hipStream_t stream, int num_cu) {
+    if (k == Residual::F32) launch_quantize_grouped_ef_f32r_guarded(q, stream, num_cu);
+    else launch_quantize_grouped_ef_guarded(q, stream, num_cu);
+}
+
+// EF-quantize one (in, residual) pair: streaming (a batch of one, which launches the single-tensor kernel) if its alignment rule holds, else guarded
+void ef_quantize_one(piquant_context_t* ctx, Residual k, const GroupedEfLaunch& q) {
+    if (ef_streams(k, q)) launch_ef_batch(k, GroupedEfBatchLaunch {q, {q}, 1}, ctx->stream);
+    else launch_ef_guarded(k, q, ctx->stream, ctx->num_cu);
+}
+
+// piquant_hip_quantize_grouped_ef_batch and the float32-residual path of piquant_hip_quantize_grouped_ef_mixed_batch, behind their type checks.
+// ONE threshold (or per-element seed and base) for the whole batch, drawn whenever count > 0 -- also when every member is empty.
+void quantize_grouped_ef_batch(piquant_context_t* ctx, const char* entry, Residual k, const void* const* inputs, piquant_dtype_t dtype_in,
+                               void* const* residuals, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size,
+                               float* const* scales, uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {
+    check_group_size(group_size);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    GroupedEfBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, true, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i]);
+            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i], numels[i]);
+            check_ef_elements(k, w, t);
+            return t;
+        },
+        [&](const GroupedTensor& t) { return ef_streams(k, t); },
+        [&](const GroupedTensor& t) { launch_ef_guarded(k, GroupedEfLaunch {t, b}, ctx->stream, ctx->num_cu); },
+        [&] { launch_ef_batch(k, b, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The three reduce entries behind their type checks: out = quantize_grouped(acc + terms [+ residual]), with error feedback when `ef`.
+// The call's one threshold is drawn once, after every buffer is resolved, whichever form then runs; numel == 0 returns before it.  A float32
+// residual for a bfloat16 accumulator has no fused kernel yet: it always takes the two-step form.
+void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef, Residual k, void* acc, piquant_dtype_t dtype_acc, void* residual,
+                             const void* const* inputs, const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count,
+                             void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                             piquant_round_mode_t mode) {
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    const Where w {entry};
+    check_tensor(w, ef, acc, residual, out, scales, zero_points);
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, acc, ef ? residual : nullptr, out, scales, zero_points, numel);
+    if (ef) check_ef_elements(k, w, t);
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, const_cast<void*>(t.in) /* acc */, numel);
+    const bool aligned = terms.aligned && aligned16(t.in) && aligned16(t.out) && (!ef || (k == Residual::Same && aligned16(t.residual)));
+    const GroupedQuantCall call {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
+    const size_t first = fused_from(count, aligned);
+    add_terms(ctx, terms, 0, first, GroupedDequantCall {call.group_size, dtype_out, dtype_acc, OP_ADD});
+    if (first < count) {
+        GroupedReduceLaunch r {t, call, {}, static_cast<int>(count - first)};
+        std::copy(terms.term.begin() + static_cast<std::ptrdiff_t>(first), terms.term.end(), r.term);
+        if (ef) launch_reduce_quantize_grouped_ef(r, ctx->stream);
+        else launch_reduce_quantize_grouped(r, ctx->stream);
+    } else if (ef) {   // no terms, or the two-step form: quantize_grouped_ef(acc, residual)
+        ef_quantize_one(ctx, k, GroupedEfLaunch {t, call});
+    } else {           // quantize_grouped(acc)
+        launch_quantize_grouped(GroupedQuantLaunch {t, call}, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+}  // namespace
+
+extern "C" {
+
+void piquant_hip_quantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                  size_t group_size, float* scales, uint8_t* zero_points, int params_given, piquant_round_mode_t mode) {
+    const Where w {"piquant_hip_quantize_grouped"};
+    if (!ctx) bad(w, "context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    // the call's one threshold (or the per-element seed and base), as quantize_uniform draws it
+    const GroupedQuantLaunch q {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given != 0, round_mode_fields(ctx, mode)}};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, q.params_given);   // given parameters are written by whatever was enqueued just before
+        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                    size_t group_size, const float* scales, const uint8_t* zero_points, piquant_reduce_op_t op) {
+    const Where w {"piquant_hip_dequantize_grouped"};
+    if (!ctx) bad(w, "context is NULL");
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size);
+    if (numel == 0) return;
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    const GroupedDequantLaunch d {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                        piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                        uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
+    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given != 0, round_mode_fields(ctx, mode)}, {}, 0};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, b.params_given);
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+            return resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_quantize_grouped(GroupedQuantLaunch {t, b}, ctx->stream, ctx->num_cu); },
+        [&] { launch_quantize_grouped_batch(b, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                          piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales,
+                                          const uint8_t* const* zero_points, size_t count, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_grouped_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    GroupedDequantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, {}, 0};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+            return resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_dequantize_grouped(GroupedDequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
+        [&] { launch_dequantize_grouped_batch(b, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
+                                         const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                         piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_reduce_quantize_grouped";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    reduce_quantize_grouped(ctx, entry, false, Residual::Same, acc, dtype_acc, nullptr, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
+                            group_size, scales, zero_points, mode);
+}
+
+void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
+                                           void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                           uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_ef_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    quantize_grouped_ef_batch(ctx, entry, Residual::Same, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, mode);
+}
+
+// The single EF calls go through their batch entry with one tensor, which launches the single-tensor kernel.
+void piquant_hip_quantize_grouped_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, void* out, piquant_dtype_t dtype_out,
+                                     size_t numel, size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_ef: context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    piquant_hip_quantize_grouped_ef_batch(ctx, &in, dtype_in, &residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1, mode);
+}
+
+void piquant_hip_reduce_quantize_grouped_ef(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual, const void* const* inputs,
+                                            const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                            piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                            piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_reduce_quantize_grouped_ef";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    reduce_quantize_grouped(ctx, entry, true, Residual::Same, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
+                            group_size, scales, zero_points, mode);
+}
+
+// Error feedback with the residual's type named: the residual's type equal to the tensor's forwards to the entries above (which draw; the
+// forwarding entry does not), a bfloat16 tensor with a float32 residual runs the same bodies with Residual::F32.
+void piquant_hip_quantize_grouped_ef_mixed_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
+                                                 piquant_dtype_t dtype_residual, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                 size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                 piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_ef_mixed_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    if (residual_kind(entry, dtype_in, dtype_residual) == Residual::Same) {
+        piquant_hip_quantize_grouped_ef_batch(ctx, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, mode);
+        return;
+    }
+    quantize_grouped_ef_batch(ctx, entry, Residual::F32, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, mode);
+}
+
+void piquant_hip_quantize_grouped_ef_mixed(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* residual, piquant_dtype_t dtype_residual,
+                                           void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                           piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_ef_mixed";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    if (residual_kind(entry, dtype_in, dtype_residual) == Residual::Same) {
+        piquant_hip_quantize_grouped_ef(ctx, in, dtype_in, residual, out, dtype_out, numel, group_size, scales, zero_points, mode);
+        return;
+    }
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    piquant_hip_quantize_grouped_ef_mixed_batch(ctx, &in, dtype_in, &residual, dtype_residual, &out, dtype_out, &numel, group_size, &scales, &zero_points, 1,
+                                                mode);
+}
+
+void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, void* residual,
+                                                  piquant_dtype_t dtype_residual, const void* const* inputs, const float* const* input_scales,
+                                                  const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                                  size_t group_size, float* scales, uint8_t* zero_points, piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_reduce_quantize_grouped_ef_mixed";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    if (residual_kind(entry, dtype_acc, dtype_residual) == Residual::Same) {
+        piquant_hip_reduce_quantize_grouped_ef(ctx, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel, group_size,
+                                               scales, zero_points, mode);
+        return;
+    }
+    reduce_quantize_grouped(ctx, entry, true, Residual::F32, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
+                            group_size, scales, zero_points, mode);
+}
+
+}  // extern "C"

@@ -279,16 +279,42 @@ float draw_threshold(piquant_context_t* ctx) {
     return std::uniform_real_distribution<float>{0.0f, 1.0f}(ctx->rng);   // reference src/piquant.cpp:199-200
 }
 
-void fill_round_mode(piquant_context_t* ctx, QuantLaunch& q, piquant_round_mode_t mode) {
-    if (mode == PIQUANT_NEAREST) q.round_mode = RM_NEAREST_FAST;
+RoundModeFields round_mode_fields(piquant_context_t* ctx, piquant_round_mode_t mode) {
+    RoundModeFields r {};
+    if (mode == PIQUANT_NEAREST) r.round_mode = RM_NEAREST_FAST;
     else if (ctx->per_element) {
-        q.round_mode = RM_STOCH_ELEM;
-        q.seed = ctx->elem_seed;
-        q.index_base = ctx->elem_base;
+        r.round_mode = RM_STOCH_ELEM;
+        r.seed = ctx->elem_seed;
+        r.index_base = ctx->elem_base;
     } else {
-        q.round_mode = RM_STOCH_CALL;
-        q.threshold = draw_threshold(ctx);
+        r.round_mode = RM_STOCH_CALL;
+        r.threshold = draw_threshold(ctx);
     }
+    return r;
+}
+
+void fill_round_mode(piquant_context_t* ctx, QuantLaunch& q, piquant_round_mode_t mode) {
+    const RoundModeFields r = round_mode_fields(ctx, mode);
+    q.round_mode = r.round_mode;
+    q.threshold = r.threshold;
+    q.seed = r.seed;
+    q.index_base = r.index_base;
+}
+
+void check_dynamic_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_round_mode_t mode) {
+    const dtype_row& dti = dtype_of(dtype_in);
+    const dtype_row& dto = dtype_of(dtype_out);
+    if (dti.quant) panic("quantize: input dtype (%s) must be a dequantized type", dti.name);
+    if (!dto.quant) panic("quantize: output dtype (%s) must be a quantized type", dto.name);
+    if (mode != PIQUANT_NEAREST && mode != PIQUANT_STOCHASTIC) panic("quantize: invalid round mode %d", static_cast<int>(mode));
+}
+
+void check_dequant_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_reduce_op_t op) {
+    const dtype_row& dti = dtype_of(dtype_in);
+    const dtype_row& dto = dtype_of(dtype_out);
+    if (!dti.quant) panic("dequantize: input dtype (%s) must be a quantized type", dti.name);
+    if (dto.quant) panic("dequantize: output dtype (%s) must be a dequantized type", dto.name);
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("dequantize: invalid reduce op %d", static_cast<int>(op));
 }
 
 }  // namespace pq

@@ -1,4 +1,4 @@
-// Host side shared by the translation units behind the C ABI (context.cpp, capi.cpp, capi_dynamic.cpp): the context object, pointer
+// Host side shared by the translation units behind the C ABI (context.cpp, capi.cpp, capi_dynamic.cpp, capi_grouped.cpp): the context object, pointer
 // classification, the completion wait of blocking calls and the ordering of launches that carry a grid barrier.
 #pragma once
 
@@ -229,8 +229,14 @@ const CpuCompanion* try_cpu_companion();        // nullptr when libpiquant_cpu.s
 bool host_calls_go_to_cpu(piquant_context_t* ctx);   // the context's host path with AUTO resolved; caller holds ctx->mu
 void* cpu_context_of(piquant_context_t* ctx);   // the context's companion context (created on first use); caller holds ctx->mu
 
-// round-mode fields of a launch: NEAREST, one threshold per call (src/piquant.cpp:197-201) or the per-element extension
-void fill_round_mode(piquant_context_t* ctx, QuantLaunch& q, piquant_round_mode_t mode);
+// round-mode fields of a launch: NEAREST, one threshold per call (src/piquant.cpp:197-201) or the per-element extension.  A stochastic call on a
+// context without a pinned threshold advances the context's generator by exactly one draw per call of either function; caller holds ctx->mu.
+RoundModeFields round_mode_fields(piquant_context_t* ctx, piquant_round_mode_t mode);
+void fill_round_mode(piquant_context_t* ctx, QuantLaunch& q, piquant_round_mode_t mode);   // the same four fields of a QuantLaunch
+
+// argument checks shared by the additive entry points: the quantize side (types and round mode) and the dequantize side (types and reduce op)
+void check_dynamic_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_round_mode_t mode);
+void check_dequant_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_reduce_op_t op);
 
 // Min/max scan of x with `action` as its epilogue (launch.hpp): one launch for device input; staged chunks plus a fold launch
 // for pageable host input; for an empty input the fold of the armed state (the identities, reference

@@ -1,10 +1,12 @@
-// Compile-time dispatch shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip, kernels_grouped_reduce_ef.hip):
-// runtime group size / types / rounding mode -> std::integral_constant, and the per-call QuantParams.
+// Host code shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip,
+// kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
+// QuantParams, the chunk table and grids, and the launch bodies of the two error-feedback kernel families.
 #pragma once
 
 #include "launch.hpp"
 
 #include "grouped_kernels.hpp"
+#include "stop_event.hpp"
 
 #include <type_traits>
 
@@ -60,12 +62,12 @@ inline void with_round_mode(int round_mode, F&& f) {
     }
 }
 
-inline QuantParams grouped_call_params(float threshold, uint64_t seed, uint64_t index_base) {
+inline QuantParams grouped_call_params(const RoundModeFields& rm) {
     QuantParams p {};
-    p.threshold = threshold;
-    p.seed_lo = static_cast<uint32_t>(seed);
-    p.seed_hi = static_cast<uint32_t>(seed >> 32);
-    p.index_base = index_base;
+    p.threshold = rm.threshold;
+    p.seed_lo = static_cast<uint32_t>(rm.seed);
+    p.seed_hi = static_cast<uint32_t>(rm.seed >> 32);
+    p.index_base = rm.index_base;
     return p;
 }
 
@@ -73,6 +75,89 @@ inline unsigned grouped_blocks(int64_t chunks, const char* what) {
     const int64_t blocks = (chunks + kGroupedBlock / 64 - 1) / (kGroupedBlock / 64);
     if (blocks > 0x7fffffff) panic("%s: %lld blocks in one launch", what, static_cast<long long>(blocks));
     return static_cast<unsigned>(blocks);
+}
+
+// Grid of the guarded (element-by-element) kernels: one wave per group, grid-stride beyond 16 blocks per CU (256 CUs when num_cu is not known).
+inline unsigned grouped_guarded_blocks(int64_t ngroups, int num_cu) {
+    const int64_t want = (ngroups + kGroupedBlock / 64 - 1) / (kGroupedBlock / 64), cap = static_cast<int64_t>(16) * (num_cu > 0 ? num_cu : 256);
+    return static_cast<unsigned>(want < cap ? want : cap);
+}
+
+// chunk_begin[] of a batch argument table whose count and numel[] are set: tensor t owns chunks [chunk_begin[t], chunk_begin[t + 1]) of
+// chunk_elems elements each -- G * NG for the <G, NG> tile of a quantize kernel (NG whole groups per chunk), the tile's CHUNK_ELEMS for
+// dequantize.  Returns the total.
+template <class Args>
+inline int64_t fill_chunk_table(Args& a, int64_t chunk_elems) {
+    int64_t chunks = 0;
+    for (int t = 0; t < a.count; ++t) {
+        a.chunk_begin[t] = chunks;
+        chunks += (a.numel[t] + chunk_elems - 1) / chunk_elems;
+    }
+    a.chunk_begin[a.count] = chunks;
+    return chunks;
+}
+
+// Launch bodies of an error-feedback kernel family; each family's unit instantiates them once (kernels_grouped_ef.hip: the residual has the
+// tensor's type; kernels_grouped_ef_f32r.hip: a bfloat16 tensor with a float32 residual).  Family::name names it in messages;
+// Family::with_pipeline_type(dt_in, f) calls f(std::integral_constant<int, DT>) for the type DT that picks the tile, the rounding modes and the
+// kernels; Family::single / batch <DT, BITS, MODE, G>() and Family::guarded <DT, BITS, MODE>() return the kernels.
+template <class Family>
+void launch_grouped_ef_batch(const GroupedEfBatchLaunch& b, hipStream_t stream) {
+    static_assert(kGroupedBatchMaxTensors == kGroupedBatchMax, "host and device batch limits");
+    if (b.count <= 0) return;
+    if (b.count > kGroupedBatchMax) panic("%s_batch: %d tensors, at most %d per launch", Family::name, b.count, kGroupedBatchMax);
+    const QuantParams p = grouped_call_params(b.rm);
+    Family::with_pipeline_type(b.dt_in, [&](auto di) {
+        constexpr int DT = decltype(di)::value;
+        with_quant_bits(b.dt_out, [&](auto bi) {
+            constexpr int BITS = decltype(bi)::value;
+            with_round_mode<DT, BITS>(b.rm.round_mode, [&](auto mi) {
+                constexpr int MODE = decltype(mi)::value;
+                with_group_size(b.group_size, Family::name, [&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    constexpr int NG = GroupedQuantTile<DT, BITS, G>::NG;
+                    GroupedEfBatchArgs a {};
+                    for (int t = 0; t < b.count; ++t) {
+                        a.in[t] = b.t[t].in;
+                        a.residual[t] = b.t[t].residual;
+                        a.out[t] = static_cast<uint8_t*>(b.t[t].out);
+                        a.scales[t] = b.t[t].scales;
+                        a.zero_points[t] = b.t[t].zero_points;
+                        a.numel[t] = b.t[t].numel;
+                    }
+                    a.count = b.count;
+                    const int64_t chunks = fill_chunk_table(a, static_cast<int64_t>(G) * NG);
+                    if (chunks == 0) return;
+                    const dim3 grid(grouped_blocks(chunks, Family::name));
+                    if (b.count == 1)   // the single call: its arguments arrive as leading scalars, no table
+                        PQ_LAUNCH((Family::template single<DT, BITS, MODE, G>()), grid, dim3(kGroupedBlock), 0, stream, a.in[0], a.residual[0], a.out[0],
+                                  a.numel[0], a.scales[0], a.zero_points[0], (a.numel[0] + G - 1) / G, p);
+                    else PQ_LAUNCH((Family::template batch<DT, BITS, MODE, G>()), grid, dim3(kGroupedBlock), 0, stream, a, p);
+                });
+            });
+        });
+    });
+    PQ_HIP(hipGetLastError());
+}
+
+template <class Family>
+void launch_grouped_ef_guarded(const GroupedEfLaunch& q, hipStream_t stream, int num_cu) {
+    if (q.numel <= 0) return;
+    const QuantParams p = grouped_call_params(q.rm);
+    const int64_t ngroups = (q.numel + q.group_size - 1) / q.group_size;
+    const dim3 grid(grouped_guarded_blocks(ngroups, num_cu));
+    Family::with_pipeline_type(q.dt_in, [&](auto di) {
+        constexpr int DT = decltype(di)::value;
+        with_quant_bits(q.dt_out, [&](auto bi) {
+            constexpr int BITS = decltype(bi)::value;
+            with_round_mode<DT, BITS>(q.rm.round_mode, [&](auto mi) {
+                constexpr int MODE = decltype(mi)::value;
+                PQ_LAUNCH((Family::template guarded<DT, BITS, MODE>()), grid, dim3(kGroupedBlock), 0, stream, q.in, q.residual, static_cast<uint8_t*>(q.out),
+                          q.numel, q.group_size, q.scales, q.zero_points, ngroups, p.threshold, p.seed_lo, p.seed_hi, p.index_base);
+            });
+        });
+    });
+    PQ_HIP(hipGetLastError());
 }
 
 }  // namespace pq

@@ -797,7 +797,7 @@ void quantize_grouped_given(const GroupedQuantLaunch& q, const QuantParams& p, h
 
 template <int DT_IN, int BITS>
 void quantize_grouped_mode(const GroupedQuantLaunch& q, const QuantParams& p, hipStream_t stream, int num_cu) {
-    switch (q.round_mode) {
+    switch (q.rm.round_mode) {
         case RM_NEAREST_FAST:
         case RM_NEAREST_I64:
             // the nearest step of quantize_uniform for the pair (quantize_mode above): f32 -> uint2 has only the generic one
@@ -806,7 +806,7 @@ void quantize_grouped_mode(const GroupedQuantLaunch& q, const QuantParams& p, hi
             return;
         case RM_STOCH_CALL: quantize_grouped_given<DT_IN, BITS, RM_STOCH_CALL>(q, p, stream, num_cu); return;
         case RM_STOCH_ELEM: quantize_grouped_given<DT_IN, BITS, RM_STOCH_ELEM>(q, p, stream, num_cu); return;
-        default: panic("invalid rounding mode %d", q.round_mode);
+        default: panic("invalid rounding mode %d", q.rm.round_mode);
     }
 }
 
@@ -875,10 +875,10 @@ void dequantize_grouped_out(const GroupedDequantLaunch& d, hipStream_t stream, i
 void launch_quantize_grouped(const GroupedQuantLaunch& q, hipStream_t stream, int num_cu) {
     if (q.numel <= 0) return;
     QuantParams p {};
-    p.threshold = q.threshold;
-    p.seed_lo = static_cast<uint32_t>(q.seed);
-    p.seed_hi = static_cast<uint32_t>(q.seed >> 32);
-    p.index_base = q.index_base;
+    p.threshold = q.rm.threshold;
+    p.seed_lo = static_cast<uint32_t>(q.rm.seed);
+    p.seed_hi = static_cast<uint32_t>(q.rm.seed >> 32);
+    p.index_base = q.rm.index_base;
     switch (q.dt_in) {
         case DT_F32: quantize_grouped_bits<DT_F32>(q, p, stream, num_cu); break;
         case DT_BF16: quantize_grouped_bits<DT_BF16>(q, p, stream, num_cu); break;

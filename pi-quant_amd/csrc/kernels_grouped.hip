@@ -13,29 +13,26 @@ void launch_quantize_grouped_batch(const GroupedQuantBatchLaunch& b, hipStream_t
     static_assert(kGroupedBatchMaxTensors == kGroupedBatchMax, "host and device batch limits");
     if (b.count <= 0) return;
     if (b.count > kGroupedBatchMax) panic("quantize_grouped_batch: %d tensors, at most %d per launch", b.count, kGroupedBatchMax);
-    const QuantParams p = grouped_call_params(b.threshold, b.seed, b.index_base);
+    const QuantParams p = grouped_call_params(b.rm);
     with_float_type(b.dt_in, [&](auto di) {
         constexpr int DT_IN = decltype(di)::value;
         with_quant_bits(b.dt_out, [&](auto bi) {
             constexpr int BITS = decltype(bi)::value;
-            with_round_mode<DT_IN, BITS>(b.round_mode, [&](auto mi) {
+            with_round_mode<DT_IN, BITS>(b.rm.round_mode, [&](auto mi) {
                 constexpr int MODE = decltype(mi)::value;
                 with_group_size(b.group_size, "quantize_grouped_batch", [&](auto gi) {
                     constexpr int G = decltype(gi)::value;
                     constexpr int NG = GroupedQuantTile<DT_IN, BITS, G>::NG;
                     GroupedQuantBatchArgs a {};
-                    int64_t chunks = 0;
                     for (int t = 0; t < b.count; ++t) {
-                        a.in[t] = b.in[t];
-                        a.out[t] = static_cast<uint8_t*>(b.out[t]);
-                        a.scales[t] = b.scales[t];
-                        a.zero_points[t] = b.zero_points[t];
-                        a.numel[t] = b.numel[t];
-                        a.chunk_begin[t] = chunks;
-                        chunks += ((b.numel[t] + G - 1) / G + NG - 1) / NG;
+                        a.in[t] = b.t[t].in;
+                        a.out[t] = static_cast<uint8_t*>(b.t[t].out);
+                        a.scales[t] = b.t[t].scales;
+                        a.zero_points[t] = b.t[t].zero_points;
+                        a.numel[t] = b.t[t].numel;
                     }
-                    a.chunk_begin[b.count] = chunks;
                     a.count = b.count;
+                    const int64_t chunks = fill_chunk_table(a, static_cast<int64_t>(G) * NG);
                     if (chunks == 0) return;
                     const dim3 grid(grouped_blocks(chunks, "quantize_grouped_batch"));
                     if (b.params_given) PQ_LAUNCH((quantize_grouped_batch_kernel<DT_IN, BITS, MODE, G, true>), grid, dim3(kGroupedBlock), 0, stream, a, p);
@@ -58,18 +55,15 @@ void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStre
                 constexpr int G = decltype(gi)::value;
                 constexpr int64_t CE = GroupedDequantTile<BITS, DT_OUT>::CHUNK_ELEMS;
                 GroupedDequantBatchArgs a {};
-                int64_t chunks = 0;
                 for (int t = 0; t < b.count; ++t) {
-                    a.in[t] = static_cast<const uint8_t*>(b.in[t]);
-                    a.out[t] = b.out[t];
-                    a.scales[t] = b.scales[t];
-                    a.zero_points[t] = b.zero_points[t];
-                    a.numel[t] = b.numel[t];
-                    a.chunk_begin[t] = chunks;
-                    chunks += (b.numel[t] + CE - 1) / CE;
+                    a.in[t] = static_cast<const uint8_t*>(b.t[t].in);
+                    a.out[t] = b.t[t].out;
+                    a.scales[t] = b.t[t].scales;
+                    a.zero_points[t] = b.t[t].zero_points;
+                    a.numel[t] = b.t[t].numel;
                 }
-                a.chunk_begin[b.count] = chunks;
                 a.count = b.count;
+                const int64_t chunks = fill_chunk_table(a, CE);
                 if (chunks == 0) return;
                 const dim3 grid(grouped_blocks(chunks, "dequantize_grouped_batch"));
                 if (b.op == OP_ADD) PQ_LAUNCH((dequantize_grouped_batch_kernel<BITS, DT_OUT, OP_ADD, G>), grid, dim3(kGroupedBlock), 0, stream, a);
@@ -84,26 +78,26 @@ void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t st
     static_assert(kGroupedReduceMaxInputs == kGroupedReduceMaxTerms, "host and device term limits");
     if (r.numel <= 0) return;
     if (r.count < 0 || r.count > kGroupedReduceMaxTerms) panic("reduce_quantize_grouped: %d terms, at most %d per launch", r.count, kGroupedReduceMaxTerms);
-    const QuantParams p = grouped_call_params(r.threshold, r.seed, r.index_base);
+    const QuantParams p = grouped_call_params(r.rm);
     GroupedTerms terms {};
     for (int i = 0; i < r.count; ++i) {
-        terms.in[i] = static_cast<const uint8_t*>(r.in[i]);
-        terms.scales[i] = r.in_scales[i];
-        terms.zero_points[i] = r.in_zero_points[i];
+        terms.in[i] = static_cast<const uint8_t*>(r.term[i].in);
+        terms.scales[i] = r.term[i].scales;
+        terms.zero_points[i] = r.term[i].zero_points;
     }
     terms.count = r.count;
     const int64_t ngroups = (r.numel + r.group_size - 1) / r.group_size;
-    with_float_type(r.dt_acc, [&](auto di) {
+    with_float_type(r.dt_in, [&](auto di) {
         constexpr int DT_ACC = decltype(di)::value;
         with_quant_bits(r.dt_out, [&](auto bi) {
             constexpr int BITS = decltype(bi)::value;
-            with_round_mode<DT_ACC, BITS>(r.round_mode, [&](auto mi) {
+            with_round_mode<DT_ACC, BITS>(r.rm.round_mode, [&](auto mi) {
                 constexpr int MODE = decltype(mi)::value;
                 with_group_size(r.group_size, "reduce_quantize_grouped", [&](auto gi) {
                     constexpr int G = decltype(gi)::value;
                     constexpr int NG = GroupedQuantTile<DT_ACC, BITS, G>::NG;
                     const dim3 grid(grouped_blocks((ngroups + NG - 1) / NG, "reduce_quantize_grouped"));
-                    PQ_LAUNCH((reduce_quantize_grouped_kernel<DT_ACC, BITS, MODE, G>), grid, dim3(kGroupedBlock), 0, stream, r.acc, static_cast<uint8_t*>(r.out),
+                    PQ_LAUNCH((reduce_quantize_grouped_kernel<DT_ACC, BITS, MODE, G>), grid, dim3(kGroupedBlock), 0, stream, r.in, static_cast<uint8_t*>(r.out),
                               r.numel, r.scales, r.zero_points, ngroups, p, terms);
                 });
             });

@@ -93,118 +93,68 @@ void launch_dequantize_batch(const DequantBatchLaunch& d, hipStream_t stream);
 // Group-wise quantization (grouped_kernels.hpp): one (scale, zero point) per run of group_size contiguous elements, group_size a power of
 // two in [32, 4096].  Quantize computes the parameters (written to scales / zero_points) or, with params_given, reads them; either way ONE
 // launch.  Buffers 16-byte aligned take the streaming kernels, anything else the guarded one-wave-per-group kernel.
+// Every grouped descriptor is made of the same three pieces: what one tensor brings (GroupedTensor), what the members of a call share
+// (GroupedQuantCall / GroupedDequantCall) and, in the former, the call's round-mode fields.  A single launch is {tensor, call}, a batch is the call
+// plus up to kGroupedBatchMaxTensors tensors, so "run member i alone" is GroupedQuantLaunch {b.t[i], b}.
 constexpr int kGroupedMinG = 32, kGroupedMaxG = 4096;
-struct GroupedQuantLaunch {
-    const void* in;
-    void* out;
-    int64_t numel;
-    int64_t group_size;
-    float* scales;         // float32[ngroups], device
-    uint8_t* zero_points;  // uint8[ngroups], device
-    bool params_given;
-    int dt_in;             // DT_F32 / DT_BF16
-    int dt_out;            // DT_UINT2/4/8
+struct RoundModeFields {   // context.hpp, round_mode_fields
     int round_mode;        // RM_* (device_math.hpp)
     float threshold;
     uint64_t seed;
     uint64_t index_base;
 };
-
-struct GroupedDequantLaunch {
-    const void* in;
+struct GroupedTensor {
+    const void* in;        // the tensor; the accumulator of a reduce
+    void* residual;        // error feedback only: numel elements, read and written
     void* out;
+    float* scales;         // float32[ngroups], device (dequantize only reads the parameters)
+    uint8_t* zero_points;  // uint8[ngroups], device
     int64_t numel;
+};
+struct GroupedQuantCall {
     int64_t group_size;
-    const float* scales;
-    const uint8_t* zero_points;
+    int dt_in;             // DT_F32 / DT_BF16
+    int dt_out;            // DT_UINT2/4/8
+    bool params_given;     // plain quantize only
+    RoundModeFields rm;
+};
+struct GroupedDequantCall {
+    int64_t group_size;
     int dt_in;             // DT_UINT2/4/8
     int dt_out;            // DT_F32 / DT_BF16
     int op;                // OP_SET / OP_ADD
 };
+struct GroupedQuantLaunch : GroupedTensor, GroupedQuantCall {};
+struct GroupedDequantLaunch : GroupedTensor, GroupedDequantCall {};
 
 // Batches (up to kGroupedBatchMaxTensors tensors of one dtype pair, group size and round mode in ONE launch, every buffer 16-byte aligned and every
 // tensor non-empty: the caller sends anything else through the single calls) and the fused reduce + quantize (every buffer 16-byte aligned, at
 // most kGroupedReduceMaxInputs terms: the caller adds the surplus first, or runs the two-step form for misaligned buffers).
 constexpr int kGroupedBatchMaxTensors = 16;
-struct GroupedQuantBatchLaunch {
-    const void* in[kGroupedBatchMaxTensors];
-    void* out[kGroupedBatchMaxTensors];
-    float* scales[kGroupedBatchMaxTensors];
-    uint8_t* zero_points[kGroupedBatchMaxTensors];
-    int64_t numel[kGroupedBatchMaxTensors];
+template <class Call>
+struct GroupedBatch : Call {
+    GroupedTensor t[kGroupedBatchMaxTensors];
     int count;
-    int64_t group_size;
-    bool params_given;
-    int dt_in;
-    int dt_out;
-    int round_mode;
-    float threshold;
-    uint64_t seed;
-    uint64_t index_base;
 };
+using GroupedQuantBatchLaunch = GroupedBatch<GroupedQuantCall>;
+using GroupedDequantBatchLaunch = GroupedBatch<GroupedDequantCall>;
 
-struct GroupedDequantBatchLaunch {
-    const void* in[kGroupedBatchMaxTensors];
-    void* out[kGroupedBatchMaxTensors];
-    const float* scales[kGroupedBatchMaxTensors];
-    const uint8_t* zero_points[kGroupedBatchMaxTensors];
-    int64_t numel[kGroupedBatchMaxTensors];
-    int count;
-    int64_t group_size;
-    int dt_in;
-    int dt_out;
-    int op;
-};
-
-// out, scales, zero_points = quantize_grouped(acc + sum_i dequantize_grouped(in[i], in_scales[i], in_zero_points[i])), terms added in order
+// out, scales, zero_points = quantize_grouped(in + sum_i dequantize_grouped(term[i])), terms added in order; dt_out is the terms' type too.
+// Error feedback on the re-quantized partial sum (grouped_kernels.hpp, reduce_quantize_grouped_ef_kernel) is the same descriptor with the residual,
+// of dt_in and numel elements, 16-byte aligned: y = in + terms + residual, (out, scales, zero_points) = quantize_grouped(y),
+// residual <- y - dequantize_grouped(out), in ONE launch.
 constexpr int kGroupedReduceMaxInputs = 16;
-struct GroupedReduceLaunch {
-    const void* acc;
-    void* out;
-    int64_t numel;
-    int64_t group_size;
-    float* scales;
-    uint8_t* zero_points;
-    const void* in[kGroupedReduceMaxInputs];
-    const float* in_scales[kGroupedReduceMaxInputs];
-    const uint8_t* in_zero_points[kGroupedReduceMaxInputs];
+struct GroupedReduceLaunch : GroupedTensor, GroupedQuantCall {
+    GroupedTensor term[kGroupedReduceMaxInputs];   // in, scales and zero_points are read
     int count;
-    int dt_acc;            // DT_F32 / DT_BF16
-    int dt_out;            // DT_UINT2/4/8 (the terms' type too)
-    int round_mode;
-    float threshold;
-    uint64_t seed;
-    uint64_t index_base;
-};
-
-// Error feedback on a re-quantized partial sum (grouped_kernels.hpp, reduce_quantize_grouped_ef_kernel): `r` as for launch_reduce_quantize_grouped
-// (every buffer 16-byte aligned, at most kGroupedReduceMaxInputs terms) plus the residual, of r.dt_acc and r.numel elements, 16-byte aligned:
-// y = acc + terms + residual, (out, scales, zero_points) = quantize_grouped(y), residual <- y - dequantize_grouped(out), in ONE launch.
-struct GroupedReduceEfLaunch {
-    GroupedReduceLaunch r;
-    void* residual;
 };
 
 // Error feedback (grouped_kernels.hpp, quantize_grouped_ef_batch_kernel): per tensor y = in + residual, (out, scales, zero_points) =
 // quantize_grouped(y) with computed parameters, residual <- y - dequantize_grouped(out), in ONE launch for up to kGroupedBatchMaxTensors tensors
-// (every buffer 16-byte aligned, every tensor non-empty; a batch of one launches quantize_grouped_ef_kernel, whose arguments are leading scalars).  launch_quantize_grouped_ef_guarded runs tensor t of the batch alone through the
-// element-by-element kernel: the same bytes for buffers of any alignment.
-struct GroupedEfBatchLaunch {
-    const void* in[kGroupedBatchMaxTensors];
-    void* residual[kGroupedBatchMaxTensors];
-    void* out[kGroupedBatchMaxTensors];
-    float* scales[kGroupedBatchMaxTensors];
-    uint8_t* zero_points[kGroupedBatchMaxTensors];
-    int64_t numel[kGroupedBatchMaxTensors];
-    int count;
-    int64_t group_size;
-    int dt_in;
-    int dt_out;
-    int round_mode;
-    float threshold;
-    uint64_t seed;
-    uint64_t index_base;
-};
+// (every buffer 16-byte aligned, every tensor non-empty; a batch of one launches quantize_grouped_ef_kernel, whose arguments are leading scalars).
+// launch_quantize_grouped_ef_guarded runs one tensor alone through the element-by-element kernel: the same bytes for buffers of any alignment.
+using GroupedEfBatchLaunch = GroupedQuantBatchLaunch;   // every t[i].residual set; params_given unused
+using GroupedEfLaunch = GroupedQuantLaunch;
 
 // All launches are asynchronous on `stream`; num_cu sizes capped grids.
 void launch_quantize(const QuantLaunch& q, hipStream_t stream, int num_cu);
@@ -216,12 +166,12 @@ void launch_quantize_grouped_batch(const GroupedQuantBatchLaunch& b, hipStream_t
 void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStream_t stream);
 void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream);
 void launch_quantize_grouped_ef_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
-void launch_reduce_quantize_grouped_ef(const GroupedReduceEfLaunch& e, hipStream_t stream);
-void launch_quantize_grouped_ef_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
+void launch_reduce_quantize_grouped_ef(const GroupedReduceLaunch& r, hipStream_t stream);
+void launch_quantize_grouped_ef_guarded(const GroupedEfLaunch& q, hipStream_t stream, int num_cu);
 // The same two for bfloat16 tensors (b.dt_in == DT_BF16) whose residuals are float32 (kernels_grouped_ef_f32r.hip): the bytes of the float32 call
 // on the widened tensor.  The streaming launch needs residual and out 16-byte aligned and the tensor 8-byte aligned; the guarded one takes anything.
 void launch_quantize_grouped_ef_f32r_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
-void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfBatchLaunch& b, int t, hipStream_t stream, int num_cu);
+void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfLaunch& q, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes
