@@ -100,8 +100,9 @@ void add_terms(piquant_context_t* ctx, const Terms& ts, size_t from, size_t to, 
 }
 
 // Index of the first term the fused reduce kernel takes; the terms in front of it go into acc by grouped dequantize ADD first.  Every buffer of
-// the call 16-byte aligned: the surplus over kGroupedReduceMaxInputs goes first and the last terms are fused.  Anything misaligned: count, i.e.
-// every term is added first and acc is quantized alone -- the two-step form, the same bytes.  (No terms: nothing to fuse either way.)
+// the call aligned as its kernel loads it (16 bytes; 8 for a bfloat16 acc with a float32 residual): the surplus over kGroupedReduceMaxInputs goes
+// first and the last terms are fused.  Anything misaligned: count, i.e. every term is added first and acc is quantized alone -- the two-step form,
+// the same bytes.  (No terms: nothing to fuse either way.)
 size_t fused_from(size_t count, bool all_aligned) {
     if (!all_aligned) return count;
     return count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0;
@@ -176,7 +177,8 @@ void quantize_grouped_ef_batch(piquant_context_t* ctx, const char* entry, Residu
 
 // The three reduce entries behind their type checks: out = quantize_grouped(acc + terms [+ residual]), with error feedback when `ef`.
 // The call's one threshold is drawn once, after every buffer is resolved, whichever form then runs; numel == 0 returns before it.  A float32
-// residual for a bfloat16 accumulator has no fused kernel yet: it always takes the two-step form.
+// residual for a bfloat16 accumulator fuses like the others (kernels_grouped_reduce_ef_f32r.hip), with ef_streams' rule for the accumulator:
+// 8-byte aligned, the width of its loads.
 void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef, Residual k, void* acc, piquant_dtype_t dtype_acc, void* residual,
                              const void* const* inputs, const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count,
                              void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
@@ -191,7 +193,7 @@ void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef,
     const GroupedTensor t = resolve_tensor(ctx, w, acc, ef ? residual : nullptr, out, scales, zero_points, numel);
     if (ef) check_ef_elements(k, w, t);
     const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, const_cast<void*>(t.in) /* acc */, numel);
-    const bool aligned = terms.aligned && aligned16(t.in) && aligned16(t.out) && (!ef || (k == Residual::Same && aligned16(t.residual)));
+    const bool aligned = terms.aligned && (ef ? ef_streams(k, t) : aligned16(t.in) && aligned16(t.out));
     const GroupedQuantCall call {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)};
     StopEventScope completion(ctx);
     IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
@@ -200,8 +202,9 @@ void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef,
     if (first < count) {
         GroupedReduceLaunch r {t, call, {}, static_cast<int>(count - first)};
         std::copy(terms.term.begin() + static_cast<std::ptrdiff_t>(first), terms.term.end(), r.term);
-        if (ef) launch_reduce_quantize_grouped_ef(r, ctx->stream);
-        else launch_reduce_quantize_grouped(r, ctx->stream);
+        if (!ef) launch_reduce_quantize_grouped(r, ctx->stream);
+        else if (k == Residual::F32) launch_reduce_quantize_grouped_ef_f32r(r, ctx->stream);
+        else launch_reduce_quantize_grouped_ef(r, ctx->stream);
     } else if (ef) {   // no terms, or the two-step form: quantize_grouped_ef(acc, residual)
         ef_quantize_one(ctx, k, GroupedEfLaunch {t, call});
     } else {           // quantize_grouped(acc)

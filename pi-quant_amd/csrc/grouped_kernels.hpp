@@ -1166,4 +1166,121 @@ quantize_grouped_ef_f32r_scalar_kernel(const void* __restrict__ in, void* residu
     }
 }
 
+// ---- The two fused: error feedback on a re-quantized partial sum of a bfloat16 accumulator with a float32 residual
+// (piquant_hip_reduce_quantize_grouped_ef_mixed).  The bytes of k grouped dequantize ADD calls into the bfloat16 acc followed by the mixed
+// quantize above, in ONE launch: acc <- rn_bf16(widen(acc) + d(term_i)) term by term with d the uint -> bfloat16 dequantize form, then
+// y = rn_f32(widen(acc) + r), the float32 quantize chunk body and r <- rn_f32(y - d).  The tile is the float32 one (a lane-row is four elements),
+// the term staging and the prefetch order are reduce_quantize_grouped_ef_kernel's on that tile.  The accumulator rows stay PACKED (u32x2: two
+// bfloat16 a dword, 2 NV registers instead of 4 NV) through the term loop -- every add rounds back to bfloat16 anyway, with the pairwise
+// conversion the bfloat16 tile uses -- and are widened once behind the last term.  No scan, no atomics, no grid barrier; waves never wait for
+// one another.
+
+// t[r] = rn_bf16(widen(t[r]) + the dequantized packed bytes of the lane's four-element vector r), in the uint -> bfloat16 form of the pair;
+// geometry and group parameters per set of the float32 tile
+template <int BITS, int G, int NV_ = GroupedQuantTile<DT_F32, BITS, G>::NV>
+__device__ __forceinline__ void grouped_add_term_bf16x4(u32x2 (&t)[NV_], const uint8_t* stage, const float* s_scale, const float* s_bias,
+                                                        const int32_t* s_zp, int lane) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
+    constexpr int FORM = DequantForm<BITS, DT_BF16>::value;
+    static_assert(T::EPV == 4 && OB <= 4, "four elements a lane-row: at most one packed dword");
+    DequantParams p[SETS];
+#pragma unroll
+    for (int s = 0; s < SETS; ++s) {
+        const int slot = s * GPR + lane / LPG;
+        p[s] = DequantParams {};
+        p[s].scale = s_scale[slot];
+        p[s].bias = s_bias[slot];
+        p[s].zp32 = s_zp[slot];
+        p[s].zp64 = p[s].zp32;
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const uint8_t* src = stage + (r * 64 + lane) * OB;
+        uint32_t w;
+        if constexpr (OB == 1) w = *src;
+        else if constexpr (OB == 2) w = *reinterpret_cast<const uint16_t*>(src);
+        else w = *reinterpret_cast<const uint32_t*>(src);
+        float f[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[e] = dequant_one<FORM>((w >> (e * BITS)) & ((1u << BITS) - 1u), p[r / RPG]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            t[r][h] = f32x2_to_bf16x2_bits(__fadd_rn(f[2 * h], __uint_as_float(t[r][h] << 16)),
+                                           __fadd_rn(f[2 * h + 1], __uint_as_float(t[r][h] & 0xffff0000u)));
+    }
+}
+
+template <int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+reduce_quantize_grouped_ef_f32r_kernel(const void* __restrict__ acc, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                       uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0, GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    using L = GroupedTermLoad<DT_F32, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // a term's {scale, bias}; then {min, max}, then {1/scale, zero point, scale}
+    __shared__ int32_t s_z[WAVES][NG];                                 // a term's zero point
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_out[wave];
+    const int count = terms.count;
+
+    u32x2 t[NV];
+    u32x4 raw[NV], res[NV];
+    if (full) {
+        L next;
+        if (count > 0) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+        grouped_load_bf16x4<NV>(acc, numel, v0, lane, true, t);
+        if (count == 0) grouped_load<DT_F32, NV>(residual, numel, v0, lane, true, res);
+        for (int i = 0; i + 1 < count; ++i) {
+            const L cur = next;
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+            wave_lds_sync();
+            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+        if (count > 0) {   // the last term: nothing left to prefetch but the residual
+            grouped_park_term(next, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            grouped_load<DT_F32, NV>(residual, numel, v0, lane, true, res);
+            wave_lds_sync();
+            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+    } else {
+        // the tensor ends inside this chunk: acc and residual read as quiet NaNs behind it, a term byte by byte up to its last byte (zeros behind it)
+        grouped_load_bf16x4<NV>(acc, numel, v0, lane, false, t);
+        grouped_load<DT_F32, NV>(residual, numel, v0, lane, false, res);
+        const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
+        for (int i = 0; i < count; ++i) {
+            const uint8_t* c = terms.in[i] + v0 * T::OB;
+            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
+            if (has_group) {
+                const float scale = terms.scales[i][gj];
+                const int32_t zp = terms.zero_points[i][gj];
+                s_a[wave][lane] = scale;
+                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
+                s_z[wave][lane] = zp;
+            }
+            wave_lds_sync();
+            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            wave_lds_sync();
+        }
+    }
+    grouped_widen_bf16x4<NV>(t, raw);
+    grouped_add_residual<DT_F32, NV>(raw, res);
+    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave],
+                                                                   s_c[wave]);
+    grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c[wave], s_b[wave]);
+}
+
 }  // namespace pq

@@ -172,6 +172,9 @@ void launch_quantize_grouped_ef_guarded(const GroupedEfLaunch& q, hipStream_t st
 // on the widened tensor.  The streaming launch needs residual and out 16-byte aligned and the tensor 8-byte aligned; the guarded one takes anything.
 void launch_quantize_grouped_ef_f32r_batch(const GroupedEfBatchLaunch& b, hipStream_t stream);
 void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfLaunch& q, hipStream_t stream, int num_cu);
+// The fused reduce with error feedback for that pair (kernels_grouped_reduce_ef_f32r.hip): r.dt_in == DT_BF16, r.residual float32.  Terms, residual
+// and out 16-byte aligned, the accumulator 8-byte aligned (its lane-row is four elements), at most kGroupedReduceMaxInputs terms.
+void launch_reduce_quantize_grouped_ef_f32r(const GroupedReduceLaunch& r, hipStream_t stream);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -482,8 +482,9 @@ class Context:
         """``reduce_quantize_grouped_ptr`` with error feedback on the re-quantization (``piquant_hip_reduce_quantize_grouped_ef``: one launch for up to
         16 terms): quantizes ``acc + sum_i dequantize_grouped(input i) + residual`` and leaves what the quantization lost in ``residual`` (``numel``
         elements of ``dtype_acc``).  The bytes of grouped dequantize ADD per term into ``acc`` followed by ``quantize_grouped_ef_ptr(acc, residual)``;
-        ``acc`` is unspecified afterwards.  ``residual_dtype`` (``None``: ``dtype_acc``) names the residual's type: ``F32`` for a ``BF16`` ``acc`` runs
-        the grouped dequantize ADD calls followed by the mixed ``quantize_grouped_ef_ptr`` (``piquant_hip_reduce_quantize_grouped_ef_mixed``)."""
+        ``acc`` is unspecified afterwards.  ``residual_dtype`` (``None``: ``dtype_acc``) names the residual's type: ``F32`` for a ``BF16`` ``acc`` writes
+        the bytes of the grouped dequantize ADD calls followed by the mixed ``quantize_grouped_ef_ptr``, still in one launch
+        (``piquant_hip_reduce_quantize_grouped_ef_mixed``)."""
         n = len(ptrs_in)
         assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
         self.assume_device_pointers(_device_ptrs)

@@ -634,7 +634,7 @@ def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensor
     ``acc``'s dtype, device and numel that the caller keeps between steps (zeros before the first); the terms are as for
     ``reduce_quantize_grouped``.  Returns (out, out_scales, out_zero_points); ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
     piquant_hip_reduce_quantize_grouped_ef).  A bfloat16 ``acc`` also takes a float32 ``residual``: the same two-call identity with the mixed
-    ``quantize_grouped_ef(acc, residual)`` as its second call, and run as that composition (k + 1 launches; no fused kernel for this pair)."""
+    ``quantize_grouped_ef(acc, residual)`` as its second call, in one launch like the others (``acc`` 8-byte aligned is enough for this pair)."""
     _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
     _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
     _check_group_size(group_size)

@@ -25,7 +25,12 @@ composition that defines it (the tensor widened to float32, then the float32 qua
 in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
 profiles/grouped_ef_f32r_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows reduce_ef_f32r: the fused reduce_quantize_grouped_ef of a bfloat16 accumulator with a FLOAT32 residual (G = 128; uint8 and uint4 terms
+with k = 1 and k = 7, uint2 with k = 1) next to the composition that defines it (k grouped dequantize ADD launches into the bfloat16 acc + the
+mixed quantize_grouped_ef) in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
+profiles/grouped_reduce_ef_f32r_bench.json; --rows all appends these rows to its table.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -442,16 +447,69 @@ def ef_f32r_rows(ctx, dev, stream, args, G=128):
     return rows
 
 
+def reduce_ef_f32r_rows(ctx, dev, stream, args, G=128):
+    """fused reduce + error-feedback quantize of a bf16 acc with an fp32 residual against the composition that defines it"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(6)
+    bf16, f32 = piquant.DataType.BF16, piquant.DataType.F32
+    for qname, k in (("uint8", 1), ("uint8", 7), ("uint4", 1), ("uint4", 7), ("uint2", 1)):
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(NUMEL)
+        fused_bytes = NUMEL * (2 + 4 + 4) + (k + 1) * (nq + 5 * ng)           # acc in; residual in and out; k terms in, one record out
+        comp_bytes = NUMEL * (4 * k + 2 + 4 + 4) + (k + 1) * (nq + 5 * ng)    # acc in and out per term; then acc in, residual in and out
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        accs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g).to(torch.bfloat16) for _ in range(nbuf)]
+        ress = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g) * 0.01 for _ in range(nbuf)]
+        terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.reduce_quantize_grouped_ef_ptr(accs[i].data_ptr(), bf16, ress[i].data_ptr(), [t.data_ptr() for t in terms[i]], [t.data_ptr() for t in tsc[i]],
+                                               [t.data_ptr() for t in tzp[i]], outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                               piquant.RoundMode.NEAREST, _device_ptrs=True, residual_dtype=f32)
+
+        def composition(i):   # adds into accs[i] in place, call after call: the sums drift by at most 0.5 a term and call, far from any overflow,
+            for t, s_, z_ in zip(terms[i], tsc[i], tzp[i]):   # and neither form's time depends on the values
+                ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, accs[i].data_ptr(), bf16, NUMEL, G, s_.data_ptr(), z_.data_ptr(), piquant.ReduceOp.ADD,
+                                           _device_ptrs=True)
+            ctx.quantize_grouped_ef_ptr(accs[i].data_ptr(), bf16, ress[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True, residual_dtype=f32)
+
+        pair = f"bf16+{k}x{qname}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("reduce_ef_f32r_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("reduce_quantize_grouped_ef_f32r", pair, G, us_f, fused_bytes, s_f)
+        fr["over_composition"] = round(us_f / us_c, 3)
+        fr["bytes_over_composition"] = round(fused_bytes / comp_bytes, 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}", flush=True)
+        rows += [cr, fr]
+        del accs, ress, terms, tsc, tzp, outs, sc, zs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
-                                                   "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json"}[args.rows])
+                                                   "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
+                                                   "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -469,6 +527,8 @@ def main():
         rows = reduce_ef_rows(ctx, dev, stream, args)
     if args.rows == "ef_f32r":
         rows = ef_f32r_rows(ctx, dev, stream, args)
+    if args.rows == "reduce_ef_f32r":
+        rows = reduce_ef_f32r_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
@@ -510,6 +570,8 @@ def main():
             del outs, rec
         del xs
         torch.cuda.empty_cache()
+    if args.rows == "all":
+        rows += reduce_ef_f32r_rows(ctx, dev, stream, args)
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
