@@ -293,6 +293,35 @@ PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context
                                                                  size_t count, void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size,
                                                                  float* scales, uint8_t* zero_points, piquant_round_mode_t mode);
 
+/* Group-wise quantize-dequantize ("fake quantization"): out (op)= dequantize_grouped(quantize_grouped(in)) -- what the tensor looks like after a
+ * group-wise round trip -- in ONE launch that reads `in` once and never writes the packed tensor.  dtype_in_out (float32 or bfloat16) is the type
+ * of both `in` and `out`; quant_dtype is the quantized type passed through (uint8, uint4 or uint2); group_size as above.  The call writes to out,
+ * scales and zero_points exactly the bytes that this composition of two public calls writes, tmp being a packed scratch tensor:
+ *   1. piquant_hip_quantize_grouped(in, dtype_in_out, tmp, quant_dtype, numel, group_size, scales, zero_points, params_given, mode);
+ *   2. piquant_hip_dequantize_grouped(tmp, quant_dtype, out, dtype_in_out, numel, group_size, scales, zero_points, op).
+ * Nearest and stochastic rounding as piquant_hip_quantize_grouped (ONE threshold per call, which piquant_hip_set_stochastic_threshold pins; the
+ * per-element mode indexes the global element).  params_given == 0: the group parameters are computed by piquant_hip_quantize_grouped's rules and
+ * written -- or scales and zero_points are BOTH NULL, and nothing is written for them (one NULL and one non-NULL aborts).  params_given != 0: both
+ * arrays are read and required.  The dequantized value is the pair's own dequantize form; SET stores it (bfloat16: rounded once), ADD is the grouped
+ * dequantize ADD (the float32 sum rounded separately, a bfloat16 result rounded once).  NaN payloads are not specified.
+ * `out` may be exactly `in` (in place), for SET and for ADD; any other overlap of the two is the caller's error.  `in` is never written unless it is
+ * `out`; nothing at or past the tensor's end is touched in any buffer.  Buffers that are not 16-byte aligned take a guarded element-by-element
+ * launch that writes the same bytes; a buffer that is not aligned to its element aborts.
+ * piquant_hip_quantize_dequantize_grouped_batch: tensor i has its own input, output, scales, zero_points and numels[i], with the rules of
+ * piquant_hip_quantize_grouped_batch (one threshold per batch, up to 16 tensors per launch and one launch per 16 beyond, empty tensors skipped, a
+ * misaligned tensor runs alone in its place in the sequence).  With params_given == 0 the lists scales and zero_points may both be NULL.
+ * Device (or pinned) buffers only; stream-ordered on the context's stream -- always behind the previous call when op is ADD or the parameters are
+ * given, otherwise as piquant_hip_quantize_grouped is -- no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op
+ * that draws no threshold. */
+PIQUANT_EXPORT void piquant_hip_quantize_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in_out, void* out,
+                                                            piquant_dtype_t quant_dtype, size_t numel, size_t group_size, float* scales,
+                                                            uint8_t* zero_points, int params_given, piquant_round_mode_t mode,
+                                                            piquant_reduce_op_t op);
+PIQUANT_EXPORT void piquant_hip_quantize_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in_out,
+                                                                  void* const* outputs, piquant_dtype_t quant_dtype, const size_t* numels,
+                                                                  size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                                  int params_given, piquant_round_mode_t mode, piquant_reduce_op_t op);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

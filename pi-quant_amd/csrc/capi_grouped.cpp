@@ -1,5 +1,5 @@
-// The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, and EF with a float32 residual
-// for a bfloat16 tensor.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
+// for a bfloat16 tensor, and quantize-dequantize.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -19,9 +19,9 @@ struct Where {
     panic("%s: %s (list index %ld)", w.entry, what, w.index);
 }
 
-void check_group_size(size_t group_size) {
+void check_group_size(size_t group_size, const char* entry = nullptr) {
     if (group_size < static_cast<size_t>(kGroupedMinG) || group_size > static_cast<size_t>(kGroupedMaxG) || (group_size & (group_size - 1)) != 0)
-        panic("group size %zu is not a power of two in [%d, %d]", group_size, kGroupedMinG, kGroupedMaxG);
+        panic("%s%sgroup size %zu is not a power of two in [%d, %d]", entry ? entry : "", entry ? ": " : "", group_size, kGroupedMinG, kGroupedMaxG);
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -32,13 +32,21 @@ void check_tensor(const Where& w, bool ef, const void* in, const void* residual,
     if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) bad(w, "scales must be 4-byte aligned");
 }
 
+// The quantize-dequantize calls' form of it: with computed parameters scales and zero_points may BOTH be NULL (no parameters wanted).
+void check_requant_tensor(const Where& w, bool params_given, const void* in, const void* out, const float* scales, const uint8_t* zero_points) {
+    if (!in || !out) bad(w, "NULL buffer");
+    if (!scales != !zero_points) bad(w, "one of scales / zero_points is NULL and the other is not");
+    if (!scales && params_given) bad(w, "given parameters need scales and zero_points");
+    if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) bad(w, "scales must be 4-byte aligned");
+}
+
 // A buffer as the kernels take it: pageable host memory has no group-wise path.
 void* device_ptr(const Where& w, const Resolved& r) {
     if (r.pageable) bad(w, "device (or pinned) buffers are needed");
     return r.dev;
 }
 
-// One tensor's buffers, resolved (caller holds ctx->mu); a NULL residual or out is left out.  The parameter arrays are always classified: the
+// One tensor's buffers, resolved (caller holds ctx->mu); a NULL residual or out, or a NULL parameter pair (check_requant_tensor), is left out.  The parameter arrays are always classified: the
 // context's assume-device mode speaks for the tensors the caller passes, not for them.
 GroupedTensor resolve_tensor(const piquant_context_t* ctx, const Where& w, const void* in, const void* residual, const void* out, const float* scales,
                              const uint8_t* zero_points, size_t numel) {
@@ -46,8 +54,8 @@ GroupedTensor resolve_tensor(const piquant_context_t* ctx, const Where& w, const
     t.in = device_ptr(w, ctx->resolve_ptr(in));
     if (residual) t.residual = device_ptr(w, ctx->resolve_ptr(residual));
     if (out) t.out = device_ptr(w, ctx->resolve_ptr(out));
-    t.scales = static_cast<float*>(device_ptr(w, resolve(scales)));
-    t.zero_points = static_cast<uint8_t*>(device_ptr(w, resolve(zero_points)));
+    if (scales) t.scales = static_cast<float*>(device_ptr(w, resolve(scales)));
+    if (zero_points) t.zero_points = static_cast<uint8_t*>(device_ptr(w, resolve(zero_points)));
     t.numel = static_cast<int64_t>(numel);
     return t;
 }
@@ -210,6 +218,45 @@ void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef,
     } else {           // quantize_grouped(acc)
         launch_quantize_grouped(GroupedQuantLaunch {t, call}, ctx->stream, ctx->num_cu);
     }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// Both quantize-dequantize entries behind their NULL-context check; `single`: the one tensor of piquant_hip_quantize_dequantize_grouped, whose messages
+// carry no list index.  ONE threshold (or per-element seed and base) for the whole batch, drawn whenever count > 0 -- also when every member is empty.
+void quantize_dequantize_grouped_batch(piquant_context_t* ctx, const char* entry, bool single, const void* const* inputs, piquant_dtype_t dtype_in_out,
+                                       void* const* outputs, piquant_dtype_t quant_dtype, const size_t* numels, size_t group_size, float* const* scales,
+                                       uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode, piquant_reduce_op_t op) {
+    if (dtype_of(dtype_in_out).quant) panic("%s: dtype_in_out (%s) must be a dequantized type", entry, dtype_of(dtype_in_out).name);
+    if (!dtype_of(quant_dtype).quant) panic("%s: quant_dtype (%s) must be a quantized type", entry, dtype_of(quant_dtype).name);
+    if (mode != PIQUANT_NEAREST && mode != PIQUANT_STOCHASTIC) panic("%s: invalid round mode %d", entry, static_cast<int>(mode));
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("%s: invalid reduce op %d", entry, static_cast<int>(op));
+    check_group_size(group_size, entry);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    const bool no_params = !scales && !zero_points;   // NULL lists: no parameters wanted
+    if (!inputs || !outputs || !numels || (!scales != !zero_points) || (no_params && params_given != 0)) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const bool add = op == PIQUANT_REDUCE_OP_ADD;
+    GroupedRequantBatchLaunch b {{{static_cast<int64_t>(group_size), dtype_in_out, quant_dtype, params_given != 0, round_mode_fields(ctx, mode)},
+                                  add ? OP_ADD : OP_SET}, {}, 0};
+    const size_t esize = dtype_in_out == PIQUANT_DTYPE_F32 ? 4 : 2;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, add || b.params_given);   // the accumulator and given parameters are written by what was enqueued before
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, single ? -1 : static_cast<long>(i)};
+            float* sc = no_params ? nullptr : scales[i];
+            uint8_t* zp = no_params ? nullptr : zero_points[i];
+            check_requant_tensor(w, b.params_given, inputs[i], outputs[i], sc, zp);
+            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], sc, zp, numels[i]);
+            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0 || reinterpret_cast<uintptr_t>(t.out) % esize != 0)
+                bad(w, "in or out is not aligned to its element size");
+            return t;
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_quantize_dequantize_grouped_guarded(GroupedRequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
+        [&] { launch_quantize_dequantize_grouped_batch(b, ctx->stream); });
     if (ctx->blocking) wait_stream(ctx);
 }
 
@@ -400,6 +447,27 @@ void piquant_hip_reduce_quantize_grouped_ef_mixed(piquant_context_t* ctx, void* 
     }
     reduce_quantize_grouped(ctx, entry, true, Residual::F32, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
                             group_size, scales, zero_points, mode);
+}
+
+void piquant_hip_quantize_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in_out, void* const* outputs,
+                                                   piquant_dtype_t quant_dtype, const size_t* numels, size_t group_size, float* const* scales,
+                                                   uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode,
+                                                   piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_quantize_dequantize_grouped_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    quantize_dequantize_grouped_batch(ctx, entry, false, inputs, dtype_in_out, outputs, quant_dtype, numels, group_size, scales, zero_points, count,
+                                      params_given, mode, op);
+}
+
+// The single call is a batch of one, which launches the single-tensor kernel; an empty tensor returns behind the argument checks and draws nothing.
+void piquant_hip_quantize_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in_out, void* out, piquant_dtype_t quant_dtype,
+                                             size_t numel, size_t group_size, float* scales, uint8_t* zero_points, int params_given,
+                                             piquant_round_mode_t mode, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_quantize_dequantize_grouped";
+    if (!ctx) panic("%s: context is NULL", entry);
+    const bool no_params = !scales && !zero_points;
+    quantize_dequantize_grouped_batch(ctx, entry, true, &in, dtype_in_out, &out, quant_dtype, &numel, group_size, no_params ? nullptr : &scales,
+                                      no_params ? nullptr : &zero_points, numel == 0 ? 0 : 1, params_given, mode, op);
 }
 
 }  // extern "C"

@@ -121,11 +121,14 @@ __device__ __forceinline__ void grouped_load(const void* in, int64_t numel, int6
 // p0 carries what is per call (threshold, seed, index base); its inv_scale / zero point are replaced per group.  The wave's LDS
 // slices (stage: OUT_BYTES bytes; s_a, s_b: NG floats each).  KEEP (the error-feedback kernels): the chunk stays readable after the call --
 // `stage` holds its packed bytes, s_a / s_b the groups' {1/scale, zero point} and s_scale (NG floats) their scales; nothing else changes.
-template <int DT_IN, int BITS, int MODE, int G, bool GIVEN, int NV_ = GroupedQuantTile<DT_IN, BITS, G>::NV, bool KEEP = false>
+// REQUANT (the fake-quantization kernels, with KEEP): the packed bytes stay in `stage` and never go to memory (`out` is not used), computed
+// parameters are written only when `scales` is not NULL, and given-or-computed is the wave-uniform runtime flag `given_rt` instead of GIVEN.
+// The default leaves every other instantiation as it was (their `given` below is a compile-time constant).
+template <int DT_IN, int BITS, int MODE, int G, bool GIVEN, int NV_ = GroupedQuantTile<DT_IN, BITS, G>::NV, bool KEEP = false, bool REQUANT = false>
 __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_t* __restrict__ out, int64_t numel,
                                                        float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
                                                        int64_t g0, bool full, int lane, uint8_t* stage, float* s_a, float* s_b,
-                                                       float* s_scale = nullptr) {
+                                                       float* s_scale = nullptr, bool given_rt = false) {
     using T = GroupedQuantTile<DT_IN, BITS, G>;
     constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR, NG = T::NG;
     constexpr int WORDS = OB > 4 ? 2 : 1, PACK = 8 / BITS;
@@ -133,11 +136,13 @@ __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_
 
     const int64_t gj = g0 + lane;                                   // lane j < NG: group j of the chunk
     bool bounded = true;
-    if constexpr (GIVEN) {
+    const bool given = REQUANT ? given_rt : GIVEN;
+    if (given) {
         if (lane < NG && gj < ngroups) {
             const float scale = scales[gj];
             s_a[lane] = __fdiv_rn(1.0f, scale);                     // as the host forms 1 / scale for quantize_uniform
             s_b[lane] = __int_as_float(static_cast<int32_t>(zero_points[gj]));
+            if constexpr (KEEP) s_scale[lane] = scale;
         }
         bounded = false;                                            // no data range known: the long step everywhere
     } else {
@@ -164,8 +169,10 @@ __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_
             int64_t zp;
             quant_params_epilogue(float_to_key(glo), float_to_key(-ghi), BITS, scale, zp);   // 0 <= zp <= 2^BITS - 1
             const float inv = __fdiv_rn(1.0f, scale);
-            st<ST_WT>(scales + gj, scale);
-            st<ST_WT>(zero_points + gj, static_cast<uint8_t>(zp));
+            if (!REQUANT || scales != nullptr) {
+                st<ST_WT>(scales + gj, scale);
+                st<ST_WT>(zero_points + gj, static_cast<uint8_t>(zp));
+            }
             // the short step needs |x / scale| far below 2^31 for every element: |x| <= max(|min|, |max|) (quant_kernels.hpp, BoundedStep)
             bounded = __fmul_rn(__builtin_fmaxf(__builtin_fabsf(glo), __builtin_fabsf(ghi)), inv) < 1.0e9f;
             s_a[lane] = inv;
@@ -210,6 +217,7 @@ __device__ __forceinline__ void grouped_quantize_chunk(u32x4 (&raw)[NV_], uint8_
         else *reinterpret_cast<u32x2*>(dst) = u32x2 {w[r][0], w[r][1]};
     }
     wave_lds_sync();
+    if constexpr (REQUANT) return;
     uint8_t* o = out + v0 * OB;
     if (full) {
         if constexpr (T::LANE_OUT_BYTES >= 16) {
@@ -716,39 +724,78 @@ __device__ __forceinline__ float residual_one(float y, float d) {
     return __fsub_rn(y, d);
 }
 
-// raw[r] <- y - dequantize(the chunk's packed bytes in `stage`), then the residual rows to memory (elements at or past numel are not written)
-template <int DT, int BITS, int G, int NV_ = GroupedQuantTile<DT, BITS, G>::NV>
-__device__ __forceinline__ void grouped_residual_store(u32x4 (&raw)[NV_], void* __restrict__ residual, int64_t numel, int64_t v0, bool full, int lane,
-                                                       const uint8_t* stage, const float* s_scale, const float* s_zp) {
+// ---- Reading a chunk back (grouped_quantize_chunk with KEEP): shared by the residual store below and the quantize-dequantize store
+// (kernels_grouped_requant.hip).
+
+// the dequantize parameters of the lane's SETS groups from what the chunk body parked: s_scale their scales, s_zp their zero points (as float bits)
+template <int DT, int BITS, int G, int SETS>
+__device__ __forceinline__ void grouped_parked_dequant_params(DequantParams (&p)[SETS], const float* s_scale, const float* s_zp, int lane) {
     using T = GroupedQuantTile<DT, BITS, G>;
-    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
-    constexpr int FORM = DequantForm<BITS, DT>::value;
-    DequantParams p[SETS];
+    static_assert(SETS == T::SETS, "one entry per group of the lane");
 #pragma unroll
     for (int s = 0; s < SETS; ++s) {
-        const int slot = s * GPR + lane / LPG;
+        const int slot = s * T::GPR + lane / T::LPG;
         p[s] = DequantParams {};
         p[s].scale = s_scale[slot];
         p[s].zp32 = __float_as_int(s_zp[slot]);
         p[s].zp64 = p[s].zp32;
         p[s].bias = __fmul_rn(-static_cast<float>(p[s].zp32), p[s].scale);   // as resolved(DequantParams) forms it
     }
+}
+
+// f = the lane's input vector of row r, dequantized from its packed words in `stage` in the pair's own form
+template <int DT, int BITS, int G>
+__device__ __forceinline__ void grouped_dequantize_row(const uint8_t* stage, int r, int lane, const DequantParams& p, float (&f)[InVec<DT>::EPV]) {
+    using T = GroupedQuantTile<DT, BITS, G>;
+    constexpr int EPV = T::EPV, OB = T::OB;
+    constexpr int FORM = DequantForm<BITS, DT>::value;
+    const uint8_t* src = stage + (r * 64 + lane) * OB;
+    uint32_t w[OB > 4 ? 2 : 1];
+    if constexpr (OB == 1) w[0] = *src;
+    else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
+    else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
+    else {
+        const u32x2 t = *reinterpret_cast<const u32x2*>(src);
+        w[0] = t[0];
+        w[1] = t[1];
+    }
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p);
+}
+
+// vector `vec` of a tensor of type DT and numel elements <- o: one 16-byte write-through store, or element by element where the tensor ends inside
+// the vector (nothing at or past numel is written).  grouped_residual_store keeps this step written out in its loop: called through here, the
+// partial-chunk tail of the bfloat16 error-feedback kernels compiled to differently arranged branches, and those kernels stay instruction for
+// instruction what they were.
+template <int DT>
+__device__ __forceinline__ void grouped_store_vector(void* __restrict__ dst, int64_t numel, int64_t vec, bool full, const u32x4& o) {
+    constexpr int EPV = InVec<DT>::EPV;
+    if (full || (vec + 1) * EPV <= numel) {
+        st<ST_WT>(static_cast<u32x4*>(dst) + vec, o);
+    } else {   // the tensor ends inside this vector, or in front of it
+#pragma unroll
+        for (int e = 0; e < EPV; ++e) {
+            const int64_t i = vec * EPV + e;
+            if (i >= numel) continue;
+            if constexpr (DT == DT_F32) static_cast<uint32_t*>(dst)[i] = o[e];
+            else static_cast<uint16_t*>(dst)[i] = static_cast<uint16_t>(o[e >> 1] >> ((e & 1) * 16));
+        }
+    }
+}
+
+// raw[r] <- y - dequantize(the chunk's packed bytes in `stage`), then the residual rows to memory (elements at or past numel are not written)
+template <int DT, int BITS, int G, int NV_ = GroupedQuantTile<DT, BITS, G>::NV>
+__device__ __forceinline__ void grouped_residual_store(u32x4 (&raw)[NV_], void* __restrict__ residual, int64_t numel, int64_t v0, bool full, int lane,
+                                                       const uint8_t* stage, const float* s_scale, const float* s_zp) {
+    using T = GroupedQuantTile<DT, BITS, G>;
+    constexpr int EPV = T::EPV, NV = T::NV, RPG = T::RPG, SETS = T::SETS;
+    DequantParams p[SETS];
+    grouped_parked_dequant_params<DT, BITS, G>(p, s_scale, s_zp, lane);
     u32x4* r16 = static_cast<u32x4*>(residual);
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
-        const uint8_t* src = stage + (r * 64 + lane) * OB;
-        uint32_t w[OB > 4 ? 2 : 1];
-        if constexpr (OB == 1) w[0] = *src;
-        else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
-        else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
-        else {
-            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
-            w[0] = t[0];
-            w[1] = t[1];
-        }
         float f[EPV];
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p[r / RPG]);
+        grouped_dequantize_row<DT, BITS, G>(stage, r, lane, p[r / RPG], f);
         u32x4 o;
         if constexpr (DT == DT_F32) {
 #pragma unroll

@@ -156,6 +156,16 @@ struct GroupedReduceLaunch : GroupedTensor, GroupedQuantCall {
 using GroupedEfBatchLaunch = GroupedQuantBatchLaunch;   // every t[i].residual set; params_given unused
 using GroupedEfLaunch = GroupedQuantLaunch;
 
+// Quantize-dequantize (kernels_grouped_requant.hip): per tensor out (op)= dequantize_grouped(quantize_grouped(in)) in ONE launch that never writes
+// the packed tensor.  in and out have type dt_in and may be the same buffer; dt_out is the quantized type passed through.  scales / zero_points are
+// read with params_given, written otherwise -- or both NULL then: no parameters wanted.  The batch takes tensors whose in and out are 16-byte
+// aligned (a batch of one launches the single-tensor kernel); the guarded launch runs one tensor of any element alignment, the same bytes.
+struct GroupedRequantCall : GroupedQuantCall {
+    int op;                // OP_SET / OP_ADD
+};
+struct GroupedRequantLaunch : GroupedTensor, GroupedRequantCall {};
+using GroupedRequantBatchLaunch = GroupedBatch<GroupedRequantCall>;
+
 // All launches are asynchronous on `stream`; num_cu sizes capped grids.
 void launch_quantize(const QuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize(const DequantLaunch& d, hipStream_t stream, int num_cu);
@@ -175,6 +185,8 @@ void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfLaunch& q, hipStream
 // The fused reduce with error feedback for that pair (kernels_grouped_reduce_ef_f32r.hip): r.dt_in == DT_BF16, r.residual float32.  Terms, residual
 // and out 16-byte aligned, the accumulator 8-byte aligned (its lane-row is four elements), at most kGroupedReduceMaxInputs terms.
 void launch_reduce_quantize_grouped_ef_f32r(const GroupedReduceLaunch& r, hipStream_t stream);
+void launch_quantize_dequantize_grouped_batch(const GroupedRequantBatchLaunch& b, hipStream_t stream);
+void launch_quantize_dequantize_grouped_guarded(const GroupedRequantLaunch& q, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -462,6 +462,37 @@ class Context:
                                                (_C.c_size_t * n)(*numels), group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
                                                reduce_op.value)
 
+    def quantize_dequantize_grouped_ptr(self, ptr_in: int, dtype_in_out: DataType, ptr_out: int, quant_dtype: DataType, numel: int, group_size: int,
+                                        scales_ptr: int, zero_points_ptr: int, params_given: bool, round_mode: RoundMode, reduce_op: ReduceOp,
+                                        _device_ptrs: bool = False) -> None:
+        """Group-wise quantize-dequantize (``piquant_hip_quantize_dequantize_grouped``): out (op)= dequantize_grouped(quantize_grouped(in)) in one
+        launch that never writes the packed tensor.  ``ptr_out`` may equal ``ptr_in``.  The parameter arrays are written from the data, or read when
+        ``params_given``; with computed parameters both pointers may be 0 (no parameters wanted)."""
+        assert dtype_in_out.is_dequantized and quant_dtype.is_quantized and (not params_given or (scales_ptr and zero_points_ptr))
+        assert bool(scales_ptr) == bool(zero_points_ptr)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_dequantize_grouped(self._ctx, ptr_in, dtype_in_out.value, ptr_out, quant_dtype.value, numel, group_size, scales_ptr or None,
+                                                  zero_points_ptr or None, 1 if params_given else 0, round_mode.value, reduce_op.value)
+
+    def quantize_dequantize_grouped_batch_ptr(self, ptrs_in, dtype_in_out: DataType, ptrs_out, quant_dtype: DataType, numels, group_size: int, scales_ptrs,
+                                              zero_points_ptrs, params_given: bool, round_mode: RoundMode, reduce_op: ReduceOp,
+                                              _device_ptrs: bool = False) -> None:
+        """``quantize_dequantize_grouped_ptr`` for several independent tensors, up to 16 per kernel launch
+        (``piquant_hip_quantize_dequantize_grouped_batch``); one stochastic threshold for the batch.  ``scales_ptrs`` and ``zero_points_ptrs`` may
+        both be None with computed parameters (no parameters wanted)."""
+        n = len(ptrs_in)
+        assert dtype_in_out.is_dequantized and quant_dtype.is_quantized and n == len(ptrs_out) == len(numels)
+        assert (scales_ptrs is None) == (zero_points_ptrs is None) and not (params_given and scales_ptrs is None)
+        assert scales_ptrs is None or n == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        sc = None if scales_ptrs is None else (_C.c_void_p * n)(*scales_ptrs)
+        zp = None if zero_points_ptrs is None else (_C.c_void_p * n)(*zero_points_ptrs)
+        C.piquant_hip_quantize_dequantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in_out.value, (_C.c_void_p * n)(*ptrs_out),
+                                                        quant_dtype.value, (_C.c_size_t * n)(*numels), group_size, sc, zp, n, 1 if params_given else 0,
+                                                        round_mode.value, reduce_op.value)
+
     def reduce_quantize_grouped_ptr(self, ptr_acc: int, dtype_acc: DataType, ptrs_in, scales_in, zero_points_in, ptr_out: int, dtype_out: DataType,
                                     numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                     _device_ptrs: bool = False) -> None:

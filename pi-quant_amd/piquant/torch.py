@@ -565,6 +565,94 @@ def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128
     return outs, scales, zero_points
 
 
+def _requant_grouped_checks(dtype_ok: bool, quant_dtype, group_size, round_mode, reduce_op, scales, zero_points) -> None:
+    _require(quant_dtype in _QUANT_TYPES, f'{quant_dtype} is not a quantized dtype')
+    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
+    _check_group_size(group_size)
+    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
+    _require(dtype_ok, 'tensor must be a float32 or bfloat16 tensor')
+
+
+def quantize_dequantize_grouped(tensor: torch.Tensor, *, quant_dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
+                                reduce_op: str = 'set', scales: Optional[torch.Tensor] = None, zero_points: Optional[torch.Tensor] = None,
+                                return_params: bool = False, ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None):
+    """Group-wise fake quantization: ``out (op)= dequantize_grouped(quantize_grouped(tensor))`` -- what the tensor looks like after a group-wise
+    round trip through ``quant_dtype`` -- bit for bit those two calls, in one launch that reads the tensor once and never writes the packed
+    bytes.  Returns ``out`` (the input's shape and dtype), or ``(out, scales, zero_points)`` with ``return_params=True``.  ``scales`` and
+    ``zero_points`` given together mean "quantize with these per-group parameters"; otherwise they are computed (and only materialised when
+    ``return_params``).  ``reduce_op='add'`` accumulates into ``out=``; ``out=tensor`` is in place, for both ops (``include/piquant_hip.h``,
+    piquant_hip_quantize_dequantize_grouped)."""
+    _requant_grouped_checks(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, quant_dtype, group_size, round_mode, reduce_op, scales,
+                            zero_points)
+    ngroups = num_groups(tensor.numel(), group_size)
+    given = scales is not None
+    if given:
+        _check_group_params(scales, zero_points, ngroups)
+    if out is None:
+        _require(reduce_op != 'add', "reduce_op='add' accumulates into out=; pass the accumulator tensor")
+    else:
+        _check_float_out(out, tensor.dtype, tensor.numel(), tensor.device)
+    _check_float_input(tensor)
+    if given:
+        _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
+    elif return_params:
+        scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
+        zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    if out is None:
+        out = torch.empty_like(tensor)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_dequantize_grouped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(quant_dtype),
+                                        tensor.numel(), group_size, 0 if scales is None else scales.data_ptr(),
+                                        0 if zero_points is None else zero_points.data_ptr(), given, _ROUND_MODES[round_mode], _REDUCE_OPS[reduce_op],
+                                        _device_ptrs=True)
+    return (out, scales, zero_points) if return_params else out
+
+
+def quantize_dequantize_grouped_batch(tensors, *, quant_dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', reduce_op: str = 'set',
+                                      scales=None, zero_points=None, return_params: bool = False, ctx: Optional[Context] = None, outs=None):
+    """``quantize_dequantize_grouped`` of several independent tensors (one dtype, quantized dtype, group size, round mode and op) with one kernel
+    launch per 16 tensors.  Returns ``outs``, or ``(outs, scales, zero_points)`` (lists) with ``return_params=True``; tensor i's entries equal the
+    single call on it (a stochastic batch draws one threshold).  ``scales`` and ``zero_points`` (lists) given together quantize with those
+    parameters; ``reduce_op='add'`` needs ``outs=``; ``outs[i]`` may be ``tensors[i]``."""
+    tensors = list(tensors)
+    _requant_grouped_checks(all(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES for t in tensors), quant_dtype, group_size, round_mode, reduce_op,
+                            scales, zero_points)
+    given = scales is not None
+    _require(outs is not None or reduce_op != 'add', "reduce_op='add' accumulates into outs=; pass the accumulator tensors")
+    lists = [tensors] + ([list(outs)] if outs is not None else []) + ([list(scales), list(zero_points)] if given else [])
+    _check_batch_lists(*lists)
+    _require(all(t.device == tensors[0].device and t.dtype == tensors[0].dtype for t in tensors), 'the tensors of a batch must share one device and one dtype')
+    device = tensors[0].device
+    if given:
+        scales, zero_points = list(scales), list(zero_points)
+        for sc, zp, t in zip(scales, zero_points, tensors):
+            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
+    if outs is not None:
+        outs = list(outs)
+        for i, (o, t) in enumerate(zip(outs, tensors)):
+            _check_float_out(o, t.dtype, t.numel(), device, f'outs[{i}]')
+    for i, t in enumerate(tensors):
+        _check_float_input(t, f'tensors[{i}]')
+    if given:
+        _require(all(sc.device == device and zp.device == device for sc, zp in zip(scales, zero_points)), f'scales and zero_points must live on {device}')
+    elif return_params:
+        scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
+        zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
+    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    if outs is None:
+        outs = [torch.empty_like(t) for t in tensors]
+    ctx = _ctx_for(tensors[0], ctx)
+    ctx.quantize_dequantize_grouped_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [o.data_ptr() for o in outs],
+                                              torch_to_piquant_dtype(quant_dtype), [t.numel() for t in tensors], group_size,
+                                              None if scales is None else [sc.data_ptr() for sc in scales],
+                                              None if zero_points is None else [zp.data_ptr() for zp in zero_points], given, _ROUND_MODES[round_mode],
+                                              _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return (outs, scales, zero_points) if return_params else outs
+
+
 def _check_residual(residual, tensor: torch.Tensor, what: str = 'residual') -> None:
     """The residual of an error-feedback call is written by raw pointer: a contiguous device tensor of the input's device and numel, and of the
     input's dtype -- or float32 for a bfloat16 input (the float32 residual, ``piquant_hip_quantize_grouped_ef_mixed``); no other pair."""

@@ -30,7 +30,12 @@ with k = 1 and k = 7, uint2 with k = 1) next to the composition that defines it 
 mixed quantize_grouped_ef) in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
 profiles/grouped_reduce_ef_f32r_bench.json; --rows all appends these rows to its table.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows requant: the group-wise quantize-dequantize (quantize_dequantize_grouped, G = 128: fp32 via uint8 and uint4, bf16 via uint8, uint4 and uint2
+with SET, fp32 via uint8 with ADD) next to the two calls that define it (quantize_grouped into a packed scratch tensor + dequantize_grouped) in the
+same run, with the byte ratio of each row (parameter bytes counted on both sides) and the target fused / composition <= 1.15 x that ratio.  Writes
+profiles/grouped_requant_bench.json; --rows all appends these rows to its table.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -499,17 +504,68 @@ def reduce_ef_f32r_rows(ctx, dev, stream, args, G=128):
     return rows
 
 
+def requant_rows(ctx, dev, stream, args, G=128):
+    """quantize_dequantize_grouped against quantize_grouped + dequantize_grouped, the two calls that define it"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(7)
+    for fname, qname, op in (("f32", "uint8", "set"), ("f32", "uint4", "set"), ("bf16", "uint8", "set"), ("bf16", "uint4", "set"), ("bf16", "uint2", "set"),
+                             ("f32", "uint8", "add")):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        rop = piquant.ReduceOp.ADD if op == "add" else piquant.ReduceOp.SET
+        nq = qdt.packed_nbytes(NUMEL)
+        fbytes = NUMEL * esize
+        out_bytes = fbytes * (2 if op == "add" else 1)                          # ADD reads the accumulator too
+        fused_bytes = fbytes + out_bytes + 5 * ng                               # x in; out; the parameters out
+        comp_bytes = fbytes + 2 * nq + out_bytes + 10 * ng                      # the packed tensor out and in again, the parameters too
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        xs = [torch.empty(NUMEL, dtype=tdt, device=dev).normal_(generator=g) for _ in range(nbuf)]
+        ys = [torch.zeros(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        tmp = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.quantize_dequantize_grouped_ptr(xs[i].data_ptr(), fdt, ys[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                                piquant.RoundMode.NEAREST, rop, _device_ptrs=True)
+
+        def composition(i):
+            ctx.quantize_grouped_ptr(xs[i].data_ptr(), fdt, tmp[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                     piquant.RoundMode.NEAREST, _device_ptrs=True)
+            ctx.dequantize_grouped_ptr(tmp[i].data_ptr(), qdt, ys[i].data_ptr(), fdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), rop, _device_ptrs=True)
+
+        pair = f"{fname} via {qname} {op.upper()}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("requant_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("quantize_dequantize_grouped", pair, G, us_f, fused_bytes, s_f)
+        fr["over_composition"] = round(us_f / us_c, 3)
+        fr["bytes_over_composition"] = round(fused_bytes / comp_bytes, 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["faster_than_composition"] = bool(us_f < us_c)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}", flush=True)
+        rows += [cr, fr]
+        del xs, ys, tmp, sc, zs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
-                                                   "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json"}[args.rows])
+                                                   "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -529,6 +585,8 @@ def main():
         rows = ef_f32r_rows(ctx, dev, stream, args)
     if args.rows == "reduce_ef_f32r":
         rows = reduce_ef_f32r_rows(ctx, dev, stream, args)
+    if args.rows == "requant":
+        rows = requant_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
@@ -572,6 +630,7 @@ def main():
         torch.cuda.empty_cache()
     if args.rows == "all":
         rows += reduce_ef_f32r_rows(ctx, dev, stream, args)
+        rows += requant_rows(ctx, dev, stream, args)
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
