@@ -1,6 +1,6 @@
 // Host code shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip,
 // kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip, kernels_grouped_reduce_ef_f32r.hip, kernels_grouped_requant*.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
-// QuantParams, the chunk table and grids, and the launch bodies of the two error-feedback kernel families.
+// QuantParams, the chunk table and grids, and the launch bodies of the error-feedback kernel families and of the fused reduce kernels.
 #pragma once
 
 #include "launch.hpp"
@@ -154,6 +154,48 @@ void launch_grouped_ef_guarded(const GroupedEfLaunch& q, hipStream_t stream, int
                 constexpr int MODE = decltype(mi)::value;
                 PQ_LAUNCH((Family::template guarded<DT, BITS, MODE>()), grid, dim3(kGroupedBlock), 0, stream, q.in, q.residual, static_cast<uint8_t*>(q.out),
                           q.numel, q.group_size, q.scales, q.zero_points, ngroups, p.threshold, p.seed_lo, p.seed_hi, p.index_base);
+            });
+        });
+    });
+    PQ_HIP(hipGetLastError());
+}
+
+// Launch body of a fused reduce + quantize kernel; each of the three units instantiates it once (kernels_grouped.hip: the plain reduce;
+// kernels_grouped_reduce_ef.hip: with error feedback; kernels_grouped_reduce_ef_f32r.hip: a bfloat16 accumulator with a float32 residual).
+// Family::name names it in messages; Family::with_pipeline_type(dt_in, f) checks the accumulator's type and calls f(std::integral_constant<int, DT>)
+// for the type DT that picks the tile and the rounding modes; Family::kernel<DT, BITS, MODE, G>() returns the kernel, which takes the residual
+// behind the accumulator when Family::residual is set.
+template <class Family>
+void launch_grouped_reduce(const GroupedReduceLaunch& r, hipStream_t stream) {
+    static_assert(kGroupedReduceMaxInputs == kGroupedReduceMaxTerms, "host and device term limits");
+    if (r.numel <= 0) return;
+    if (r.count < 0 || r.count > kGroupedReduceMaxTerms) panic("%s: %d terms, at most %d per launch", Family::name, r.count, kGroupedReduceMaxTerms);
+    const QuantParams p = grouped_call_params(r.rm);
+    GroupedTerms terms {};
+    for (int i = 0; i < r.count; ++i) {
+        terms.in[i] = static_cast<const uint8_t*>(r.term[i].in);
+        terms.scales[i] = r.term[i].scales;
+        terms.zero_points[i] = r.term[i].zero_points;
+    }
+    terms.count = r.count;
+    const int64_t ngroups = (r.numel + r.group_size - 1) / r.group_size;
+    Family::with_pipeline_type(r.dt_in, [&](auto di) {
+        constexpr int DT = decltype(di)::value;
+        with_quant_bits(r.dt_out, [&](auto bi) {
+            constexpr int BITS = decltype(bi)::value;
+            with_round_mode<DT, BITS>(r.rm.round_mode, [&](auto mi) {
+                constexpr int MODE = decltype(mi)::value;
+                with_group_size(r.group_size, Family::name, [&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    constexpr int NG = GroupedQuantTile<DT, BITS, G>::NG;
+                    const dim3 grid(grouped_blocks((ngroups + NG - 1) / NG, Family::name));
+                    if constexpr (Family::residual)
+                        PQ_LAUNCH((Family::template kernel<DT, BITS, MODE, G>()), grid, dim3(kGroupedBlock), 0, stream, r.in, r.residual,
+                                  static_cast<uint8_t*>(r.out), r.numel, r.scales, r.zero_points, ngroups, p, terms);
+                    else
+                        PQ_LAUNCH((Family::template kernel<DT, BITS, MODE, G>()), grid, dim3(kGroupedBlock), 0, stream, r.in, static_cast<uint8_t*>(r.out),
+                                  r.numel, r.scales, r.zero_points, ngroups, p, terms);
+                });
             });
         });
     });

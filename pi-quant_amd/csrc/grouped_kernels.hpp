@@ -26,12 +26,28 @@
 // Dequantize: a wave owns NIN KiB of packed input (16 bytes per lane and row), staged through LDS and read back as the packed bytes of one
 // 16-byte output vector per lane and step, so that loads and stores are both coalesced 16-byte accesses; the group parameters of the chunk are
 // loaded once into LDS and every output vector picks its group's.
+//
+// The helpers the kernels are made of, each rule stated on the one that owns it:
+//   grouped_batch_tensor          a wave's tensor in a batch's prefix table (all five batch kernels, grouped_requant_kernels.hpp's included)
+//   staged_words                  the packed bytes of one vector out of the wave's LDS slice, as dwords
+//   grouped_dequantize_row        staged_words + dequant_one over a lane-row: the read-back of a staged term and of the chunk's own output
+//   grouped_load / _bf16x4        a chunk's rows from memory, quiet NaNs behind the tensor's end; grouped_widen_bf16x4 widens the packed rows
+//   grouped_quantize_chunk        parameters, quantization and staged stores of one chunk (KEEP / REQUANT: the chunk stays readable)
+//   GroupedTermLoad, grouped_park_term / grouped_park_term_partial, grouped_term_dequant_params, grouped_add_term
+//                                 a term of the fused reduce kernels: loaded a term ahead, staged (full chunk / partial chunk), gathered, added
+//   grouped_guarded_params        the group prologue of the four guarded quantizing kernels
+//   grouped_add_residual, residual_one, grouped_parked_dequant_params, grouped_store_vector, grouped_residual_store
+//                                 the error-feedback steps around the chunk body; grouped_ef_chunk is the whole tile for both residual types
+// A kernel's code depends on how these are cut, not only on what they say: the notes "by reference", "G is not used" and "written out" on some of
+// them record forms that were tried and compiled to other code (profiles/EXPERIMENTS.md, "Shared helpers for the grouped kernels").
 #pragma once
 
 #include "dequant_kernels.hpp"
 #include "fused_kernels.hpp"
 #include "minmax_kernels.hpp"
 #include "quant_kernels.hpp"
+
+#include <type_traits>
 
 namespace pq {
 
@@ -65,6 +81,45 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Batches: the chunks of tensor t are [chunk_begin[t], chunk_begin[t + 1]) of the grid's waves.  The tensor of wave c of the grid from that prefix
+// table (wave-uniform, <= 15 compares); false for a wave behind the batch's last chunk.  The wave's chunk inside its tensor is c - a.chunk_begin[t].
+// Args is the kernel's argument table, by reference: handed the table and the count as values, or left to return t, the search loop compiled to a
+// different scalar prologue in every batch kernel (profiles/EXPERIMENTS.md).
+template <class Args>
+__device__ __forceinline__ bool grouped_batch_tensor(const Args& a, int64_t c, int& t) {
+    if (c >= a.chunk_begin[a.count]) return false;
+    t = 0;
+    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    return true;
+}
+
+// The NB = 1, 2, 4 or 8 packed bytes at `src` (NB-aligned, in the wave's LDS slice) as dwords: one LDS read of exactly that width.
+template <int NB>
+__device__ __forceinline__ void staged_words(const uint8_t* src, uint32_t (&w)[NB > 4 ? 2 : 1]) {
+    static_assert(NB == 1 || NB == 2 || NB == 4 || NB == 8, "the packed bytes of one 16-byte vector");
+    if constexpr (NB == 1) w[0] = *src;
+    else if constexpr (NB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
+    else if constexpr (NB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
+    else {
+        const u32x2 t = *reinterpret_cast<const u32x2*>(src);
+        w[0] = t[0];
+        w[1] = t[1];
+    }
+}
+
+// f = the lane's vector of row r of a chunk of the tile of type DT (InVec<DT>::EPV elements, OB = EPV * BITS / 8 packed bytes at vector r * 64 + lane
+// of `stage`), dequantized with p in FORM -- the tile's own pair unless the accumulator has another type.  The one read-back of the wave's LDS
+// slice: a term's staged chunk (grouped_add_term) and the chunk's own packed output (grouped_residual_store, grouped_requant_store).  G is not used:
+// it keeps one instance per tile, as there was -- with one shared by all group sizes a quantize-dequantize kernel came out scheduled differently.
+template <int DT, int BITS, int G, int FORM = DequantForm<BITS, DT>::value>
+__device__ __forceinline__ void grouped_dequantize_row(const uint8_t* stage, int r, int lane, const DequantParams& p, float (&f)[InVec<DT>::EPV]) {
+    constexpr int EPV = InVec<DT>::EPV, OB = EPV * BITS / 8;
+    uint32_t w[OB > 4 ? 2 : 1];
+    staged_words<OB>(stage + (r * 64 + lane) * OB, w);
+#pragma unroll
+    for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p);
 }
 
 template <int DT_IN, int BITS, int G>
@@ -114,6 +169,48 @@ __device__ __forceinline__ void grouped_load(const void* in, int64_t numel, int6
             }
         }
     }
+}
+
+// The rows of a tensor of type DT on the tile of type DT_TILE.  DT == DT_TILE: the tile's own 16-byte vectors (grouped_load).  A bfloat16 tensor on
+// the float32 tile (error feedback with a float32 residual): a lane-row is four elements, which are 8 bytes of the tensor (one global_load_dwordx2,
+// 512 contiguous bytes per wave-row), kept PACKED (u32x2: two bfloat16 a dword) until grouped_widen_bf16x4.
+template <int DT, int DT_TILE>
+using GroupedRow = std::conditional_t<DT == DT_TILE, u32x4, u32x2>;
+
+// one wave's chunk of the bfloat16 tensor `in` as NV rows of four elements, still packed (8 bytes a lane-row); elements at or past numel read as
+// quiet NaNs.  Load only: nothing here uses what it loads, so that the residual's loads can be issued behind these without a wait between them.
+template <int NV>
+__device__ __forceinline__ void grouped_load_bf16x4(const void* in, int64_t numel, int64_t v0, int lane, bool full, u32x2 (&t)[NV]) {
+    const u32x2* in8 = static_cast<const u32x2*>(in);
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < NV; ++r) t[r] = ld<true>(in8 + v0 + r * 64 + lane);
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const int64_t vec = v0 + r * 64 + lane;
+        if ((vec + 1) * 4 <= numel) {
+            t[r] = ld<true>(in8 + vec);
+        } else {
+            t[r] = u32x2 {0x7fc07fc0u, 0x7fc07fc0u};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {   // unrolled: constant register indices
+                const int64_t i = vec * 4 + e;
+                if (i >= numel) continue;
+                t[r][e >> 1] = (t[r][e >> 1] & ((e & 1) ? 0x0000ffffu : 0xffff0000u)) |
+                               (static_cast<uint32_t>(static_cast<const uint16_t*>(in)[i]) << ((e & 1) * 16));
+            }
+        }
+    }
+}
+
+// the packed rows widened to float32 bits: raw[r][e] = bits << 16.  Loading and widening are two steps on purpose: a load that widened in place
+// would put a use between the tensor's loads and the residual's.
+template <int NV>
+__device__ __forceinline__ void grouped_widen_bf16x4(const u32x2 (&t)[NV], u32x4 (&raw)[NV]) {
+#pragma unroll
+    for (int r = 0; r < NV; ++r) raw[r] = u32x4 {t[r][0] << 16, t[r][0] & 0xffff0000u, t[r][1] << 16, t[r][1] & 0xffff0000u};
 }
 
 // Quantize of one chunk whose NV rows are in `raw` (grouped_load: elements at or past numel are quiet NaNs): parameters, quantization, staged
@@ -256,8 +353,9 @@ quantize_grouped_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, 
     grouped_quantize_chunk<DT_IN, BITS, MODE, G, GIVEN>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, s_out[wave], s_a[wave], s_b[wave]);
 }
 
-// Batch: up to kGroupedBatchMax independent tensors in ONE launch.  The chunks of tensor t are [chunk_begin[t], chunk_begin[t + 1]) of the grid's
-// waves; a wave finds its tensor from the prefix table (wave-uniform, <= 15 compares) and then runs exactly the single-tensor kernel's body.
+// Batch: up to kGroupedBatchMax independent tensors in ONE launch.  A wave finds its tensor and its chunk (grouped_batch_tensor) and then runs exactly
+// the single-tensor kernel's body.  The four argument tables (this one, GroupedDequantBatchArgs, GroupedEfBatchArgs, GroupedRequantBatchArgs) stay
+// four plain structs: their member types differ, and one template or a shared base would change the kernels' mangled names or the kernarg layout.
 constexpr int kGroupedBatchMax = 16;
 struct GroupedQuantBatchArgs {
     const void* in[kGroupedBatchMax];
@@ -280,9 +378,8 @@ quantize_grouped_batch_kernel(GroupedQuantBatchArgs a, QuantParams p0) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    if (c >= a.chunk_begin[a.count]) return;
-    int t = 0;
-    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
     const int64_t numel = a.numel[t];
     const int64_t ngroups = (numel + G - 1) / G;
     const int64_t g0 = (c - a.chunk_begin[t]) * NG;
@@ -352,46 +449,74 @@ struct GroupedTermLoad {
     }
 };
 
-// raw[r] (op)= the dequantized packed bytes of input vector r of the lane (ADD: rounded to DT_ACC after the add), group parameters per set
-template <int DT_ACC, int BITS, int G, int NV_ = GroupedQuantTile<DT_ACC, BITS, G>::NV>
-__device__ __forceinline__ void grouped_add_term(u32x4 (&raw)[NV_], const uint8_t* stage, const float* s_scale,
-                                                 const float* s_bias, const int32_t* s_zp, int lane) {
-    using T = GroupedQuantTile<DT_ACC, BITS, G>;
-    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
-    constexpr int FORM = DequantForm<BITS, DT_ACC>::value;
-    DequantParams p[SETS];
+// Staging a term: its chunk's packed bytes into `stage` and, from lane j < NG, group j's {scale, bias, zero point} into the wave's LDS slices, where
+// grouped_add_term finds them.  A full chunk comes out of the registers of a GroupedTermLoad (loaded a term ahead) ...
+template <class L>
+__device__ __forceinline__ void grouped_park_term(const L& t, uint8_t* stage, float* s_scale, float* s_bias, int32_t* s_zp, bool has_group, int lane) {
+    t.park(stage, lane);
+    if (has_group) {
+        s_scale[lane] = t.scale;
+        s_bias[lane] = __fmul_rn(-static_cast<float>(t.zp), t.scale);   // as resolved(DequantParams) forms it
+        s_zp[lane] = t.zp;
+    }
+}
+
+// ... and a chunk the tensor ends in (at vector v0 of term i, `left` bytes before the tensor's last packed byte) straight from memory: byte loads
+// up to that byte, zeros behind it -- they meet the quiet NaNs of the accumulator's missing elements, which stay NaN.  T: the tile.  The terms
+// come as the kernel's argument by reference: handed the term's three pointers as values, the scalar loads of the two parameter pointers moved in
+// front of the byte loop in every reduce kernel.
+template <class T, class Terms>
+__device__ __forceinline__ void grouped_park_term_partial(const Terms& terms, int i, int64_t v0, int64_t left, int64_t gj, uint8_t* stage, float* s_scale,
+                                                          float* s_bias, int32_t* s_zp, bool has_group, int lane) {
+    const uint8_t* c = terms.in[i] + v0 * T::OB;
+    for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
+    if (has_group) {
+        const float scale = terms.scales[i][gj];
+        const int32_t zp = terms.zero_points[i][gj];
+        s_scale[lane] = scale;
+        s_bias[lane] = __fmul_rn(-static_cast<float>(zp), scale);
+        s_zp[lane] = zp;
+    }
+}
+
+// the dequantize parameters of the lane's SETS groups (tile T) from a parked term's {scale, bias, zero point} (grouped_park_term)
+template <class T>
+__device__ __forceinline__ void grouped_term_dequant_params(DequantParams (&p)[T::SETS], const float* s_scale, const float* s_bias, const int32_t* s_zp,
+                                                            int lane) {
 #pragma unroll
-    for (int s = 0; s < SETS; ++s) {
-        const int slot = s * GPR + lane / LPG;
+    for (int s = 0; s < T::SETS; ++s) {
+        const int slot = s * T::GPR + lane / T::LPG;
         p[s] = DequantParams {};
         p[s].scale = s_scale[slot];
         p[s].bias = s_bias[slot];
         p[s].zp32 = s_zp[slot];
         p[s].zp64 = p[s].zp32;
     }
+}
+
+// x[r] = rn(x[r] + the dequantized packed bytes of vector r of the lane) in the accumulator's type DT_ACC, group parameters per set: the arithmetic
+// of a grouped dequantize ADD, in the pair's form uint -> DT_ACC, on the geometry of the tile of type DT_TILE.  A bfloat16 accumulator, on its own
+// tile (eight elements a row) or packed on the float32 tile (four), adds in float32 and rounds each pair of sums back with the pairwise conversion.
+template <int DT_ACC, int DT_TILE, int BITS, int G, int NV_ = GroupedQuantTile<DT_TILE, BITS, G>::NV>
+__device__ __forceinline__ void grouped_add_term(GroupedRow<DT_ACC, DT_TILE> (&x)[NV_], const uint8_t* stage, const float* s_scale, const float* s_bias,
+                                                 const int32_t* s_zp, int lane) {
+    using T = GroupedQuantTile<DT_TILE, BITS, G>;
+    constexpr int EPV = T::EPV, NV = T::NV, RPG = T::RPG, SETS = T::SETS;
+    static_assert(DT_ACC == DT_TILE || (DT_ACC == DT_BF16 && DT_TILE == DT_F32), "the accumulator on its own tile, or bfloat16 packed on the float32 tile");
+    DequantParams p[SETS];
+    grouped_term_dequant_params<T>(p, s_scale, s_bias, s_zp, lane);
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
-        const uint8_t* src = stage + (r * 64 + lane) * OB;
-        uint32_t w[OB > 4 ? 2 : 1];
-        if constexpr (OB == 1) w[0] = *src;
-        else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
-        else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
-        else {
-            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
-            w[0] = t[0];
-            w[1] = t[1];
-        }
         float f[EPV];
-#pragma unroll
-        for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p[r / RPG]);
+        grouped_dequantize_row<DT_TILE, BITS, G, DequantForm<BITS, DT_ACC>::value>(stage, r, lane, p[r / RPG], f);
         if constexpr (DT_ACC == DT_F32) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) raw[r][e] = __float_as_uint(__fadd_rn(f[e], __uint_as_float(raw[r][e])));
+            for (int e = 0; e < 4; ++e) x[r][e] = __float_as_uint(__fadd_rn(f[e], __uint_as_float(x[r][e])));
         } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                raw[r][e] = f32x2_to_bf16x2_bits(__fadd_rn(f[2 * e], __uint_as_float(raw[r][e] << 16)),
-                                                 __fadd_rn(f[2 * e + 1], __uint_as_float(raw[r][e] & 0xffff0000u)));
+            for (int h = 0; h < EPV / 2; ++h)
+                x[r][h] = f32x2_to_bf16x2_bits(__fadd_rn(f[2 * h], __uint_as_float(x[r][h] << 16)),
+                                               __fadd_rn(f[2 * h + 1], __uint_as_float(x[r][h] & 0xffff0000u)));
         }
     }
 }
@@ -425,34 +550,65 @@ reduce_quantize_grouped_kernel(const void* __restrict__ acc, uint8_t* __restrict
     for (int i = 0; i < terms.count; ++i) {
         if (full) {
             const L cur = next;
-            cur.park(stage, lane);
-            if (has_group) {
-                s_a[wave][lane] = cur.scale;
-                s_b[wave][lane] = __fmul_rn(-static_cast<float>(cur.zp), cur.scale);   // as resolved(DequantParams) forms it
-                s_z[wave][lane] = cur.zp;
-            }
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             if (i + 1 < terms.count) next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
         } else {
-            // the tensor ends inside this chunk: byte loads up to the term's last byte, zeros behind it (they meet quiet NaNs, which stay NaN)
-            const uint8_t* c = terms.in[i] + v0 * T::OB;
-            const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
-            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
-            if (has_group) {
-                const float scale = terms.scales[i][gj];
-                const int32_t zp = terms.zero_points[i][gj];
-                s_a[wave][lane] = scale;
-                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
-                s_z[wave][lane] = zp;
-            }
+            grouped_park_term_partial<T>(terms, i, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
         }
         wave_lds_sync();
-        grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+        grouped_add_term<DT_ACC, DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
         wave_lds_sync();
     }
     grouped_quantize_chunk<DT_ACC, BITS, MODE, G, false>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave]);
 }
 
-// Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element.  Correct, not fast.
+// ---- The guarded kernels, for buffers that are not 16-byte aligned: one wave per group, element by element, the same bytes.  Correct, not fast.
+
+// What every guarded quantizing kernel does first for its group of `len` elements (<= 4096: 32-bit offsets inside the group; x_of(o) is element
+// o of what is quantized): the group's parameters -- read where they are given, else min / max with every element quieted, the wave reduction,
+// the f64 epilogue and, from lane 0 and unless `scales` is NULL, the write -- then the group's QuantParams (what is per call comes as the four
+// scalars) and DequantParams.  The min / max rounds have wave-uniform trip counts: a lane past the group's end sits the round out.  Every lane's
+// loads of the group are complete behind the wave reduction, so a kernel may overwrite what x_of reads.
+template <int BITS, class X>
+__device__ __forceinline__ void grouped_guarded_params(X&& x_of, int len, int lane, bool given, float* scales, uint8_t* zero_points, int64_t g, float threshold,
+                                                       uint32_t seed_lo, uint32_t seed_hi, uint64_t index_base, QuantParams& p, DequantParams& d) {
+    float scale;
+    int64_t zp;
+    if (given) {
+        scale = scales[g];
+        zp = zero_points[g];
+    } else {
+        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;   // the scan's identities (minmax_kernels.hpp)
+        for (int o0 = 0; o0 < len; o0 += 64) {
+            if (o0 + lane < len) {
+                const float x = quieted(x_of(o0 + lane));
+                lo = __builtin_fminf(lo, x);
+                hi = __builtin_fmaxf(hi, x);
+            }
+        }
+        lo = wave_min(lo);
+        hi = wave_max(hi);
+        quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
+        if (lane == 0 && scales != nullptr) {
+            scales[g] = scale;
+            zero_points[g] = static_cast<uint8_t>(zp);
+        }
+    }
+    p = QuantParams {};
+    p.threshold = threshold;
+    p.seed_lo = seed_lo;
+    p.seed_hi = seed_hi;
+    p.index_base = index_base;
+    p.inv_scale = __fdiv_rn(1.0f, scale);   // as the host forms 1 / scale for quantize_uniform
+    p.zp64 = zp;
+    p.zp32 = static_cast<int32_t>(zp);
+    d = DequantParams {};
+    d.scale = scale;
+    d.zp32 = p.zp32;
+    d.zp64 = zp;
+    d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);   // as resolved(DequantParams) forms it
+}
+
 template <int DT_IN, int BITS, int MODE, bool GIVEN>
 __global__ void __launch_bounds__(kGroupedBlock)
 quantize_grouped_scalar_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, int64_t group_size, float* __restrict__ scales,
@@ -460,33 +616,13 @@ quantize_grouped_scalar_kernel(const void* __restrict__ in, uint8_t* __restrict_
     constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1;
     const int lane = threadIdx.x & 63;
     const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
-    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + (threadIdx.x >> 6); g < ngroups; g += waves) {
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the group loop is wave-uniform
+    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
         const int64_t b = g * group_size, e = b + group_size < numel ? b + group_size : numel;
-        float scale;
-        int64_t zp;
-        if constexpr (GIVEN) {
-            scale = scales[g];
-            zp = zero_points[g];
-        } else {
-            float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
-            for (int64_t i = b + lane; i < e; i += 64) {
-                const float x = quieted(InVec<DT_IN>::load_scalar(in, i));
-                lo = __builtin_fminf(lo, x);
-                hi = __builtin_fmaxf(hi, x);
-            }
-            lo = wave_min(lo);
-            hi = wave_max(hi);
-            quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
-            if (lane == 0) {
-                scales[g] = scale;
-                zero_points[g] = static_cast<uint8_t>(zp);
-            }
-        }
-        QuantParams p = p0;
-        p.dyn = nullptr;
-        p.inv_scale = __fdiv_rn(1.0f, scale);
-        p.zp64 = zp;
-        p.zp32 = static_cast<int32_t>(zp);
+        QuantParams p;
+        DequantParams d;   // not used: nothing is read back here
+        grouped_guarded_params<BITS>([&](int o) { return InVec<DT_IN>::load_scalar(in, b + o); }, static_cast<int>(e - b), lane, GIVEN, scales, zero_points, g,
+                                     p0.threshold, p0.seed_lo, p0.seed_hi, p0.index_base, p, d);
         for (int64_t by = b / PACK + lane; by < (e + PACK - 1) / PACK; by += 64) {
             uint32_t acc = 0;
             for (int k = 0; k < PACK; ++k) {
@@ -567,16 +703,8 @@ __device__ __forceinline__ void grouped_dequantize_chunk(const uint8_t* __restri
         p.zp32 = s_zp[slot];
         p.zp64 = p.zp32;
         uint32_t w[IB > 4 ? 2 : 1];
-        const uint8_t* src = s_in + c * IB;
-        if constexpr (IB == 1) w[0] = *src;
-        else if constexpr (IB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
-        else if constexpr (IB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
-        else {
-            const u32x2 t = *reinterpret_cast<const u32x2*>(src);
-            w[0] = t[0];
-            w[1] = t[1];
-        }
-        float f[EPV];
+        staged_words<IB>(s_in + c * IB, w);
+        float f[EPV];   // the loop is written out: through grouped_dequantize_row several instances of these kernels compiled to other code
 #pragma unroll
         for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p);
         if (full || e0 + ce + EPV <= numel) {
@@ -659,9 +787,8 @@ dequantize_grouped_batch_kernel(GroupedDequantBatchArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    if (c >= a.chunk_begin[a.count]) return;
-    int t = 0;
-    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
     const int64_t numel = a.numel[t];
     grouped_dequantize_chunk<BITS, DT_OUT, OP, G>(a.in[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G,
                                                   (c - a.chunk_begin[t]) * T::CHUNK_ELEMS, lane, s_in[wave], s_scale[wave], s_bias[wave], s_zp[wave]);
@@ -743,26 +870,6 @@ __device__ __forceinline__ void grouped_parked_dequant_params(DequantParams (&p)
     }
 }
 
-// f = the lane's input vector of row r, dequantized from its packed words in `stage` in the pair's own form
-template <int DT, int BITS, int G>
-__device__ __forceinline__ void grouped_dequantize_row(const uint8_t* stage, int r, int lane, const DequantParams& p, float (&f)[InVec<DT>::EPV]) {
-    using T = GroupedQuantTile<DT, BITS, G>;
-    constexpr int EPV = T::EPV, OB = T::OB;
-    constexpr int FORM = DequantForm<BITS, DT>::value;
-    const uint8_t* src = stage + (r * 64 + lane) * OB;
-    uint32_t w[OB > 4 ? 2 : 1];
-    if constexpr (OB == 1) w[0] = *src;
-    else if constexpr (OB == 2) w[0] = *reinterpret_cast<const uint16_t*>(src);
-    else if constexpr (OB == 4) w[0] = *reinterpret_cast<const uint32_t*>(src);
-    else {
-        const u32x2 t = *reinterpret_cast<const u32x2*>(src);
-        w[0] = t[0];
-        w[1] = t[1];
-    }
-#pragma unroll
-    for (int e = 0; e < EPV; ++e) f[e] = dequant_one<FORM>((w[(e * BITS) >> 5] >> ((e * BITS) & 31)) & ((1u << BITS) - 1u), p);
-}
-
 // vector `vec` of a tensor of type DT and numel elements <- o: one 16-byte write-through store, or element by element where the tensor ends inside
 // the vector (nothing at or past numel is written).  grouped_residual_store keeps this step written out in its loop: called through here, the
 // partial-chunk tail of the bfloat16 error-feedback kernels compiled to differently arranged branches, and those kernels stay instruction for
@@ -821,25 +928,35 @@ __device__ __forceinline__ void grouped_residual_store(u32x4 (&raw)[NV_], void* 
     }
 }
 
-// one wave's chunk (NG groups from group g0 on) of one (tensor, residual) pair; the wave's LDS slices as in grouped_quantize_chunk plus s_c (NG floats)
-template <int DT_IN, int BITS, int MODE, int G>
+// One wave's chunk (NG groups from group g0 on) of one (tensor, residual) pair; the wave's LDS slices as in grouped_quantize_chunk plus s_c (NG
+// floats).  DT_RES, the residual's type, is the pipeline's: it picks the tile, the quantize body and the dequantize form of the subtraction.  The
+// tensor has that type too, or is bfloat16 beside a float32 residual: then the bytes are those of the float32 pipeline on widen(x), and x is only
+// ever read.  Every load of x and of the residual is issued before the first use.
+template <int DT_IN, int DT_RES, int BITS, int MODE, int G>
 __device__ __forceinline__ void grouped_ef_chunk(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel,
                                                  float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
                                                  int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b, float* s_c) {
-    using T = GroupedQuantTile<DT_IN, BITS, G>;
+    using T = GroupedQuantTile<DT_RES, BITS, G>;
     constexpr int NV = T::NV, NG = T::NG;
     const int64_t v0 = g0 * T::V;
     const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
 
     u32x4 raw[NV];
-    {
+    if constexpr (DT_IN == DT_RES) {
         u32x4 res[NV];
-        grouped_load<DT_IN, NV>(in, numel, v0, lane, full, raw);
-        grouped_load<DT_IN, NV>(residual, numel, v0, lane, full, res);
-        grouped_add_residual<DT_IN, NV>(raw, res);
+        grouped_load<DT_RES, NV>(in, numel, v0, lane, full, raw);
+        grouped_load<DT_RES, NV>(residual, numel, v0, lane, full, res);
+        grouped_add_residual<DT_RES, NV>(raw, res);
+    } else {
+        u32x2 t[NV];
+        u32x4 res[NV];
+        grouped_load_bf16x4<NV>(in, numel, v0, lane, full, t);
+        grouped_load<DT_RES, NV>(residual, numel, v0, lane, full, res);
+        grouped_widen_bf16x4<NV>(t, raw);
+        grouped_add_residual<DT_RES, NV>(raw, res);
     }
-    grouped_quantize_chunk<DT_IN, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
-    grouped_residual_store<DT_IN, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
+    grouped_quantize_chunk<DT_RES, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
+    grouped_residual_store<DT_RES, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
 }
 
 template <int DT_IN, int BITS, int MODE, int G>
@@ -853,9 +970,11 @@ quantize_grouped_ef_kernel(const void* __restrict__ in, void* residual, uint8_t*
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t g0 = (static_cast<int64_t>(blockIdx.x) * WAVES + wave) * NG;
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
     if (g0 >= ngroups) return;
-    grouped_ef_chunk<DT_IN, BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+    grouped_ef_chunk<DT_IN, DT_IN, BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave],
+                                                  s_c[wave]);
 }
 
 // Up to kGroupedBatchMax independent (tensor, residual) pairs in ONE launch, found through the prefix table of quantize_grouped_batch_kernel.
@@ -881,37 +1000,21 @@ quantize_grouped_ef_batch_kernel(GroupedEfBatchArgs a, QuantParams p0) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    if (c >= a.chunk_begin[a.count]) return;
-    int t = 0;
-    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
     const int64_t numel = a.numel[t];
-    grouped_ef_chunk<DT_IN, BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
-                                           (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+    grouped_ef_chunk<DT_IN, DT_IN, BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
+                                                  (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
 }
 
 // ---- Error feedback on a re-quantized partial sum (piquant_hip_reduce_quantize_grouped_ef): the owner's step of a mesh all-reduce and every hop of
 // a ring, compensated.  y = rn(rn(..rn(acc + d(term_0)).. + d(term_{k-1})) + residual), (q, scales, zero_points) = quantize_grouped(y),
 // residual <- rn(y - d(q)), in ONE launch: the bytes of k grouped dequantize ADD calls into acc followed by quantize_grouped_ef(acc, residual).
 // The tile and the term staging are reduce_quantize_grouped_kernel's, the tail is grouped_ef_chunk's.  The last term is peeled out of the loop so
-// that the residual rows need not be live across it: their loads are issued either with the acc rows (RES_EARLY: NV more vectors per lane through
-// the whole term loop) or right after the last term has been parked in LDS, where they fly during that term's dequantize and add
-// (profiles/EXPERIMENTS.md has the comparison; DESIGN.md 4c the choice).  No scan, no atomics, no grid barrier; waves never wait for one another.
-#ifndef PQ_REDUCE_EF_RESIDUAL_EARLY
-#define PQ_REDUCE_EF_RESIDUAL_EARLY 0
-#endif
-
-// the term in `t` into the wave's LDS slices: its packed bytes and, from lane j < NG, group j's {scale, bias, zero point}
-template <class L>
-__device__ __forceinline__ void grouped_park_term(const L& t, uint8_t* stage, float* s_scale, float* s_bias, int32_t* s_zp, bool has_group, int lane) {
-    t.park(stage, lane);
-    if (has_group) {
-        s_scale[lane] = t.scale;
-        s_bias[lane] = __fmul_rn(-static_cast<float>(t.zp), t.scale);   // as resolved(DequantParams) forms it
-        s_zp[lane] = t.zp;
-    }
-}
-
-template <int DT_ACC, int BITS, int MODE, int G, bool RES_EARLY = (PQ_REDUCE_EF_RESIDUAL_EARLY != 0)>
+// that the residual rows need not be live across it: their loads are issued right after the last term has been parked in LDS, where they fly
+// during that term's dequantize and add (loading them with the acc rows lost: profiles/EXPERIMENTS.md has the comparison, DESIGN.md 4c the
+// choice).  No scan, no atomics, no grid barrier; waves never wait for one another.
+template <int DT_ACC, int BITS, int MODE, int G>
 __global__ void __launch_bounds__(kGroupedBlock)
 reduce_quantize_grouped_ef_kernel(const void* __restrict__ acc, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
                                   uint8_t* __restrict__ zero_points, int64_t ngroups, QuantParams p0, GroupedTerms terms) {
@@ -939,20 +1042,20 @@ reduce_quantize_grouped_ef_kernel(const void* __restrict__ acc, void* residual, 
         L next;
         if (count > 0) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
         grouped_load<DT_ACC, NV>(acc, numel, v0, lane, true, raw);
-        if (RES_EARLY || count == 0) grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
+        if (count == 0) grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
         for (int i = 0; i + 1 < count; ++i) {
             const L cur = next;
             grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
             wave_lds_sync();
-            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_ACC, DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
         if (count > 0) {   // the last term: nothing left to prefetch but the residual
             grouped_park_term(next, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
-            if constexpr (!RES_EARLY) grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
+            grouped_load<DT_ACC, NV>(residual, numel, v0, lane, true, res);
             wave_lds_sync();
-            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_ACC, DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
     } else {
@@ -961,17 +1064,9 @@ reduce_quantize_grouped_ef_kernel(const void* __restrict__ acc, void* residual, 
         grouped_load<DT_ACC, NV>(residual, numel, v0, lane, false, res);
         const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
         for (int i = 0; i < count; ++i) {
-            const uint8_t* c = terms.in[i] + v0 * T::OB;
-            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
-            if (has_group) {
-                const float scale = terms.scales[i][gj];
-                const int32_t zp = terms.zero_points[i][gj];
-                s_a[wave][lane] = scale;
-                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
-                s_z[wave][lane] = zp;
-            }
+            grouped_park_term_partial<T>(terms, i, v0, left, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             wave_lds_sync();
-            grouped_add_term<DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_ACC, DT_ACC, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
     }
@@ -981,54 +1076,28 @@ reduce_quantize_grouped_ef_kernel(const void* __restrict__ acc, void* residual, 
     grouped_residual_store<DT_ACC, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c[wave], s_b[wave]);
 }
 
-// Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element, the same bytes.  Correct, not fast.
-template <int DT_IN, int BITS, int MODE>
-__global__ void __launch_bounds__(kGroupedBlock)
-quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
-                                  float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, float threshold, uint32_t seed_lo,
-                                  uint32_t seed_hi, uint64_t index_base) {
-    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1, FORM = DequantForm<BITS, DT_IN>::value;
+// Guarded form (grouped_guarded_params) of both error-feedback quantizes: the tensor of type DT_IN, the residual -- and with it the pipeline -- of
+// type DT_RES.  y = rn(x + r) in DT_RES is formed twice, for the min / max pass and for the quantization; the residual is overwritten in between
+// by nobody: its stores come behind the wave reduction.
+template <int DT_IN, int DT_RES, int BITS, int MODE>
+__device__ __forceinline__ void grouped_ef_guarded(const void* in, void* residual, uint8_t* out, int64_t numel, int64_t group_size, float* scales,
+                                                   uint8_t* zero_points, int64_t ngroups, float threshold, uint32_t seed_lo, uint32_t seed_hi,
+                                                   uint64_t index_base) {
+    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1, FORM = DequantForm<BITS, DT_RES>::value;
     const int lane = threadIdx.x & 63;
     const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the group loop is wave-uniform
     for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
         const int64_t b = g * group_size;
-        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);   // <= 4096: 32-bit offsets inside the group
+        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);
         auto y_of = [&](int o) {
-            const float y = __fadd_rn(InVec<DT_IN>::load_scalar(in, b + o), InVec<DT_IN>::load_scalar(residual, b + o));
-            if constexpr (DT_IN == DT_BF16) return bf16_bits_to_f32(f32_to_bf16_bits(y));
+            const float y = __fadd_rn(InVec<DT_IN>::load_scalar(in, b + o), InVec<DT_RES>::load_scalar(residual, b + o));
+            if constexpr (DT_RES == DT_BF16) return bf16_bits_to_f32(f32_to_bf16_bits(y));
             else return y;
         };
-        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
-        for (int o0 = 0; o0 < len; o0 += 64) {   // wave-uniform trip counts: a lane past the group's end sits the step out
-            if (o0 + lane < len) {
-                const float x = quieted(y_of(o0 + lane));
-                lo = __builtin_fminf(lo, x);
-                hi = __builtin_fmaxf(hi, x);
-            }
-        }
-        lo = wave_min(lo);   // every lane's loads of the group are complete here: the residual is overwritten below
-        hi = wave_max(hi);
-        float scale;
-        int64_t zp;
-        quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
-        if (lane == 0) {
-            scales[g] = scale;
-            zero_points[g] = static_cast<uint8_t>(zp);
-        }
-        QuantParams p {};   // what is per call, and the group's parameters
-        p.threshold = threshold;
-        p.seed_lo = seed_lo;
-        p.seed_hi = seed_hi;
-        p.index_base = index_base;
-        p.inv_scale = __fdiv_rn(1.0f, scale);
-        p.zp64 = zp;
-        p.zp32 = static_cast<int32_t>(zp);
-        DequantParams d {};
-        d.scale = scale;
-        d.zp32 = p.zp32;
-        d.zp64 = zp;
-        d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);
+        QuantParams p;
+        DequantParams d;
+        grouped_guarded_params<BITS>(y_of, len, lane, false, scales, zero_points, g, threshold, seed_lo, seed_hi, index_base, p, d);
         uint8_t* og = out + b / PACK;   // a group starts on a whole packed byte
         for (int by0 = 0; by0 * PACK < len; by0 += 64) {
             const int by = by0 + lane;
@@ -1041,8 +1110,8 @@ quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, u
                 const float y = y_of(o);
                 const uint32_t q = quant_one<MODE, QMAX>(y, p, static_cast<uint64_t>(b + o));
                 acc |= q << (k * BITS);
-                const float nr = residual_one<DT_IN>(y, dequant_one<FORM>(q, d));
-                if constexpr (DT_IN == DT_F32) static_cast<float*>(residual)[b + o] = nr;
+                const float nr = residual_one<DT_RES>(y, dequant_one<FORM>(q, d));
+                if constexpr (DT_RES == DT_F32) static_cast<float*>(residual)[b + o] = nr;
                 else static_cast<uint16_t*>(residual)[b + o] = static_cast<uint16_t>(f32_to_bf16_bits(nr));
             }
             og[by] = static_cast<uint8_t>(acc);
@@ -1050,69 +1119,20 @@ quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, u
     }
 }
 
+template <int DT_IN, int BITS, int MODE>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_ef_scalar_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
+                                  float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, float threshold, uint32_t seed_lo,
+                                  uint32_t seed_hi, uint64_t index_base) {
+    grouped_ef_guarded<DT_IN, DT_IN, BITS, MODE>(in, residual, out, numel, group_size, scales, zero_points, ngroups, threshold, seed_lo, seed_hi, index_base);
+}
+
 // ---- Error feedback with a float32 residual for a bfloat16 tensor (piquant_hip_quantize_grouped_ef_mixed): the bytes of
 // quantize_grouped_ef(widen(x), residual) in the float32 pipeline, without the widened copy of x ever reaching memory.  The tile is the float32
 // one, GroupedQuantTile<DT_F32, BITS, G>: a lane-row is four elements, which of x are 8 bytes (one global_load_dwordx2, 512 contiguous bytes per
-// wave-row) widened into raw[r][e] = bits << 16, and of the residual one 16-byte vector.  From there on everything is grouped_ef_chunk<DT_F32>'s:
-// y = rn_f32(widen(x) + r), the float32 quantize chunk body (KEEP), r <- rn_f32(y - d) with d the float32 dequantize form.  x is never written.
-
-// one wave's chunk of the bfloat16 tensor `in` as NV rows of four elements, still packed (8 bytes a lane-row); elements at or past numel read as
-// quiet NaNs.  Load only: nothing here uses what it loads, so that the residual's loads can be issued behind these without a wait between them.
-template <int NV>
-__device__ __forceinline__ void grouped_load_bf16x4(const void* in, int64_t numel, int64_t v0, int lane, bool full, u32x2 (&t)[NV]) {
-    const u32x2* in8 = static_cast<const u32x2*>(in);
-    if (full) {
-#pragma unroll
-        for (int r = 0; r < NV; ++r) t[r] = ld<true>(in8 + v0 + r * 64 + lane);
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < NV; ++r) {
-        const int64_t vec = v0 + r * 64 + lane;
-        if ((vec + 1) * 4 <= numel) {
-            t[r] = ld<true>(in8 + vec);
-        } else {
-            t[r] = u32x2 {0x7fc07fc0u, 0x7fc07fc0u};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {   // unrolled: constant register indices
-                const int64_t i = vec * 4 + e;
-                if (i >= numel) continue;
-                t[r][e >> 1] = (t[r][e >> 1] & ((e & 1) ? 0x0000ffffu : 0xffff0000u)) |
-                               (static_cast<uint32_t>(static_cast<const uint16_t*>(in)[i]) << ((e & 1) * 16));
-            }
-        }
-    }
-}
-
-// the packed rows widened to float32 bits: raw[r][e] = bits << 16
-template <int NV>
-__device__ __forceinline__ void grouped_widen_bf16x4(const u32x2 (&t)[NV], u32x4 (&raw)[NV]) {
-#pragma unroll
-    for (int r = 0; r < NV; ++r) raw[r] = u32x4 {t[r][0] << 16, t[r][0] & 0xffff0000u, t[r][1] << 16, t[r][1] & 0xffff0000u};
-}
-
-// one wave's chunk (NG groups of the float32 tile from group g0 on) of one (bfloat16 tensor, float32 residual) pair; LDS slices as grouped_ef_chunk
-template <int BITS, int MODE, int G>
-__device__ __forceinline__ void grouped_ef_f32r_chunk(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel,
-                                                      float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, const QuantParams& p0,
-                                                      int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b, float* s_c) {
-    using T = GroupedQuantTile<DT_F32, BITS, G>;
-    constexpr int NV = T::NV, NG = T::NG;
-    const int64_t v0 = g0 * T::V;
-    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
-
-    u32x4 raw[NV];
-    {
-        u32x2 t[NV];
-        u32x4 res[NV];
-        grouped_load_bf16x4<NV>(in, numel, v0, lane, full, t);   // every load of x and of the residual is issued before the first use
-        grouped_load<DT_F32, NV>(residual, numel, v0, lane, full, res);
-        grouped_widen_bf16x4<NV>(t, raw);
-        grouped_add_residual<DT_F32, NV>(raw, res);
-    }
-    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
-    grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
-}
+// wave-row) widened into raw[r][e] = bits << 16, and of the residual one 16-byte vector.  That is the second branch of grouped_ef_chunk
+// (DT_IN = bfloat16, DT_RES = float32); behind it the function goes on as for a float32 tensor: y = rn_f32(widen(x) + r), the float32 quantize
+// chunk body (KEEP), r <- rn_f32(y - d) with d the float32 dequantize form.  x is never written.
 
 template <int BITS, int MODE, int G>
 __global__ void __launch_bounds__(kGroupedBlock)
@@ -1125,9 +1145,11 @@ quantize_grouped_ef_f32r_kernel(const void* __restrict__ in, void* residual, uin
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t g0 = (static_cast<int64_t>(blockIdx.x) * WAVES + wave) * NG;
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
     if (g0 >= ngroups) return;
-    grouped_ef_f32r_chunk<BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+    grouped_ef_chunk<DT_BF16, DT_F32, BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, p0, g0, lane, s_out[wave], s_a[wave], s_b[wave],
+                                                     s_c[wave]);
 }
 
 // up to kGroupedBatchMax independent pairs in ONE launch, found through the prefix table of quantize_grouped_batch_kernel
@@ -1142,122 +1164,28 @@ quantize_grouped_ef_f32r_batch_kernel(GroupedEfBatchArgs a, QuantParams p0) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    if (c >= a.chunk_begin[a.count]) return;
-    int t = 0;
-    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
     const int64_t numel = a.numel[t];
-    grouped_ef_f32r_chunk<BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
-                                         (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
+    grouped_ef_chunk<DT_BF16, DT_F32, BITS, MODE, G>(a.in[t], a.residual[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0,
+                                                     (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
 }
 
-// Guarded form for buffers of any (element) alignment: one wave per group, element by element, the same bytes.  Correct, not fast.
+// the guarded form, for buffers of any (element) alignment
 template <int BITS, int MODE>
 __global__ void __launch_bounds__(kGroupedBlock)
 quantize_grouped_ef_f32r_scalar_kernel(const void* __restrict__ in, void* residual, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
                                        float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, float threshold, uint32_t seed_lo,
                                        uint32_t seed_hi, uint64_t index_base) {
-    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1, FORM = DequantForm<BITS, DT_F32>::value;
-    const int lane = threadIdx.x & 63;
-    const int64_t waves = static_cast<int64_t>(gridDim.x) * (kGroupedBlock / 64);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // the group loop is wave-uniform
-    for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
-        const int64_t b = g * group_size;
-        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);   // <= 4096: 32-bit offsets inside the group
-        auto y_of = [&](int o) { return __fadd_rn(InVec<DT_BF16>::load_scalar(in, b + o), static_cast<const float*>(residual)[b + o]); };
-        float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
-        for (int o0 = 0; o0 < len; o0 += 64) {   // wave-uniform trip counts: a lane past the group's end sits the step out
-            if (o0 + lane < len) {
-                const float x = quieted(y_of(o0 + lane));
-                lo = __builtin_fminf(lo, x);
-                hi = __builtin_fmaxf(hi, x);
-            }
-        }
-        lo = wave_min(lo);   // every lane's loads of the group are complete here: the residual is overwritten below
-        hi = wave_max(hi);
-        float scale;
-        int64_t zp;
-        quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
-        if (lane == 0) {
-            scales[g] = scale;
-            zero_points[g] = static_cast<uint8_t>(zp);
-        }
-        QuantParams p {};   // what is per call, and the group's parameters
-        p.threshold = threshold;
-        p.seed_lo = seed_lo;
-        p.seed_hi = seed_hi;
-        p.index_base = index_base;
-        p.inv_scale = __fdiv_rn(1.0f, scale);
-        p.zp64 = zp;
-        p.zp32 = static_cast<int32_t>(zp);
-        DequantParams d {};
-        d.scale = scale;
-        d.zp32 = p.zp32;
-        d.zp64 = zp;
-        d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);
-        uint8_t* og = out + b / PACK;   // a group starts on a whole packed byte
-        for (int by0 = 0; by0 * PACK < len; by0 += 64) {
-            const int by = by0 + lane;
-            if (by * PACK >= len) continue;
-            uint32_t acc = 0;
-#pragma unroll
-            for (int k = 0; k < PACK; ++k) {
-                const int o = by * PACK + k;
-                if (o >= len) continue;
-                const float y = y_of(o);
-                const uint32_t q = quant_one<MODE, QMAX>(y, p, static_cast<uint64_t>(b + o));
-                acc |= q << (k * BITS);
-                static_cast<float*>(residual)[b + o] = residual_one<DT_F32>(y, dequant_one<FORM>(q, d));
-            }
-            og[by] = static_cast<uint8_t>(acc);
-        }
-    }
+    grouped_ef_guarded<DT_BF16, DT_F32, BITS, MODE>(in, residual, out, numel, group_size, scales, zero_points, ngroups, threshold, seed_lo, seed_hi, index_base);
 }
 
 // ---- The two fused: error feedback on a re-quantized partial sum of a bfloat16 accumulator with a float32 residual
-// (piquant_hip_reduce_quantize_grouped_ef_mixed).  The bytes of k grouped dequantize ADD calls into the bfloat16 acc followed by the mixed
-// quantize above, in ONE launch: acc <- rn_bf16(widen(acc) + d(term_i)) term by term with d the uint -> bfloat16 dequantize form, then
-// y = rn_f32(widen(acc) + r), the float32 quantize chunk body and r <- rn_f32(y - d).  The tile is the float32 one (a lane-row is four elements),
-// the term staging and the prefetch order are reduce_quantize_grouped_ef_kernel's on that tile.  The accumulator rows stay PACKED (u32x2: two
-// bfloat16 a dword, 2 NV registers instead of 4 NV) through the term loop -- every add rounds back to bfloat16 anyway, with the pairwise
-// conversion the bfloat16 tile uses -- and are widened once behind the last term.  No scan, no atomics, no grid barrier; waves never wait for
-// one another.
-
-// t[r] = rn_bf16(widen(t[r]) + the dequantized packed bytes of the lane's four-element vector r), in the uint -> bfloat16 form of the pair;
-// geometry and group parameters per set of the float32 tile
-template <int BITS, int G, int NV_ = GroupedQuantTile<DT_F32, BITS, G>::NV>
-__device__ __forceinline__ void grouped_add_term_bf16x4(u32x2 (&t)[NV_], const uint8_t* stage, const float* s_scale, const float* s_bias,
-                                                        const int32_t* s_zp, int lane) {
-    using T = GroupedQuantTile<DT_F32, BITS, G>;
-    constexpr int OB = T::OB, NV = T::NV, RPG = T::RPG, SETS = T::SETS, LPG = T::LPG, GPR = T::GPR;
-    constexpr int FORM = DequantForm<BITS, DT_BF16>::value;
-    static_assert(T::EPV == 4 && OB <= 4, "four elements a lane-row: at most one packed dword");
-    DequantParams p[SETS];
-#pragma unroll
-    for (int s = 0; s < SETS; ++s) {
-        const int slot = s * GPR + lane / LPG;
-        p[s] = DequantParams {};
-        p[s].scale = s_scale[slot];
-        p[s].bias = s_bias[slot];
-        p[s].zp32 = s_zp[slot];
-        p[s].zp64 = p[s].zp32;
-    }
-#pragma unroll
-    for (int r = 0; r < NV; ++r) {
-        const uint8_t* src = stage + (r * 64 + lane) * OB;
-        uint32_t w;
-        if constexpr (OB == 1) w = *src;
-        else if constexpr (OB == 2) w = *reinterpret_cast<const uint16_t*>(src);
-        else w = *reinterpret_cast<const uint32_t*>(src);
-        float f[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) f[e] = dequant_one<FORM>((w >> (e * BITS)) & ((1u << BITS) - 1u), p[r / RPG]);
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            t[r][h] = f32x2_to_bf16x2_bits(__fadd_rn(f[2 * h], __uint_as_float(t[r][h] << 16)),
-                                           __fadd_rn(f[2 * h + 1], __uint_as_float(t[r][h] & 0xffff0000u)));
-    }
-}
-
+// (piquant_hip_reduce_quantize_grouped_ef_mixed).  reduce_quantize_grouped_ef_kernel on the float32 tile, in three places different: the
+// accumulator rows stay PACKED (u32x2: two bfloat16 a dword, 2 NV registers instead of 4 NV) through the term loop -- every add rounds back to
+// bfloat16 anyway --, grouped_add_term adds in the uint -> bfloat16 form, and the rows are widened once behind the last term.  The bytes are
+// those of k grouped dequantize ADD calls into the bfloat16 acc followed by the mixed quantize above.  The two kernels are written out side by
+// side: as one body under two thin kernels every probed instance of both compiled to other code (profiles/EXPERIMENTS.md).
 template <int BITS, int MODE, int G>
 __global__ void __launch_bounds__(kGroupedBlock)
 reduce_quantize_grouped_ef_f32r_kernel(const void* __restrict__ acc, void* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
@@ -1293,14 +1221,14 @@ reduce_quantize_grouped_ef_f32r_kernel(const void* __restrict__ acc, void* resid
             grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
             wave_lds_sync();
-            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_BF16, DT_F32, BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
         if (count > 0) {   // the last term: nothing left to prefetch but the residual
             grouped_park_term(next, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             grouped_load<DT_F32, NV>(residual, numel, v0, lane, true, res);
             wave_lds_sync();
-            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_BF16, DT_F32, BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
     } else {
@@ -1309,17 +1237,9 @@ reduce_quantize_grouped_ef_f32r_kernel(const void* __restrict__ acc, void* resid
         grouped_load<DT_F32, NV>(residual, numel, v0, lane, false, res);
         const int64_t left = (numel + PACK - 1) / PACK - v0 * T::OB;
         for (int i = 0; i < count; ++i) {
-            const uint8_t* c = terms.in[i] + v0 * T::OB;
-            for (int b = lane; b < T::OUT_BYTES; b += 64) stage[b] = b < left ? c[b] : 0;
-            if (has_group) {
-                const float scale = terms.scales[i][gj];
-                const int32_t zp = terms.zero_points[i][gj];
-                s_a[wave][lane] = scale;
-                s_b[wave][lane] = __fmul_rn(-static_cast<float>(zp), scale);
-                s_z[wave][lane] = zp;
-            }
+            grouped_park_term_partial<T>(terms, i, v0, left, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
             wave_lds_sync();
-            grouped_add_term_bf16x4<BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+            grouped_add_term<DT_BF16, DT_F32, BITS, G>(t, stage, s_a[wave], s_b[wave], s_z[wave], lane);
             wave_lds_sync();
         }
     }

@@ -84,7 +84,8 @@ quantize_dequantize_grouped_kernel(const void* in, void* out, int64_t numel, flo
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t g0 = (static_cast<int64_t>(blockIdx.x) * WAVES + wave) * NG;
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
     if (g0 >= ngroups) return;
     grouped_requant_chunk<DT, BITS, MODE, G>(in, out, numel, scales, zero_points, ngroups, p0, g0, given != 0, add != 0, lane, s_out[wave], s_a[wave],
                                              s_b[wave], s_c[wave]);
@@ -112,17 +113,16 @@ quantize_dequantize_grouped_batch_kernel(GroupedRequantBatchArgs a, int given, i
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    if (c >= a.chunk_begin[a.count]) return;
-    int t = 0;
-    while (t + 1 < a.count && c >= a.chunk_begin[t + 1]) ++t;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
     const int64_t numel = a.numel[t];
     grouped_requant_chunk<DT, BITS, MODE, G>(a.in[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, p0, (c - a.chunk_begin[t]) * NG,
                                              given != 0, add != 0, lane, s_out[wave], s_a[wave], s_b[wave], s_c[wave]);
 }
 
-// Guarded form for buffers that are not 16-byte aligned: one wave per group, element by element, the same bytes.  Correct, not fast.  Given
-// parameters, the store op and whether computed parameters are written are runtime here.  The group's min / max pass ends in a wave reduction, so
-// every load of it is complete before the group's first store: out == in stays correct.
+// Guarded form (grouped_guarded_params) for buffers that are not 16-byte aligned.  Given parameters, the store op and whether computed parameters
+// are written are runtime here.  The group's min / max pass ends in a wave reduction, so every load of it is complete before the group's first
+// store: out == in stays correct.
 template <int DT, int BITS, int MODE>
 __global__ void __launch_bounds__(kGroupedBlock)
 quantize_dequantize_grouped_scalar_kernel(const void* in, void* out, int64_t numel, int64_t group_size, float* scales, uint8_t* zero_points, int64_t ngroups,
@@ -134,41 +134,10 @@ quantize_dequantize_grouped_scalar_kernel(const void* in, void* out, int64_t num
     for (int64_t g = static_cast<int64_t>(blockIdx.x) * (kGroupedBlock / 64) + wave; g < ngroups; g += waves) {
         const int64_t b = g * group_size;
         const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);   // <= 4096: 32-bit offsets inside the group
-        float scale;
-        int64_t zp;
-        if (given) {
-            scale = scales[g];
-            zp = zero_points[g];
-        } else {
-            float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
-            for (int o0 = 0; o0 < len; o0 += 64) {   // wave-uniform trip counts: a lane past the group's end sits the step out
-                if (o0 + lane < len) {
-                    const float x = quieted(InVec<DT>::load_scalar(in, b + o0 + lane));
-                    lo = __builtin_fminf(lo, x);
-                    hi = __builtin_fmaxf(hi, x);
-                }
-            }
-            lo = wave_min(lo);   // every lane's loads of the group are complete here: with out == in the group is overwritten below
-            hi = wave_max(hi);
-            quant_params_epilogue(float_to_key(lo), float_to_key(-hi), BITS, scale, zp);
-            if (lane == 0 && scales != nullptr) {
-                scales[g] = scale;
-                zero_points[g] = static_cast<uint8_t>(zp);
-            }
-        }
-        QuantParams p {};   // what is per call, and the group's parameters
-        p.threshold = threshold;
-        p.seed_lo = seed_lo;
-        p.seed_hi = seed_hi;
-        p.index_base = index_base;
-        p.inv_scale = __fdiv_rn(1.0f, scale);
-        p.zp64 = zp;
-        p.zp32 = static_cast<int32_t>(zp);
-        DequantParams d {};
-        d.scale = scale;
-        d.zp32 = p.zp32;
-        d.zp64 = zp;
-        d.bias = __fmul_rn(-static_cast<float>(d.zp32), scale);
+        QuantParams p;
+        DequantParams d;
+        grouped_guarded_params<BITS>([&](int o) { return InVec<DT>::load_scalar(in, b + o); }, len, lane, given != 0, scales, zero_points, g, threshold, seed_lo,
+                                     seed_hi, index_base, p, d);
         for (int o0 = 0; o0 < len; o0 += 64) {
             const int o = o0 + lane;
             if (o >= len) continue;

@@ -74,36 +74,23 @@ void launch_dequantize_grouped_batch(const GroupedDequantBatchLaunch& b, hipStre
     PQ_HIP(hipGetLastError());
 }
 
-void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream) {
-    static_assert(kGroupedReduceMaxInputs == kGroupedReduceMaxTerms, "host and device term limits");
-    if (r.numel <= 0) return;
-    if (r.count < 0 || r.count > kGroupedReduceMaxTerms) panic("reduce_quantize_grouped: %d terms, at most %d per launch", r.count, kGroupedReduceMaxTerms);
-    const QuantParams p = grouped_call_params(r.rm);
-    GroupedTerms terms {};
-    for (int i = 0; i < r.count; ++i) {
-        terms.in[i] = static_cast<const uint8_t*>(r.term[i].in);
-        terms.scales[i] = r.term[i].scales;
-        terms.zero_points[i] = r.term[i].zero_points;
+namespace {
+
+struct ReduceFamily {
+    static constexpr const char* name = "reduce_quantize_grouped";
+    static constexpr bool residual = false;
+    template <class F>
+    static void with_pipeline_type(int dt_in, F&& f) {
+        with_float_type(dt_in, f);
     }
-    terms.count = r.count;
-    const int64_t ngroups = (r.numel + r.group_size - 1) / r.group_size;
-    with_float_type(r.dt_in, [&](auto di) {
-        constexpr int DT_ACC = decltype(di)::value;
-        with_quant_bits(r.dt_out, [&](auto bi) {
-            constexpr int BITS = decltype(bi)::value;
-            with_round_mode<DT_ACC, BITS>(r.rm.round_mode, [&](auto mi) {
-                constexpr int MODE = decltype(mi)::value;
-                with_group_size(r.group_size, "reduce_quantize_grouped", [&](auto gi) {
-                    constexpr int G = decltype(gi)::value;
-                    constexpr int NG = GroupedQuantTile<DT_ACC, BITS, G>::NG;
-                    const dim3 grid(grouped_blocks((ngroups + NG - 1) / NG, "reduce_quantize_grouped"));
-                    PQ_LAUNCH((reduce_quantize_grouped_kernel<DT_ACC, BITS, MODE, G>), grid, dim3(kGroupedBlock), 0, stream, r.in, static_cast<uint8_t*>(r.out),
-                              r.numel, r.scales, r.zero_points, ngroups, p, terms);
-                });
-            });
-        });
-    });
-    PQ_HIP(hipGetLastError());
-}
+    template <int DT_ACC, int BITS, int MODE, int G>
+    static auto kernel() {
+        return &reduce_quantize_grouped_kernel<DT_ACC, BITS, MODE, G>;
+    }
+};
+
+}  // namespace
+
+void launch_reduce_quantize_grouped(const GroupedReduceLaunch& r, hipStream_t stream) { launch_grouped_reduce<ReduceFamily>(r, stream); }
 
 }  // namespace pq
