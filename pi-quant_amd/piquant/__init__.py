@@ -67,6 +67,20 @@ class DataType(Enum):
         return (numel + per - 1) // per
 
 
+def _ptr_array(ptrs):
+    """``void*[]`` of a list of addresses for a C call (one slot for an empty list, so that the array is never NULL)."""
+    return (_C.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+
+def _size_array(sizes):
+    return (_C.c_size_t * len(sizes))(*sizes)
+
+
+def _ef_entry(plain, mixed, residual_dtype):
+    """The C entry point of an error-feedback call and what it takes behind the residual's address: nothing, or the residual's own dtype (``_mixed``)."""
+    return (plain, ()) if residual_dtype is None else (mixed, (residual_dtype.value,))
+
+
 class Context:
     """Owns one native context, bound to the HIP device that is current at construction.
 
@@ -280,8 +294,8 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        C.piquant_hip_quantize_dynamic_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
-                                             (_C.c_size_t * n)(*numels), (_C.c_void_p * n)(*params_ptrs), n, round_mode.value)
+        C.piquant_hip_quantize_dynamic_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value, _size_array(numels),
+                                             _ptr_array(params_ptrs), n, round_mode.value)
 
     def dequantize_dp_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, params_ptrs, reduce_op: ReduceOp,
                                 _device_ptrs: bool = False) -> None:
@@ -291,18 +305,17 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        C.piquant_hip_dequantize_dp_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
-                                          (_C.c_size_t * n)(*numels), (_C.c_void_p * n)(*params_ptrs), n, reduce_op.value)
+        C.piquant_hip_dequantize_dp_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value, _size_array(numels),
+                                          _ptr_array(params_ptrs), n, reduce_op.value)
 
     def reduce_quantize_dynamic_ptr(self, ptr_acc: int, dtype_acc: DataType, ptrs_in, params_in, ptr_out: int, dtype_out: DataType, numel: int,
                                     params_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         """out = quantize(acc + sum_i dequantize(input i)) with parameters from that sum, left in ``params_ptr`` (include/piquant_hip.h,
         piquant_hip_reduce_quantize_dynamic); the inputs have type ``dtype_out``.  ``acc`` is unspecified afterwards."""
         assert dtype_acc.is_dequantized and dtype_out.is_quantized and len(ptrs_in) == len(params_in) and params_ptr != 0
-        n = len(ptrs_in)
         self.assume_device_pointers(_device_ptrs)
-        C.piquant_hip_reduce_quantize_dynamic(self._ctx, ptr_acc, dtype_acc.value, (_C.c_void_p * max(n, 1))(*ptrs_in), (_C.c_void_p * max(n, 1))(*params_in), n,
-                                              ptr_out, dtype_out.value, numel, params_ptr, round_mode.value)
+        C.piquant_hip_reduce_quantize_dynamic(self._ctx, ptr_acc, dtype_acc.value, _ptr_array(ptrs_in), _ptr_array(params_in), len(ptrs_in), ptr_out,
+                                              dtype_out.value, numel, params_ptr, round_mode.value)
 
     def dequantize_sum_ptr(self, ptrs_in, params_ptrs, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, reduce_op: ReduceOp,
                            _device_ptrs: bool = False) -> None:
@@ -313,9 +326,7 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        arr_in = (_C.c_void_p * n)(*ptrs_in)
-        arr_p = (_C.c_void_p * n)(*params_ptrs)
-        C.piquant_hip_dequantize_sum(self._ctx, arr_in, arr_p, n, dtype_in.value, ptr_out, dtype_out.value, numel, reduce_op.value)
+        C.piquant_hip_dequantize_sum(self._ctx, _ptr_array(ptrs_in), _ptr_array(params_ptrs), n, dtype_in.value, ptr_out, dtype_out.value, numel, reduce_op.value)
 
     def peer_alloc(self, nbytes: int, fine_grained: bool, fill_word: int = 0):
         """-> (device address, 64-byte IPC handle) of a fresh allocation other GPUs / processes of the node may map (include/piquant_hip.h)."""
@@ -446,9 +457,8 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        C.piquant_hip_quantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
-                                             (_C.c_size_t * n)(*numels), group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
-                                             1 if params_given else 0, round_mode.value)
+        C.piquant_hip_quantize_grouped_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value, _size_array(numels),
+                                             group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, 1 if params_given else 0, round_mode.value)
 
     def dequantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
                                      zero_points_ptrs, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
@@ -458,9 +468,8 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        C.piquant_hip_dequantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value,
-                                               (_C.c_size_t * n)(*numels), group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
-                                               reduce_op.value)
+        C.piquant_hip_dequantize_grouped_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value, _size_array(numels),
+                                               group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, reduce_op.value)
 
     def quantize_dequantize_grouped_ptr(self, ptr_in: int, dtype_in_out: DataType, ptr_out: int, quant_dtype: DataType, numel: int, group_size: int,
                                         scales_ptr: int, zero_points_ptr: int, params_given: bool, round_mode: RoundMode, reduce_op: ReduceOp,
@@ -487,11 +496,10 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        sc = None if scales_ptrs is None else (_C.c_void_p * n)(*scales_ptrs)
-        zp = None if zero_points_ptrs is None else (_C.c_void_p * n)(*zero_points_ptrs)
-        C.piquant_hip_quantize_dequantize_grouped_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in_out.value, (_C.c_void_p * n)(*ptrs_out),
-                                                        quant_dtype.value, (_C.c_size_t * n)(*numels), group_size, sc, zp, n, 1 if params_given else 0,
-                                                        round_mode.value, reduce_op.value)
+        sc = None if scales_ptrs is None else _ptr_array(scales_ptrs)
+        zp = None if zero_points_ptrs is None else _ptr_array(zero_points_ptrs)
+        C.piquant_hip_quantize_dequantize_grouped_batch(self._ctx, _ptr_array(ptrs_in), dtype_in_out.value, _ptr_array(ptrs_out), quant_dtype.value,
+                                                        _size_array(numels), group_size, sc, zp, n, 1 if params_given else 0, round_mode.value, reduce_op.value)
 
     def reduce_quantize_grouped_ptr(self, ptr_acc: int, dtype_acc: DataType, ptrs_in, scales_in, zero_points_in, ptr_out: int, dtype_out: DataType,
                                     numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
@@ -502,10 +510,8 @@ class Context:
         n = len(ptrs_in)
         assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
         self.assume_device_pointers(_device_ptrs)
-        m = max(n, 1)
-        C.piquant_hip_reduce_quantize_grouped(self._ctx, ptr_acc, dtype_acc.value, (_C.c_void_p * m)(*ptrs_in), (_C.c_void_p * m)(*scales_in),
-                                              (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
-                                              round_mode.value)
+        C.piquant_hip_reduce_quantize_grouped(self._ctx, ptr_acc, dtype_acc.value, _ptr_array(ptrs_in), _ptr_array(scales_in), _ptr_array(zero_points_in), n,
+                                              ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr, round_mode.value)
 
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
@@ -519,15 +525,9 @@ class Context:
         n = len(ptrs_in)
         assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
         self.assume_device_pointers(_device_ptrs)
-        m = max(n, 1)
-        if residual_dtype is not None:
-            C.piquant_hip_reduce_quantize_grouped_ef_mixed(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, residual_dtype.value, (_C.c_void_p * m)(*ptrs_in),
-                                                           (_C.c_void_p * m)(*scales_in), (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value,
-                                                           numel, group_size, scales_ptr, zero_points_ptr, round_mode.value)
-            return
-        C.piquant_hip_reduce_quantize_grouped_ef(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, (_C.c_void_p * m)(*ptrs_in), (_C.c_void_p * m)(*scales_in),
-                                                 (_C.c_void_p * m)(*zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
-                                                 zero_points_ptr, round_mode.value)
+        entry, residual_type = _ef_entry(C.piquant_hip_reduce_quantize_grouped_ef, C.piquant_hip_reduce_quantize_grouped_ef_mixed, residual_dtype)
+        entry(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, *residual_type, _ptr_array(ptrs_in), _ptr_array(scales_in), _ptr_array(zero_points_in), n,
+              ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr, round_mode.value)
 
     def quantize_grouped_ef_ptr(self, ptr_in: int, dtype_in: DataType, ptr_residual: int, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
                                 scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode, _device_ptrs: bool = False,
@@ -538,12 +538,9 @@ class Context:
         the widened tensor (``piquant_hip_quantize_grouped_ef_mixed``), still in one launch."""
         assert dtype_in.is_dequantized and dtype_out.is_quantized
         self.assume_device_pointers(_device_ptrs)
-        if residual_dtype is not None:
-            C.piquant_hip_quantize_grouped_ef_mixed(self._ctx, ptr_in, dtype_in.value, ptr_residual, residual_dtype.value, ptr_out, dtype_out.value, numel,
-                                                    group_size, scales_ptr, zero_points_ptr, round_mode.value)
-            return
-        C.piquant_hip_quantize_grouped_ef(self._ctx, ptr_in, dtype_in.value, ptr_residual, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
-                                          zero_points_ptr, round_mode.value)
+        entry, residual_type = _ef_entry(C.piquant_hip_quantize_grouped_ef, C.piquant_hip_quantize_grouped_ef_mixed, residual_dtype)
+        entry(self._ctx, ptr_in, dtype_in.value, ptr_residual, *residual_type, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+              round_mode.value)
 
     def quantize_grouped_ef_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_residual, ptrs_out, dtype_out: DataType, numels, group_size: int,
                                       scales_ptrs, zero_points_ptrs, round_mode: RoundMode, _device_ptrs: bool = False,
@@ -557,15 +554,9 @@ class Context:
         if n == 0:
             return
         self.assume_device_pointers(_device_ptrs)
-        if residual_dtype is not None:
-            C.piquant_hip_quantize_grouped_ef_mixed_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_residual),
-                                                          residual_dtype.value, (_C.c_void_p * n)(*ptrs_out), dtype_out.value, (_C.c_size_t * n)(*numels),
-                                                          group_size, (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n,
-                                                          round_mode.value)
-            return
-        C.piquant_hip_quantize_grouped_ef_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*ptrs_residual),
-                                                (_C.c_void_p * n)(*ptrs_out), dtype_out.value, (_C.c_size_t * n)(*numels), group_size,
-                                                (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*zero_points_ptrs), n, round_mode.value)
+        entry, residual_type = _ef_entry(C.piquant_hip_quantize_grouped_ef_batch, C.piquant_hip_quantize_grouped_ef_mixed_batch, residual_dtype)
+        entry(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_residual), *residual_type, _ptr_array(ptrs_out), dtype_out.value,
+              _size_array(numels), group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, round_mode.value)
 
     def compute_quant_params_dist_ptr(self, ptr: int, dtype: DataType, numel: int, target_quant_dtype: DataType, nccl_comm: int,
                                       _device_ptrs: bool = False) -> Tuple[float, int]:

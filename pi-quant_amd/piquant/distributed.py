@@ -16,7 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import Context, DataType, decode_minmax_keys, quant_params_from_minmax
-from .torch import _QUANT_TYPES, _ctx_for, torch_to_piquant_dtype
+from .torch import _QUANT_TYPES, _REDUCE_OPS, _ROUND_MODES, _ctx_for, _residual_dtype, torch_to_piquant_dtype
 
 
 _P2P_MAX_TIMEOUT_S = 4294.0   # the C ABI carries microseconds in 32 bits
@@ -436,9 +436,8 @@ class _DeviceOps:
 
     @staticmethod
     def _mode(round_mode: str):
-        from . import RoundMode
-
-        return RoundMode.NEAREST if round_mode == 'nearest' else RoundMode.STOCHASTIC
+        """``quantized_all_reduce`` hands its ``round_mode=`` down unchecked: as ever, whatever is not 'nearest' rounds stochastically."""
+        return _ROUND_MODES['nearest' if round_mode == 'nearest' else 'stochastic']
 
     def encode(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str) -> None:
         p = buf.data_ptr()
@@ -446,11 +445,9 @@ class _DeviceOps:
                                          self._mode(round_mode), _device_ptrs=True)
 
     def decode(self, buf: torch.Tensor, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str) -> None:
-        from . import ReduceOp
-
         p = buf.data_ptr()
         self._cx(out).dequantize_dp_ptr(p + _HEADER_BYTES, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype), out.numel(), p,
-                                        ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+                                        _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     def encode_batch(self, xs, bufs, qdtype: torch.dtype, round_mode: str) -> None:
         """encode(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks (each chunk its own parameters)."""
@@ -461,13 +458,11 @@ class _DeviceOps:
 
     def decode_batch(self, bufs, outs, qdtype: torch.dtype, reduce_op: str) -> None:
         """decode(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
-        from . import ReduceOp
-
         if bufs:
             ps = [b.data_ptr() for b in bufs]
             self._cx(outs[0]).dequantize_dp_batch_ptr([p + _HEADER_BYTES for p in ps], torch_to_piquant_dtype(qdtype), [o.data_ptr() for o in outs],
                                                       torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], ps,
-                                                      ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+                                                      _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     def reduce_encode(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str) -> None:
         """encode(acc + sum of the wire buffers) into ``buf`` as one call (``acc`` is scratch afterwards)."""
@@ -478,11 +473,9 @@ class _DeviceOps:
 
     def decode_sum(self, bufs, out: torch.Tensor, qdtype: torch.dtype) -> None:
         """out += sum of the wire buffers, one pass over ``out`` (same result as decode(..., 'add') buffer by buffer)."""
-        from . import ReduceOp
-
         ps = [b.data_ptr() for b in bufs]
         self._cx(out).dequantize_sum_ptr([p + _HEADER_BYTES for p in ps], ps, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype),
-                                         out.numel(), ReduceOp.ADD, _device_ptrs=True)
+                                         out.numel(), _REDUCE_OPS['add'], _device_ptrs=True)
 
     # ---- the grouped wire (grouped_wire_layout): per-group parameters in front of the packed bytes ----
     @staticmethod
@@ -498,11 +491,9 @@ class _DeviceOps:
                                          False, self._mode(round_mode), _device_ptrs=True)
 
     def decode_grouped(self, buf: torch.Tensor, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
-        from . import ReduceOp
-
         sc, zp, data = self._record(buf, out.numel(), qdtype, group_size)
         self._cx(out).dequantize_grouped_ptr(data, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype), out.numel(), group_size,
-                                             sc, zp, ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+                                             sc, zp, _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     def encode_batch_grouped(self, xs, bufs, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
@@ -512,18 +503,13 @@ class _DeviceOps:
                                                        torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
                                                        [r[1] for r in recs], False, self._mode(round_mode), _device_ptrs=True)
 
-    @staticmethod
-    def _residual_dtype(residual: torch.Tensor, x: torch.Tensor):
-        """``residual_dtype=`` of the ``*_ef*_ptr`` methods: None (the same-dtype symbol) unless the residual's dtype differs from the tensor's."""
-        return None if residual.dtype == x.dtype else torch_to_piquant_dtype(residual.dtype)
-
     def encode_grouped_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped(x + residual) with residual <- (x + residual) - what the record decodes to, one launch.  The residual's dtype goes down
         with it: float32 for a bfloat16 ``x`` is the float32 pipeline on the widened ``x``."""
         sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
         self._cx(x).quantize_grouped_ef_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), residual.data_ptr(), data, torch_to_piquant_dtype(qdtype),
                                             x.numel(), group_size, sc, zp, self._mode(round_mode), _device_ptrs=True,
-                                            residual_dtype=self._residual_dtype(residual, x))
+                                            residual_dtype=_residual_dtype(residual, x))
 
     def encode_batch_grouped_ef(self, xs, residuals, bufs, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped_ef(xs[i], residuals[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
@@ -532,17 +518,15 @@ class _DeviceOps:
             self._cx(xs[0]).quantize_grouped_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r.data_ptr() for r in residuals],
                                                           [r[2] for r in recs], torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size,
                                                           [r[0] for r in recs], [r[1] for r in recs], self._mode(round_mode), _device_ptrs=True,
-                                                          residual_dtype=self._residual_dtype(residuals[0], xs[0]))
+                                                          residual_dtype=_residual_dtype(residuals[0], xs[0]))
 
     def decode_batch_grouped(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
         """decode_grouped(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
-        from . import ReduceOp
-
         if bufs:
             recs = [self._record(b, o.numel(), qdtype, group_size) for b, o in zip(bufs, outs)]
             self._cx(outs[0]).dequantize_grouped_batch_ptr([r[2] for r in recs], torch_to_piquant_dtype(qdtype), [o.data_ptr() for o in outs],
                                                            torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], group_size, [r[0] for r in recs],
-                                                           [r[1] for r in recs], ReduceOp.ADD if reduce_op == 'add' else ReduceOp.SET, _device_ptrs=True)
+                                                           [r[1] for r in recs], _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     def reduce_encode_grouped(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped(acc + the wire buffers, added in order) into ``buf`` as one launch (``acc`` is scratch afterwards)."""
@@ -562,7 +546,7 @@ class _DeviceOps:
         sc, zp, data = self._record(buf, n, qdtype, group_size)
         self._cx(acc).reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[2] for r in recs],
                                                      [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp,
-                                                     self._mode(round_mode), _device_ptrs=True, residual_dtype=self._residual_dtype(residual, acc))
+                                                     self._mode(round_mode), _device_ptrs=True, residual_dtype=_residual_dtype(residual, acc))
 
 
 def _exchange(send: torch.Tensor, recv: torch.Tensor, nxt: int, prv: int, group) -> None:

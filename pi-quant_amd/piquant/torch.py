@@ -19,6 +19,7 @@ device='cuda')``) even though it implements hardly any operator on them -- ``pac
 """
 from __future__ import annotations
 
+from itertools import repeat
 from typing import Optional, Tuple
 
 import torch
@@ -174,6 +175,97 @@ def _numel_of(shape) -> int:
     return n
 
 
+# The blocks every additive entry point is made of.  The ORDER in which a function calls them is behaviour: it decides which fault is reported when
+# an argument list has several, and everything that can be checked on host tensors is checked before the "ROCm device tensor" rule.
+_NA = object()   # "this call has no such argument" (None is a value callers pass, and it is reported)
+
+
+def _check_modes(*, quant_dtype=_NA, float_dtype=_NA, round_mode=_NA, reduce_op=_NA, group_size=_NA) -> None:
+    """The mode arguments a call has, in the order every entry point reports them."""
+    if quant_dtype is not _NA and quant_dtype not in _QUANT_TYPES:
+        raise ValueError(f'{quant_dtype} is not a quantized dtype')
+    if float_dtype is not _NA and float_dtype not in _DEQUANT_TYPES:
+        raise ValueError(f'{float_dtype} is not a float dtype to dequantize into')
+    if round_mode is not _NA and round_mode not in _ROUND_MODES:
+        raise ValueError(f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
+    if reduce_op is not _NA and reduce_op not in _REDUCE_OPS:
+        raise ValueError(f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
+    if group_size is not _NA:
+        _check_group_size(group_size)
+
+
+def _packed_outs(outs, dtype: torch.dtype, like, device: torch.device, what: str = 'outs'):
+    """Quantized outputs of `dtype`, one per tensor of `like` and of its shape: given, so check; otherwise allocate."""
+    if outs is None:
+        return [torch.empty(t.shape, dtype=dtype, device=device) for t in like]
+    qdt = torch_to_piquant_dtype(dtype)
+    for i, (o, t) in enumerate(zip(outs, like)):
+        _check_packed_out(o, qdt, t.numel(), device, what if what == 'out' else f'{what}[{i}]')
+    return outs
+
+
+def _float_outs(outs, reduce_op: str, dtype: torch.dtype, shapes, numels, device: torch.device, what: str = 'outs'):
+    """Float outputs of `dtype`, one per shape: given, so check; otherwise allocate -- which ``reduce_op='add'`` cannot use, it accumulates."""
+    if outs is None:
+        if reduce_op == 'add':
+            raise ValueError(f"reduce_op='add' accumulates into {what}=; pass the accumulator tensor{'' if what == 'out' else 's'}")
+        return [torch.empty(shape, dtype=dtype, device=device) for shape in shapes]
+    for i, (o, n) in enumerate(zip(outs, numels)):
+        _check_float_out(o, dtype, n, device, what if what == 'out' else f'{what}[{i}]')
+    return outs
+
+
+def _group_params(scales, zero_points, numels, group_size: int, device: torch.device, what: str = 'scales and zero_points', shapes_checked: bool = False):
+    """Per-group parameters, one float32[ngroups] / uint8[ngroups] pair per tensor of `numels` elements: given, so check -- their placement alone if
+    shape and dtype were checked ahead of the device rule; otherwise allocate."""
+    if scales is None:
+        ngroups = [num_groups(n, group_size) for n in numels]
+        return [torch.empty(g, dtype=torch.float32, device=device) for g in ngroups], [torch.empty(g, dtype=torch.uint8, device=device) for g in ngroups]
+    for sc, zp, n in zip(scales, zero_points, numels):
+        if not shapes_checked:
+            _check_group_params(sc, zp, num_groups(n, group_size))
+        _require(sc.device == device and zp.device == device, f'{what} must live on {device}')
+    return scales, zero_points
+
+
+# The same for one tensor: lists of one, unwrapped.  (The list forms are the base: a None inside a given list is a fault of that list, not "allocate".)
+def _packed_out(out, dtype: torch.dtype, like: torch.Tensor, device: torch.device) -> torch.Tensor:
+    return _packed_outs(None if out is None else (out,), dtype, (like,), device, 'out')[0]
+
+
+def _float_out(out, reduce_op: str, dtype: torch.dtype, shape, numel: int, device: torch.device) -> torch.Tensor:
+    return _float_outs(None if out is None else (out,), reduce_op, dtype, (shape,), (numel,), device, 'out')[0]
+
+
+def _group_params_of(scales, zero_points, numel: int, group_size: int, device: torch.device, what: str = 'scales and zero_points', shapes_checked: bool = False):
+    sc, zp = _group_params(None if scales is None else (scales,), None if zero_points is None else (zero_points,), (numel,), group_size, device, what,
+                           shapes_checked)
+    return sc[0], zp[0]
+
+
+def _check_grouped_terms(tensors, scales, zero_points, dtype_in: DataType, numels, group_size: int, device: torch.device) -> None:
+    """Term i of a grouped reduce or batched dequantize: `numels[i]` packed elements with their own per-group parameters, all on `device`."""
+    for i, (t, sc, zp, n) in enumerate(zip(tensors, scales, zero_points, numels)):
+        _check_packed_in(t, dtype_in, n, device, f'tensors[{i}]')
+        _check_group_params(sc, zp, num_groups(n, group_size))
+        _require(sc.device == device and zp.device == device, f'scales[{i}] and zero_points[{i}] must live on {device}')
+
+
+def _check_dynamic_terms(tensors, params, dtype_in: DataType, numels, device: torch.device) -> None:
+    """Term i of a per-tensor reduce or batched dequantize: `numels[i]` packed elements with their device parameter record, all on `device`."""
+    for i, (t, p, n) in enumerate(zip(tensors, params, numels)):
+        _check_packed_in(t, dtype_in, n, device, f'tensors[{i}]')
+        _check_params(p, device, f'params[{i}]')
+
+
+def _contiguous(tensors):
+    return [t if t.is_contiguous() else t.contiguous() for t in tensors]
+
+
+def _ptrs(tensors):
+    return [t.data_ptr() for t in tensors]
+
+
 def compute_quant_params(tensor: torch.Tensor, *, dtype: torch.dtype, ctx: Optional[Context] = None) -> Tuple[float, int]:
     """(scale, zero_point) from the tensor's min/max (reference ``torch.py:53-67``)."""
     assert dtype in _QUANT_TYPES, f'Unsupported quantized dtype: {dtype}; choose from {[str(t) for t in _QUANT_TYPES]}'
@@ -300,16 +392,11 @@ def quantize_dequantize(
 ) -> torch.Tensor:
     """out (op)= dequantize(quantize(tensor)) in one pass over HBM -- the reference's C++-only
     ``context::quantize_dequantize_fused`` (``include/piquant.hpp:276-285``); ``out`` may be ``tensor`` (in place)."""
-    _require(quant_dtype in _QUANT_TYPES, f'{quant_dtype} is not a quantized dtype')
+    _check_modes(quant_dtype=quant_dtype)
     _check_float_input(tensor)
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
-    if out is None:
-        if reduce_op == 'add':
-            raise ValueError("reduce_op='add' accumulates into out=; pass the accumulator tensor")
-        out = torch.empty_like(tensor)
-    else:
-        _check_float_out(out, tensor.dtype, tensor.numel(), tensor.device)
+    out = _float_out(out, reduce_op, tensor.dtype, tensor.shape, tensor.numel(), tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.quantize_dequantize_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(quant_dtype),
                                 tensor.numel(), scale, zero_point, _ROUND_MODES[round_mode], _REDUCE_OPS[reduce_op], _device_ptrs=True)
@@ -333,7 +420,7 @@ def params_to_host(params: torch.Tensor) -> Tuple[float, int]:
 def compute_quant_params_device(tensor: torch.Tensor, *, dtype: torch.dtype, ctx: Optional[Context] = None,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Like ``compute_quant_params`` but asynchronous: the result is a 16-byte uint8 device tensor (the parameter record)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _check_modes(quant_dtype=dtype)
     _check_float_input(tensor)
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
@@ -351,17 +438,14 @@ def quantize_dynamic(tensor: torch.Tensor, *, dtype: torch.dtype, round_mode: st
     """``compute_quant_params`` + ``quantize`` in one asynchronous call, parameters computed and kept on the device.  Returns
     (quantized, parameter record).  A tensor that fits on the chip (up to ~113 MB on an MI355X) is read from HBM once, by a single
     kernel that keeps it in registers / LDS between the min/max pass and the quantization; larger ones take two launches (scan with the parameter epilogue, then quantize)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _check_modes(quant_dtype=dtype)
     _check_float_input(tensor)
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
     if params is None:
         params = torch.empty(PARAMS_NBYTES, dtype=torch.uint8, device=tensor.device)
     _check_params(params, tensor.device)
-    if out is None:
-        out = torch.empty(tensor.shape, dtype=dtype, device=tensor.device)
-    else:
-        _check_packed_out(out, torch_to_piquant_dtype(dtype), tensor.numel(), tensor.device)
+    out = _packed_out(out, dtype, tensor, tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.quantize_dynamic_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(dtype), tensor.numel(),
                              params.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
@@ -372,7 +456,7 @@ def dequantize_dynamic(tensor: torch.Tensor, params: torch.Tensor, *, dtype: tor
                        ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None,
                        shape=None) -> torch.Tensor:
     """``dequantize`` with (scale, zero_point) read from a device parameter record."""
-    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
+    _check_modes(float_dtype=dtype)
     _require(isinstance(tensor, torch.Tensor) and tensor.is_cuda, 'dequantize_dynamic needs a ROCm device tensor')
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
@@ -380,12 +464,7 @@ def dequantize_dynamic(tensor: torch.Tensor, params: torch.Tensor, *, dtype: tor
     numel = _numel_of(logical_shape)
     _check_packed_in(tensor, dtype_in, numel, tensor.device, 'tensor')
     _check_params(params, tensor.device)
-    if out is None:
-        if reduce_op == 'add':
-            raise ValueError("reduce_op='add' accumulates into out=; pass the accumulator tensor")
-        out = torch.empty(logical_shape, dtype=dtype, device=tensor.device)
-    else:
-        _check_float_out(out, dtype, numel, tensor.device)
+    out = _float_out(out, reduce_op, dtype, logical_shape, numel, tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.dequantize_dp_ptr(tensor.data_ptr(), dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, params.data_ptr(),
                           _REDUCE_OPS[reduce_op], _device_ptrs=True)
@@ -406,6 +485,10 @@ def _check_group_size(group_size) -> None:
              f'group_size must be a power of two in [32, 4096], got {group_size!r}')
 
 
+_GIVEN_PAIR = 'pass both scales and zero_points (given parameters) or neither (computed parameters)'
+_OUT_PAIR = 'pass both out_scales and out_zero_points or neither'
+
+
 def _check_group_params(scales, zero_points, ngroups: int) -> None:
     """Shape and dtype of the per-group parameters (device placement is checked against the tensor separately)."""
     _require(isinstance(scales, torch.Tensor) and scales.dtype == torch.float32 and scales.dim() == 1 and scales.numel() == ngroups and scales.is_contiguous(),
@@ -423,27 +506,17 @@ def quantize_grouped(tensor: torch.Tensor, *, dtype: torch.dtype, group_size: in
     parameters equal ``compute_quant_params`` of that slice and its bytes equal the position-independent quantize of the slice with them.
     Passing both ``scales`` and ``zero_points`` quantizes with those parameters instead of computing them.  One asynchronous launch on the
     current stream (``include/piquant_hip.h``, piquant_hip_quantize_grouped)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
-    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    _require((scales is None) == (zero_points is None), _GIVEN_PAIR)
     _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
-    ngroups = num_groups(tensor.numel(), group_size)
     given = scales is not None
     if given:
-        _check_group_params(scales, zero_points, ngroups)
+        _check_group_params(scales, zero_points, num_groups(tensor.numel(), group_size))
     _check_float_input(tensor)
-    if given:
-        _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
-    else:
-        scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
-        zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    scales, zero_points = _group_params_of(scales, zero_points, tensor.numel(), group_size, tensor.device, shapes_checked=True)
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
-    if out is None:
-        out = torch.empty(tensor.shape, dtype=dtype, device=tensor.device)
-    else:
-        _check_packed_out(out, torch_to_piquant_dtype(dtype), tensor.numel(), tensor.device)
+    out = _packed_out(out, dtype, tensor, tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.quantize_grouped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(dtype), tensor.numel(),
                              group_size, scales.data_ptr(), zero_points.data_ptr(), given, _ROUND_MODES[round_mode], _device_ptrs=True)
@@ -455,9 +528,7 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
                        quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
     """Inverse of ``quantize_grouped``: group g of the result (``reduce_op='set'``) or of ``out`` (``'add'``) is the dequantized group g with
     ``scales[g]`` / ``zero_points[g]``.  A raw uint8 buffer of packed bytes needs ``quant_dtype=`` and ``shape=``."""
-    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
-    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
-    _check_group_size(group_size)
+    _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
     _require(isinstance(tensor, torch.Tensor) and (tensor.dtype in _QUANT_TYPES or quant_dtype is not None), 'tensor must be a quantized tensor')
     dtype_in, logical_shape = _quant_meta(tensor, quant_dtype, shape)
     numel = _numel_of(logical_shape)
@@ -467,16 +538,12 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
     _check_packed_in(tensor, dtype_in, numel, tensor.device, 'tensor')
-    if out is None:
-        if reduce_op == 'add':
-            raise ValueError("reduce_op='add' accumulates into out=; pass the accumulator tensor")
-        out = torch.empty(logical_shape, dtype=dtype, device=tensor.device)
-    else:
-        _check_float_out(out, dtype, numel, tensor.device)
+    out = _float_out(out, reduce_op, dtype, logical_shape, numel, tensor.device)
     ctx = _ctx_for(tensor, ctx)
     ctx.dequantize_grouped_ptr(tensor.data_ptr(), dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, group_size, scales.data_ptr(),
                                zero_points.data_ptr(), _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return out
+
 
 def reduce_quantize_grouped(acc: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
                             ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
@@ -487,36 +554,34 @@ def reduce_quantize_grouped(acc: torch.Tensor, tensors, scales, zero_points, *, 
     ``dequantize_grouped(tensors[i], ..., reduce_op='add', out=acc)`` for every i in order followed by ``quantize_grouped(acc)``.  Returns
     (out, out_scales, out_zero_points) as ``quantize_grouped`` does; ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
     piquant_hip_reduce_quantize_grouped)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
+    return _reduce_quantize_grouped(acc, _NA, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points)
+
+
+def _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points):
+    """``reduce_quantize_grouped`` (``residual`` is ``_NA``) and ``reduce_quantize_grouped_ef``: the second checks the residual and makes the ``_ef`` call."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
     tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
     _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
              f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
+    if residual is not _NA:
+        _require(isinstance(acc, torch.Tensor) and acc.dtype in _DEQUANT_TYPES, 'acc must be a float32 or bfloat16 tensor')
+        _check_residual(residual, acc)
     _check_float_input(acc, 'acc')
     _require(acc.is_contiguous(), 'acc must be contiguous (it is the accumulator)')
-    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
     numel = acc.numel()
-    ngroups = num_groups(numel, group_size)
     qdt = torch_to_piquant_dtype(dtype)
-    for i, (t, sc, zp) in enumerate(zip(tensors, scales, zero_points)):
-        _check_packed_in(t, qdt, numel, acc.device, f'tensors[{i}]')
-        _check_group_params(sc, zp, ngroups)
-        _require(sc.device == acc.device and zp.device == acc.device, f'scales[{i}] and zero_points[{i}] must live on {acc.device}')
-    if out is None:
-        out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
-    else:
-        _check_packed_out(out, qdt, numel, acc.device)
-    if out_scales is None:
-        out_scales = torch.empty(ngroups, dtype=torch.float32, device=acc.device)
-        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=acc.device)
-    else:
-        _check_group_params(out_scales, out_zero_points, ngroups)
-        _require(out_scales.device == acc.device and out_zero_points.device == acc.device, f'out_scales and out_zero_points must live on {acc.device}')
+    _check_grouped_terms(tensors, scales, zero_points, qdt, repeat(numel), group_size, acc.device)
+    out = _packed_out(out, dtype, acc, acc.device)
+    out_scales, out_zero_points = _group_params_of(out_scales, out_zero_points, numel, group_size, acc.device, 'out_scales and out_zero_points')
     ctx = _ctx_for(acc, ctx)
-    ctx.reduce_quantize_grouped_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [t.data_ptr() for t in tensors], [sc.data_ptr() for sc in scales],
-                                    [zp.data_ptr() for zp in zero_points], out.data_ptr(), qdt, numel, group_size, out_scales.data_ptr(),
-                                    out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+    if residual is _NA:
+        ctx.reduce_quantize_grouped_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), _ptrs(tensors), _ptrs(scales), _ptrs(zero_points), out.data_ptr(), qdt,
+                                        numel, group_size, out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
+    else:
+        ctx.reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), _ptrs(tensors), _ptrs(scales),
+                                           _ptrs(zero_points), out.data_ptr(), qdt, numel, group_size, out_scales.data_ptr(), out_zero_points.data_ptr(),
+                                           _ROUND_MODES[round_mode], _device_ptrs=True, residual_dtype=_residual_dtype(residual, acc))
     return out, out_scales, out_zero_points
 
 
@@ -530,48 +595,48 @@ def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128
     """``quantize_grouped`` of several independent tensors (one dtype pair, group size and round mode) with one kernel launch per 16 tensors.
     Returns (outs, scales, zero_points) as lists; tensor i's entries equal ``quantize_grouped(tensors[i])`` (a stochastic batch draws one
     threshold).  Passing ``scales`` and ``zero_points`` (lists) quantizes with those parameters instead of computing them."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
-    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
+    return _quantize_grouped_batch(tensors, _NA, dtype, group_size, round_mode, ctx, outs, scales, zero_points, _GIVEN_PAIR, 'scales and zero_points')
+
+
+def _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, ctx, outs, scales, zero_points, pair_rule: str, what: str):
+    """``quantize_grouped_batch`` (``residuals`` is ``_NA``; ``scales`` / ``zero_points`` are given parameters) and ``quantize_grouped_ef_batch`` (they are
+    its ``out_scales`` / ``out_zero_points``): the second checks the residuals and makes the ``_ef`` call."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    _require((scales is None) == (zero_points is None), pair_rule)
     tensors = list(tensors)
+    lists = [tensors]
+    if residuals is not _NA:
+        residuals = list(residuals)
+        lists.append(residuals)
+    if outs is not None:
+        outs = list(outs)
+        lists.append(outs)
     given = scales is not None
-    lists = [tensors] + ([list(outs)] if outs is not None else []) + ([list(scales), list(zero_points)] if given else [])
+    if given:
+        scales, zero_points = list(scales), list(zero_points)
+        lists += [scales, zero_points]
     _check_batch_lists(*lists)
+    if residuals is not _NA:
+        for i, (t, r) in enumerate(zip(tensors, residuals)):
+            _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, f'tensors[{i}] must be a float32 or bfloat16 tensor')
+            _check_residual(r, t, f'residuals[{i}]')
+            _require(r.dtype == residuals[0].dtype, f'the residuals of a batch must share one dtype, got {residuals[0].dtype} and {r.dtype}')
     for i, t in enumerate(tensors):
         _check_float_input(t, f'tensors[{i}]')
         _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
     device = tensors[0].device
-    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
-    qdt = torch_to_piquant_dtype(dtype)
-    if given:
-        scales, zero_points = list(scales), list(zero_points)
-        for sc, zp, t in zip(scales, zero_points, tensors):
-            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
-            _require(sc.device == device and zp.device == device, f'scales and zero_points must live on {device}')
-    else:
-        scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
-        zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
-    if outs is None:
-        outs = [torch.empty(t.shape, dtype=dtype, device=device) for t in tensors]
-    else:
-        outs = list(outs)
-        for i, (o, t) in enumerate(zip(outs, tensors)):
-            _check_packed_out(o, qdt, t.numel(), device, f'outs[{i}]')
+    tensors = _contiguous(tensors)
+    numels = [t.numel() for t in tensors]
+    scales, zero_points = _group_params(scales, zero_points, numels, group_size, device, what)
+    outs = _packed_outs(outs, dtype, tensors, device)
     ctx = _ctx_for(tensors[0], ctx)
-    ctx.quantize_grouped_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [o.data_ptr() for o in outs], qdt,
-                                   [t.numel() for t in tensors], group_size, [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], given,
-                                   _ROUND_MODES[round_mode], _device_ptrs=True)
+    fdt, qdt, mode = torch_to_piquant_dtype(tensors[0].dtype), torch_to_piquant_dtype(dtype), _ROUND_MODES[round_mode]
+    if residuals is _NA:
+        ctx.quantize_grouped_batch_ptr(_ptrs(tensors), fdt, _ptrs(outs), qdt, numels, group_size, _ptrs(scales), _ptrs(zero_points), given, mode, _device_ptrs=True)
+    else:
+        ctx.quantize_grouped_ef_batch_ptr(_ptrs(tensors), fdt, _ptrs(residuals), _ptrs(outs), qdt, numels, group_size, _ptrs(scales), _ptrs(zero_points), mode,
+                                          _device_ptrs=True, residual_dtype=_residual_dtype(residuals[0], tensors[0]))
     return outs, scales, zero_points
-
-
-def _requant_grouped_checks(dtype_ok: bool, quant_dtype, group_size, round_mode, reduce_op, scales, zero_points) -> None:
-    _require(quant_dtype in _QUANT_TYPES, f'{quant_dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
-    _check_group_size(group_size)
-    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points (given parameters) or neither (computed parameters)')
-    _require(dtype_ok, 'tensor must be a float32 or bfloat16 tensor')
 
 
 def quantize_dequantize_grouped(tensor: torch.Tensor, *, quant_dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
@@ -583,26 +648,18 @@ def quantize_dequantize_grouped(tensor: torch.Tensor, *, quant_dtype: torch.dtyp
     ``zero_points`` given together mean "quantize with these per-group parameters"; otherwise they are computed (and only materialised when
     ``return_params``).  ``reduce_op='add'`` accumulates into ``out=``; ``out=tensor`` is in place, for both ops (``include/piquant_hip.h``,
     piquant_hip_quantize_dequantize_grouped)."""
-    _requant_grouped_checks(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, quant_dtype, group_size, round_mode, reduce_op, scales,
-                            zero_points)
-    ngroups = num_groups(tensor.numel(), group_size)
+    _check_modes(quant_dtype=quant_dtype, round_mode=round_mode, reduce_op=reduce_op, group_size=group_size)
+    _require((scales is None) == (zero_points is None), _GIVEN_PAIR)
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
     given = scales is not None
     if given:
-        _check_group_params(scales, zero_points, ngroups)
-    if out is None:
-        _require(reduce_op != 'add', "reduce_op='add' accumulates into out=; pass the accumulator tensor")
-    else:
-        _check_float_out(out, tensor.dtype, tensor.numel(), tensor.device)
+        _check_group_params(scales, zero_points, num_groups(tensor.numel(), group_size))
+    out = _float_out(out, reduce_op, tensor.dtype, tensor.shape, tensor.numel(), tensor.device)
     _check_float_input(tensor)
-    if given:
-        _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
-    elif return_params:
-        scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
-        zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    if given or return_params:
+        scales, zero_points = _group_params_of(scales, zero_points, tensor.numel(), group_size, tensor.device, shapes_checked=True)
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
-    if out is None:
-        out = torch.empty_like(tensor)
     ctx = _ctx_for(tensor, ctx)
     ctx.quantize_dequantize_grouped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(quant_dtype),
                                         tensor.numel(), group_size, 0 if scales is None else scales.data_ptr(),
@@ -618,38 +675,35 @@ def quantize_dequantize_grouped_batch(tensors, *, quant_dtype: torch.dtype, grou
     single call on it (a stochastic batch draws one threshold).  ``scales`` and ``zero_points`` (lists) given together quantize with those
     parameters; ``reduce_op='add'`` needs ``outs=``; ``outs[i]`` may be ``tensors[i]``."""
     tensors = list(tensors)
-    _requant_grouped_checks(all(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES for t in tensors), quant_dtype, group_size, round_mode, reduce_op,
-                            scales, zero_points)
+    _check_modes(quant_dtype=quant_dtype, round_mode=round_mode, reduce_op=reduce_op, group_size=group_size)
+    _require((scales is None) == (zero_points is None), _GIVEN_PAIR)
+    _require(all(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES for t in tensors), 'tensor must be a float32 or bfloat16 tensor')
     given = scales is not None
     _require(outs is not None or reduce_op != 'add', "reduce_op='add' accumulates into outs=; pass the accumulator tensors")
-    lists = [tensors] + ([list(outs)] if outs is not None else []) + ([list(scales), list(zero_points)] if given else [])
+    lists = [tensors]
+    if outs is not None:
+        outs = list(outs)
+        lists.append(outs)
+    if given:
+        scales, zero_points = list(scales), list(zero_points)
+        lists += [scales, zero_points]
     _check_batch_lists(*lists)
     _require(all(t.device == tensors[0].device and t.dtype == tensors[0].dtype for t in tensors), 'the tensors of a batch must share one device and one dtype')
     device = tensors[0].device
+    numels = [t.numel() for t in tensors]
     if given:
-        scales, zero_points = list(scales), list(zero_points)
-        for sc, zp, t in zip(scales, zero_points, tensors):
-            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
-    if outs is not None:
-        outs = list(outs)
-        for i, (o, t) in enumerate(zip(outs, tensors)):
-            _check_float_out(o, t.dtype, t.numel(), device, f'outs[{i}]')
+        for sc, zp, n in zip(scales, zero_points, numels):
+            _check_group_params(sc, zp, num_groups(n, group_size))
+    outs = _float_outs(outs, reduce_op, tensors[0].dtype, [t.shape for t in tensors], numels, device)
     for i, t in enumerate(tensors):
         _check_float_input(t, f'tensors[{i}]')
-    if given:
-        _require(all(sc.device == device and zp.device == device for sc, zp in zip(scales, zero_points)), f'scales and zero_points must live on {device}')
-    elif return_params:
-        scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
-        zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
-    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
-    if outs is None:
-        outs = [torch.empty_like(t) for t in tensors]
+    if given or return_params:
+        scales, zero_points = _group_params(scales, zero_points, numels, group_size, device, shapes_checked=True)
+    tensors = _contiguous(tensors)
     ctx = _ctx_for(tensors[0], ctx)
-    ctx.quantize_dequantize_grouped_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [o.data_ptr() for o in outs],
-                                              torch_to_piquant_dtype(quant_dtype), [t.numel() for t in tensors], group_size,
-                                              None if scales is None else [sc.data_ptr() for sc in scales],
-                                              None if zero_points is None else [zp.data_ptr() for zp in zero_points], given, _ROUND_MODES[round_mode],
-                                              _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    ctx.quantize_dequantize_grouped_batch_ptr(_ptrs(tensors), torch_to_piquant_dtype(tensors[0].dtype), _ptrs(outs), torch_to_piquant_dtype(quant_dtype), numels,
+                                              group_size, None if scales is None else _ptrs(scales), None if zero_points is None else _ptrs(zero_points), given,
+                                              _ROUND_MODES[round_mode], _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return (outs, scales, zero_points) if return_params else outs
 
 
@@ -682,30 +736,18 @@ def quantize_grouped_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: 
     A bfloat16 ``tensor`` also takes a float32 ``residual``: then ``y`` and the new residual are float32 and the call writes exactly what
     ``quantize_grouped_ef(tensor.float(), residual)`` writes, still in one launch -- the residual no longer loses up to 2^-9 |y| per rounding,
     as much as the half step of a uint8 wire (piquant_hip_quantize_grouped_ef_mixed).  No other pair of dtypes is accepted."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
-    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
     _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
     _check_residual(residual, tensor)
     _check_float_input(tensor)
-    ngroups = num_groups(tensor.numel(), group_size)
-    if out_scales is None:
-        out_scales = torch.empty(ngroups, dtype=torch.float32, device=tensor.device)
-        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
-    else:
-        _check_group_params(out_scales, out_zero_points, ngroups)
-        _require(out_scales.device == tensor.device and out_zero_points.device == tensor.device, f'out_scales and out_zero_points must live on {tensor.device}')
+    out_scales, out_zero_points = _group_params_of(out_scales, out_zero_points, tensor.numel(), group_size, tensor.device, 'out_scales and out_zero_points')
     if not tensor.is_contiguous():
         tensor = tensor.contiguous()
-    qdt = torch_to_piquant_dtype(dtype)
-    if out is None:
-        out = torch.empty(tensor.shape, dtype=dtype, device=tensor.device)
-    else:
-        _check_packed_out(out, qdt, tensor.numel(), tensor.device)
+    out = _packed_out(out, dtype, tensor, tensor.device)
     ctx = _ctx_for(tensor, ctx)
-    ctx.quantize_grouped_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), out.data_ptr(), qdt, tensor.numel(), group_size,
-                                out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True,
+    ctx.quantize_grouped_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), out.data_ptr(), torch_to_piquant_dtype(dtype),
+                                tensor.numel(), group_size, out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True,
                                 residual_dtype=_residual_dtype(residual, tensor))
     return out, out_scales, out_zero_points
 
@@ -723,40 +765,7 @@ def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensor
     ``reduce_quantize_grouped``.  Returns (out, out_scales, out_zero_points); ``acc`` is unspecified afterwards (``include/piquant_hip.h``,
     piquant_hip_reduce_quantize_grouped_ef).  A bfloat16 ``acc`` also takes a float32 ``residual``: the same two-call identity with the mixed
     ``quantize_grouped_ef(acc, residual)`` as its second call, in one launch like the others (``acc`` 8-byte aligned is enough for this pair)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
-    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
-    _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
-             f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
-    _require(isinstance(acc, torch.Tensor) and acc.dtype in _DEQUANT_TYPES, 'acc must be a float32 or bfloat16 tensor')
-    _check_residual(residual, acc)
-    _check_float_input(acc, 'acc')
-    _require(acc.is_contiguous(), 'acc must be contiguous (it is the accumulator)')
-    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
-    numel = acc.numel()
-    ngroups = num_groups(numel, group_size)
-    qdt = torch_to_piquant_dtype(dtype)
-    for i, (t, sc, zp) in enumerate(zip(tensors, scales, zero_points)):
-        _check_packed_in(t, qdt, numel, acc.device, f'tensors[{i}]')
-        _check_group_params(sc, zp, ngroups)
-        _require(sc.device == acc.device and zp.device == acc.device, f'scales[{i}] and zero_points[{i}] must live on {acc.device}')
-    if out is None:
-        out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
-    else:
-        _check_packed_out(out, qdt, numel, acc.device)
-    if out_scales is None:
-        out_scales = torch.empty(ngroups, dtype=torch.float32, device=acc.device)
-        out_zero_points = torch.empty(ngroups, dtype=torch.uint8, device=acc.device)
-    else:
-        _check_group_params(out_scales, out_zero_points, ngroups)
-        _require(out_scales.device == acc.device and out_zero_points.device == acc.device, f'out_scales and out_zero_points must live on {acc.device}')
-    ctx = _ctx_for(acc, ctx)
-    ctx.reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [t.data_ptr() for t in tensors],
-                                       [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], out.data_ptr(), qdt, numel, group_size,
-                                       out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True,
-                                       residual_dtype=_residual_dtype(residual, acc))
-    return out, out_scales, out_zero_points
+    return _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points)
 
 
 def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
@@ -765,57 +774,20 @@ def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_s
     per 16 pairs.  Returns (outs, scales, zero_points) as lists; pair i's entries and its updated residual equal
     ``quantize_grouped_ef(tensors[i], residuals[i])`` (a stochastic batch draws one threshold).  The residuals of a batch share one dtype: the
     tensors', or float32 for bfloat16 tensors."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
-    _require(round_mode in _ROUND_MODES, f'round_mode must be one of {sorted(_ROUND_MODES)}, got {round_mode!r}')
-    _check_group_size(group_size)
-    _require((out_scales is None) == (out_zero_points is None), 'pass both out_scales and out_zero_points or neither')
-    tensors, residuals = list(tensors), list(residuals)
-    lists = [tensors, residuals] + ([list(outs)] if outs is not None else []) + ([list(out_scales), list(out_zero_points)] if out_scales is not None else [])
-    _check_batch_lists(*lists)
-    for i, (t, r) in enumerate(zip(tensors, residuals)):
-        _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, f'tensors[{i}] must be a float32 or bfloat16 tensor')
-        _check_residual(r, t, f'residuals[{i}]')
-        _require(r.dtype == residuals[0].dtype, f'the residuals of a batch must share one dtype, got {residuals[0].dtype} and {r.dtype}')
-    for i, t in enumerate(tensors):
-        _check_float_input(t, f'tensors[{i}]')
-        _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
-    device = tensors[0].device
-    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
-    qdt = torch_to_piquant_dtype(dtype)
-    if out_scales is None:
-        out_scales = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.float32, device=device) for t in tensors]
-        out_zero_points = [torch.empty(num_groups(t.numel(), group_size), dtype=torch.uint8, device=device) for t in tensors]
-    else:
-        out_scales, out_zero_points = list(out_scales), list(out_zero_points)
-        for sc, zp, t in zip(out_scales, out_zero_points, tensors):
-            _check_group_params(sc, zp, num_groups(t.numel(), group_size))
-            _require(sc.device == device and zp.device == device, f'out_scales and out_zero_points must live on {device}')
-    if outs is None:
-        outs = [torch.empty(t.shape, dtype=dtype, device=device) for t in tensors]
-    else:
-        outs = list(outs)
-        for i, (o, t) in enumerate(zip(outs, tensors)):
-            _check_packed_out(o, qdt, t.numel(), device, f'outs[{i}]')
-    ctx = _ctx_for(tensors[0], ctx)
-    ctx.quantize_grouped_ef_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(tensors[0].dtype), [r.data_ptr() for r in residuals],
-                                      [o.data_ptr() for o in outs], qdt, [t.numel() for t in tensors], group_size, [sc.data_ptr() for sc in out_scales],
-                                      [zp.data_ptr() for zp in out_zero_points], _ROUND_MODES[round_mode], _device_ptrs=True,
-                                      residual_dtype=_residual_dtype(residuals[0], tensors[0]))
-    return outs, out_scales, out_zero_points
+    return _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, ctx, outs, out_scales, out_zero_points, _OUT_PAIR,
+                                   'out_scales and out_zero_points')
 
 
 def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, reduce_op: str = 'set', ctx: Optional[Context] = None,
                              outs=None, quant_dtype: Optional[torch.dtype] = None, shapes=None):
     """``dequantize_grouped`` of several independent tensors with one kernel launch per 16 tensors; returns the list of outputs.  Raw uint8
     buffers of packed bytes need ``quant_dtype=`` and ``shapes=`` (one shape per tensor); ``reduce_op='add'`` accumulates into ``outs``."""
-    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
-    _require(reduce_op in _REDUCE_OPS, f'reduce_op must be one of {sorted(_REDUCE_OPS)}, got {reduce_op!r}')
-    _check_group_size(group_size)
+    _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
     tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
-    lists = [tensors, scales, zero_points] + ([list(outs)] if outs is not None else []) + ([list(shapes)] if shapes is not None else [])
+    outs = None if outs is None else list(outs)
+    lists = [tensors, scales, zero_points] + ([outs] if outs is not None else []) + ([list(shapes)] if shapes is not None else [])
     _check_batch_lists(*lists)
-    if reduce_op == 'add':
-        _require(outs is not None, "reduce_op='add' accumulates into outs=; pass the accumulator tensors")
+    _require(outs is not None or reduce_op != 'add', "reduce_op='add' accumulates into outs=; pass the accumulator tensors")
     metas = []
     for i, t in enumerate(tensors):
         _require(isinstance(t, torch.Tensor) and (t.dtype in _QUANT_TYPES or quant_dtype is not None), f'tensors[{i}] must be a quantized tensor')
@@ -823,22 +795,13 @@ def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype
         metas.append(_quant_meta(t, quant_dtype, shapes[i] if shapes is not None else None))
     device = tensors[0].device
     _require(all(t.device == device for t in tensors) and all(m[0] == metas[0][0] for m in metas), 'the tensors of a batch must share one device and one dtype')
-    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    tensors = _contiguous(tensors)
     numels = [_numel_of(shape) for _, shape in metas]
-    for i, (t, sc, zp, (dt_in, _), n) in enumerate(zip(tensors, scales, zero_points, metas, numels)):
-        _check_packed_in(t, dt_in, n, device, f'tensors[{i}]')
-        _check_group_params(sc, zp, num_groups(n, group_size))
-        _require(sc.device == device and zp.device == device, f'scales and zero_points must live on {device}')
-    if outs is None:
-        outs = [torch.empty(shape, dtype=dtype, device=device) for _, shape in metas]
-    else:
-        outs = list(outs)
-        for i, (o, n) in enumerate(zip(outs, numels)):
-            _check_float_out(o, dtype, n, device, f'outs[{i}]')
+    _check_grouped_terms(tensors, scales, zero_points, metas[0][0], numels, group_size, device)
+    outs = _float_outs(outs, reduce_op, dtype, [shape for _, shape in metas], numels, device)
     ctx = _ctx_for(tensors[0], ctx)
-    ctx.dequantize_grouped_batch_ptr([t.data_ptr() for t in tensors], metas[0][0], [o.data_ptr() for o in outs], torch_to_piquant_dtype(dtype), numels,
-                                     group_size, [sc.data_ptr() for sc in scales], [zp.data_ptr() for zp in zero_points], _REDUCE_OPS[reduce_op],
-                                     _device_ptrs=True)
+    ctx.dequantize_grouped_batch_ptr(_ptrs(tensors), metas[0][0], _ptrs(outs), torch_to_piquant_dtype(dtype), numels, group_size, _ptrs(scales),
+                                     _ptrs(zero_points), _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return outs
 
 
@@ -847,37 +810,30 @@ def dequantize_sum(tensors, params, *, dtype: torch.dtype, reduce_op: str = 'set
     """out (op)= sum_i dequantize(tensors[i]) with (scale, zero_point) of input i read from the device record ``params[i]``: one pass
     over the accumulator instead of ``len(tensors)``; the result equals ``dequantize_dynamic`` applied in order (first with
     ``reduce_op``, the rest with 'add') bit for bit.  The reduction step of ``piquant.distributed.quantized_all_reduce``."""
-    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
+    _check_modes(float_dtype=dtype)
     _require(len(tensors) == len(params) and len(tensors) > 0, 'dequantize_sum needs as many parameter records as tensors, and at least one')
     first = tensors[0]
     _require(isinstance(first, torch.Tensor) and first.is_cuda, 'dequantize_sum needs ROCm device tensors')
     dtype_in, logical_shape = _quant_meta(first, quant_dtype, shape)
     numel = _numel_of(logical_shape)
-    for i, (t, p) in enumerate(zip(tensors, params)):
-        _check_packed_in(t, dtype_in, numel, first.device, f'tensors[{i}]')
-        _check_params(p, first.device, f'params[{i}]')
-    if out is None:
-        if reduce_op == 'add':
-            raise ValueError("reduce_op='add' accumulates into out=; pass the accumulator tensor")
-        out = torch.empty(logical_shape, dtype=dtype, device=first.device)
-    else:
-        _check_float_out(out, dtype, numel, first.device)
+    _check_dynamic_terms(tensors, params, dtype_in, repeat(numel), first.device)
+    out = _float_out(out, reduce_op, dtype, logical_shape, numel, first.device)
     ctx = _ctx_for(first, ctx)
-    ctx.dequantize_sum_ptr([t.data_ptr() for t in tensors], [p.data_ptr() for p in params], dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype),
-                           numel, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    ctx.dequantize_sum_ptr(_ptrs(tensors), _ptrs(params), dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, _REDUCE_OPS[reduce_op],
+                           _device_ptrs=True)
     return out
 
 
 def quantize_dynamic_batch(tensors, *, dtype: torch.dtype, round_mode: str = 'nearest', ctx: Optional[Context] = None, outs=None, params=None):
     """``quantize_dynamic`` for a list of independent tensors of one float dtype: each gets its own (scale, zero_point) and record,
     up to 16 of them are processed by ONE kernel launch.  Returns (list of quantized tensors, list of parameter records)."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _check_modes(quant_dtype=dtype)
     _require(len(tensors) > 0, 'quantize_dynamic_batch needs at least one tensor')
     fdt = tensors[0].dtype
     for i, t in enumerate(tensors):
         _check_float_input(t, f'tensors[{i}]')
         _require(t.dtype == fdt and t.device == tensors[0].device, 'all tensors of a batch share one float dtype and one device')
-    tensors = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    tensors = _contiguous(tensors)
     if outs is None:
         outs = [torch.empty(t.shape, dtype=dtype, device=t.device) for t in tensors]
     if params is None:
@@ -889,8 +845,8 @@ def quantize_dynamic_batch(tensors, *, dtype: torch.dtype, round_mode: str = 'ne
         _check_packed_out(o, qdt, t.numel(), t.device, f'outs[{i}]')
         _check_params(p, t.device, f'params[{i}]')
     ctx = _ctx_for(tensors[0], ctx)
-    ctx.quantize_dynamic_batch_ptr([t.data_ptr() for t in tensors], torch_to_piquant_dtype(fdt), [o.data_ptr() for o in outs], torch_to_piquant_dtype(dtype),
-                                   [t.numel() for t in tensors], [p.data_ptr() for p in params], _ROUND_MODES[round_mode], _device_ptrs=True)
+    ctx.quantize_dynamic_batch_ptr(_ptrs(tensors), torch_to_piquant_dtype(fdt), _ptrs(outs), qdt, [t.numel() for t in tensors], _ptrs(params), _ROUND_MODES[round_mode],
+                                   _device_ptrs=True)
     return outs, params
 
 
@@ -898,7 +854,7 @@ def dequantize_dynamic_batch(tensors, params, *, dtype: torch.dtype, reduce_op: 
                              quant_dtype: Optional[torch.dtype] = None, shapes=None):
     """``dequantize_dynamic`` for a list of independent quantized tensors (raw uint8 buffers with ``quant_dtype=`` and ``shapes=``, or
     quantized torch tensors) in one launch per 16; ``outs`` are required for ``reduce_op='add'``."""
-    _require(dtype in _DEQUANT_TYPES, f'{dtype} is not a float dtype to dequantize into')
+    _check_modes(float_dtype=dtype)
     _require(len(tensors) == len(params) and len(tensors) > 0, 'dequantize_dynamic_batch needs as many parameter records as tensors, and at least one')
     _require(all(isinstance(t, torch.Tensor) and t.is_cuda for t in tensors), 'dequantize_dynamic_batch needs ROCm device tensors')
     metas = [_quant_meta(t, quant_dtype, None if shapes is None else shapes[i]) for i, t in enumerate(tensors)]
@@ -906,19 +862,12 @@ def dequantize_dynamic_batch(tensors, params, *, dtype: torch.dtype, reduce_op: 
     _require(all(m[0] == dtype_in for m in metas), 'all tensors of a batch share one quantized dtype')
     numels = [_numel_of(shp) for _dt, shp in metas]
     device = tensors[0].device
-    for i, (t, p, n) in enumerate(zip(tensors, params, numels)):
-        _check_packed_in(t, dtype_in, n, device, f'tensors[{i}]')
-        _check_params(p, device, f'params[{i}]')
-    if outs is None:
-        if reduce_op == 'add':
-            raise ValueError("reduce_op='add' accumulates into outs=; pass the accumulator tensors")
-        outs = [torch.empty(m[1], dtype=dtype, device=t.device) for m, t in zip(metas, tensors)]
-    _require(len(outs) == len(tensors), 'outs= must have one entry per tensor')
-    for i, (o, n) in enumerate(zip(outs, numels)):
-        _check_float_out(o, dtype, n, device, f'outs[{i}]')
+    _check_dynamic_terms(tensors, params, dtype_in, numels, device)
+    _require(outs is None or len(outs) == len(tensors), 'outs= must have one entry per tensor')
+    outs = _float_outs(outs, reduce_op, dtype, [shape for _, shape in metas], numels, device)
     ctx = _ctx_for(tensors[0], ctx)
-    ctx.dequantize_dp_batch_ptr([t.data_ptr() for t in tensors], dtype_in, [o.data_ptr() for o in outs], torch_to_piquant_dtype(dtype), numels,
-                                [p.data_ptr() for p in params], _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    ctx.dequantize_dp_batch_ptr(_ptrs(tensors), dtype_in, _ptrs(outs), torch_to_piquant_dtype(dtype), numels, _ptrs(params), _REDUCE_OPS[reduce_op],
+                                _device_ptrs=True)
     return outs
 
 
@@ -927,23 +876,17 @@ def reduce_quantize_dynamic(acc: torch.Tensor, tensors, params, *, dtype: torch.
     """(quantize(acc + sum_i dequantize(tensors[i])), record): the owner's step of a mesh all-reduce as one call -- one kernel launch
     that never writes the sum to memory when it stays on chip.  ``tensors`` are raw uint8 buffers of packed ``dtype`` values with
     ``acc.numel()`` elements each, ``params`` their device records.  The contents of ``acc`` afterwards are unspecified."""
-    _require(dtype in _QUANT_TYPES, f'{dtype} is not a quantized dtype')
+    _check_modes(quant_dtype=dtype)
     _check_float_input(acc, 'acc')
     _require(acc.is_contiguous(), 'acc must be contiguous')
     _require(len(tensors) == len(params), 'reduce_quantize_dynamic needs as many parameter records as tensors')
     qdt = torch_to_piquant_dtype(dtype)
-    for i, (t, p) in enumerate(zip(tensors, params)):
-        _check_packed_in(t, qdt, acc.numel(), acc.device, f'tensors[{i}]')
-        _check_params(p, acc.device, f'params[{i}]')
-    if out is None:
-        out = torch.empty(acc.shape, dtype=dtype, device=acc.device)
-    else:
-        _check_packed_out(out, qdt, acc.numel(), acc.device)
+    _check_dynamic_terms(tensors, params, qdt, repeat(acc.numel()), acc.device)
+    out = _packed_out(out, dtype, acc, acc.device)
     if out_params is None:
         out_params = torch.empty(PARAMS_NBYTES, dtype=torch.uint8, device=acc.device)
     _check_params(out_params, acc.device, 'out_params')
     ctx = _ctx_for(acc, ctx)
-    ctx.reduce_quantize_dynamic_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [t.data_ptr() for t in tensors], [p.data_ptr() for p in params],
-                                    out.data_ptr(), torch_to_piquant_dtype(dtype), acc.numel(), out_params.data_ptr(), _ROUND_MODES[round_mode],
-                                    _device_ptrs=True)
+    ctx.reduce_quantize_dynamic_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), _ptrs(tensors), _ptrs(params), out.data_ptr(), qdt, acc.numel(),
+                                    out_params.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
     return out, out_params

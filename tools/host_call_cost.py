@@ -54,6 +54,18 @@ for n in (4096, 3_408_000):
             r["piquant.torch.quantize(out=)"] = timed(lambda i: pt.quantize(xs[i % sets], scale=0.0078431377, zero_point=128, dtype=torch.uint8, ctx=ctx, out=qs[i % sets]))
             r["piquant.torch.dequantize(out=)"] = timed(lambda i: pt.dequantize(qs[i % sets], scale=0.0078431377, zero_point=128, dtype=torch.float32, ctx=ctx, out=xs[i % sets]))
             r["piquant.torch.quantize_dynamic(out=, params=)"] = timed(lambda i: pt.quantize_dynamic(xs[i % sets], dtype=torch.uint8, ctx=ctx, out=qs[i % sets], params=rec))
+            # the group-wise wrappers, every buffer supplied (group size 128; one and seven terms: the ring's and the 8-way mesh's reduce)
+            q8, sc, zp = pt.quantize_grouped(xs[0], dtype=torch.uint8, group_size=128, ctx=ctx)
+            osc, ozp, res0 = torch.empty_like(sc), torch.empty_like(zp), torch.zeros_like(xs[0])
+            kw = dict(dtype=torch.uint8, group_size=128, ctx=ctx)
+            r["piquant.torch.quantize_grouped"] = timed(lambda i: pt.quantize_grouped(xs[i % sets], out=qs[i % sets], scales=sc, zero_points=zp, **kw))
+            r["piquant.torch.dequantize_grouped"] = timed(lambda i: pt.dequantize_grouped(q8, sc, zp, dtype=torch.float32, group_size=128, ctx=ctx, out=xs[i % sets]))
+            r["piquant.torch.quantize_grouped_ef"] = timed(lambda i: pt.quantize_grouped_ef(xs[i % sets], res0, out=qs[i % sets], out_scales=osc, out_zero_points=ozp, **kw))
+            for k in (1, 7):
+                r[f"piquant.torch.reduce_quantize_grouped, {k} terms"] = timed(lambda i: pt.reduce_quantize_grouped(
+                    xs[i % sets], [q8] * k, [sc] * k, [zp] * k, out=qs[i % sets], out_scales=osc, out_zero_points=ozp, **kw))
+            r["piquant.torch.quantize_grouped_batch of 16"] = timed(lambda i: pt.quantize_grouped_batch(
+                xs[:16], outs=qs[:16], scales=[sc] * 16, zero_points=[zp] * 16, **kw))
             ctx.set_stream(s.cuda_stream)
             ctx.set_blocking(False)
         g = torch.cuda.CUDAGraph()
