@@ -36,8 +36,9 @@ def O(oracle_mod):
     return oracle_mod
 
 
-# block tile = 4096 (f32) / 8192 (bf16) elements for quantize; boundaries around them, odd and ragged sizes
-SIZES = [1, 2, 3, 5, 63, 64, 65, 1000, 4095, 4096, 4097, 8191, 8192, 8193, 12289, 65536 + 17, 1_000_003]
+# quantize tiles are 512 or 1024 elements (64- or 128-thread blocks, two 16-byte vectors per lane: csrc/tuning.hpp); 1024, 4096 and 8192 elements are
+# dequantize's tiles.  Boundaries around all of them, odd and ragged sizes
+SIZES = [1, 2, 3, 5, 63, 64, 65, 511, 512, 513, 1000, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, 12289, 65536 + 17, 1_000_003]
 
 
 # ---------------------------------------------------------------------------------------------------
