@@ -11,6 +11,7 @@ import oracle as O
 from ef_model import ef_step, widen
 
 
-def ef_f32r_step(x_bf16, r_f32, qd, G, round_mode=O.NEAREST, threshold=0.0):
-    """-> (packed bytes, scales, zero points, new float32 residual, y, d), y and d float32; x_bf16 and r_f32 are not modified."""
-    return ef_step(widen(x_bf16, O.BF16), r_f32, O.F32, qd, G, round_mode, threshold)
+def ef_f32r_step(x_bf16, r_f32, qd, G, round_mode=O.NEAREST, threshold=0.0, quantize=None):
+    """-> (packed bytes, scales, zero points, new float32 residual, y, d), y and d float32; x_bf16 and r_f32 are not modified.  quantize: as in
+    tests/ef_model.py's ef_step."""
+    return ef_step(widen(x_bf16, O.BF16), r_f32, O.F32, qd, G, round_mode, threshold, quantize)

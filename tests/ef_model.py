@@ -35,11 +35,12 @@ def sub_t(a, b, dt):
         return narrow(widen(a, dt) - widen(b, dt), dt)
 
 
-def ef_step(x, r, dt, qd, G, round_mode=O.NEAREST, threshold=0.0):
-    """-> (packed bytes, scales, zero points, new residual, y, d); x and r are not modified."""
+def ef_step(x, r, dt, qd, G, round_mode=O.NEAREST, threshold=0.0, quantize=None):
+    """-> (packed bytes, scales, zero points, new residual, y, d); x and r are not modified.  quantize: (y, scales, zero points) -> packed bytes
+    that takes the place of step 2's rounding (tests/per_element_model.py: per-element thresholds); the parameters stay the computed ones."""
     y = add_t(x, r, dt)
     s, z = group_params_all(widen(y, dt), G, qd)
-    q, _, _ = quantize_grouped(y, dt, qd, G, round_mode, threshold, params=(s, z))
+    q = quantize_grouped(y, dt, qd, G, round_mode, threshold, params=(s, z))[0] if quantize is None else quantize(y, s, z)
     d = dequantize_grouped(q, qd, dt, y.size, G, s, z)
     return q, s, z, sub_t(y, d, dt), y, d
 

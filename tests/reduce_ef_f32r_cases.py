@@ -17,7 +17,7 @@ import numpy as np
 import oracle as O
 from ef_f32r_model import ef_f32r_step
 from ef_model import widen
-from grouped_model import PACK, dequantize_grouped, group_params_all
+from grouped_model import PACK, dequantize_grouped
 
 BF16 = O.BF16
 BITS = {O.UINT8: 8, O.UINT4: 4, O.UINT2: 2}
@@ -67,19 +67,6 @@ def add_terms(acc, terms, qd, G):
 def reduce_ef_f32r_model(acc, r, terms, qd, G, round_mode=O.NEAREST, threshold=0.0):
     """reduce_ef_f32r_step (tests/grouped_ef_f32r_sim.py) with the rounding mode passed on -> (packed bytes, scales, zero points, new residual)"""
     return ef_f32r_step(add_terms(acc, terms, qd, G), r, qd, G, round_mode, threshold)[:4]
-
-
-def reduce_ef_f32r_per_element_model(acc, r, terms, qd, G, seed, index_base):
-    """the same with per-element thresholds: element i of the tensor draws the threshold of index_base + i"""
-    a = add_terms(acc, terms, qd, G)
-    with np.errstate(invalid="ignore", over="ignore"):
-        y = widen(a, BF16) + r
-    s, z = group_params_all(y, G, qd)
-    q = np.concatenate([O.quantize_per_element(y[b: b + G], O.F32, qd, float(s[g]), int(z[g]), seed, index_base + b)
-                        for g, b in enumerate(range(0, y.size, G))])
-    d = dequantize_grouped(q, qd, O.F32, y.size, G, s, z)
-    with np.errstate(invalid="ignore", over="ignore"):
-        return q, s, z, y - d
 
 
 def float32_sum_variant(acc, r, terms, qd, G):

@@ -18,7 +18,8 @@ import grouped_edge_cases as E
 import oracle as O
 from ef_model import EPS
 from grouped_ef_f32r_sim import reduce_ef_f32r_step
-from reduce_ef_f32r_cases import TIE_ORDERS, reduce_ef_f32r_model, reduce_ef_f32r_per_element_model, tie_case
+from per_element_model import reduce_ef_f32r_per_element_model
+from reduce_ef_f32r_cases import TIE_ORDERS, reduce_ef_f32r_model, tie_case
 from test_gpu_grouped_ef_f32r import BITS, GROUP_SIZES, GUARD, QDS, QDT, assert_residual_equal, chunk_elems, make_input
 
 pytestmark = pytest.mark.gpu
