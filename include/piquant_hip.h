@@ -203,6 +203,27 @@ PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, 
                                                         const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
                                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
                                                         piquant_round_mode_t mode);
+/* Grouped dequantize-sum: out (op)= dequantize_grouped(inputs[0]) + ... + dequantize_grouped(inputs[count - 1]) in ONE pass over out -- the
+ * group-wise piquant_hip_dequantize_sum, and piquant_hip_reduce_quantize_grouped's sum stored instead of re-quantized: the owner's step of a grouped
+ * reduce-scatter.  Term i is a packed tensor of numel elements of dtype_in with its own per-group parameters input_scales[i] /
+ * input_zero_points[i] (one group_size for all).  The call writes to out exactly the bytes that this composition of public calls writes:
+ *   ADD: piquant_hip_dequantize_grouped(inputs[i], ..., out, ..., PIQUANT_REDUCE_OP_ADD) for i = 0 .. count - 1 in order;
+ *   SET: that call with PIQUANT_REDUCE_OP_SET for i = 0, then with PIQUANT_REDUCE_OP_ADD for i = 1 .. count - 1.
+ * The running sum is rounded to dtype_out after every term: float32 with a separately rounded addition per term; bfloat16 with each term's
+ * float32 sum rounded to bfloat16 before the next term is added (SET: the first term rounded once, then the second added).  Every dequantized
+ * value is formed in the pair's own dequantize form.  All six dtype pairs, all eight group sizes.  SET never reads out.  NaN payloads are not
+ * specified.  count >= 1 is required: count == 0 aborts like a NULL argument.  numel == 0 is a no-op.
+ * out and every term's packed bytes 16-byte aligned: ONE launch for up to 16 terms (no scan, no atomics, no grid barrier; the sum stays in
+ * registers: with seven uint8 terms into float32, 15 bytes of memory traffic per element against the composition's 63); more than 16 terms run as
+ * successive launches of up to 16 in order, the first with the call's op and the others ADD (the same bytes).  With anything misaligned the
+ * composition itself runs through the guarded grouped dequantize, count launches.  An out that is not aligned to its element aborts.
+ * Nothing at or past the tensor's end is read or written in any buffer; out must not overlap a term.  Device (or pinned) buffers only;
+ * stream-ordered on the context's stream, always behind the previous call whatever piquant_hip_set_independent_calls says; no host
+ * synchronisation, no allocation on the device (hipGraph-capturable). */
+PIQUANT_EXPORT void piquant_hip_dequantize_sum_grouped(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                       const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count,
+                                                       void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, piquant_reduce_op_t op);
+
 /* piquant_hip_reduce_quantize_grouped with error feedback (piquant_hip_quantize_grouped_ef below) on the re-quantization: the owner's step of a
  * grouped mesh all-reduce and every hop of a grouped ring, compensated.  T is dtype_acc (float32 or bfloat16); `residual` has type T and numel
  * elements and is read AND written.  The call writes exactly the bytes that this composition of two public calls writes to out, scales,

@@ -371,6 +371,47 @@ void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piqu
                             group_size, scales, zero_points, mode);
 }
 
+// out (op)= the terms, in order.  Everything 16-byte aligned: one launch per kGroupedReduceMaxInputs terms, the first with the call's op and the
+// others ADD -- the composition rounds to dtype_out at every term, so where the launches are cut changes no byte.  Anything misaligned: the
+// composition itself, one guarded grouped dequantize per term.
+void piquant_hip_dequantize_sum_grouped(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, const float* const* input_scales,
+                                        const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out, size_t numel,
+                                        size_t group_size, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_sum_grouped";
+    const Where w {entry};
+    if (!ctx) bad(w, "context is NULL");
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size, entry);
+    if (count == 0) bad(w, "no terms (count must be at least 1)");
+    if (!inputs || !input_scales || !input_zero_points) bad(w, "NULL term list");
+    if (!out) bad(w, "NULL buffer");
+    if (numel == 0) return;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    void* out_dev = device_ptr(w, ctx->resolve_ptr(out));
+    if (reinterpret_cast<uintptr_t>(out_dev) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, out_dev, numel);
+    const int first_op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
+    const GroupedDequantCall call {static_cast<int64_t>(group_size), dtype_in, dtype_out, first_op};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
+        if (terms.aligned && aligned16(out_dev)) {
+            for (size_t from = 0; from < count; from += kGroupedReduceMaxInputs) {
+                const size_t n = std::min(count - from, static_cast<size_t>(kGroupedReduceMaxInputs));
+                GroupedDequantSumLaunch d {call, out_dev, static_cast<int64_t>(numel), {}, static_cast<int>(n)};
+                if (from != 0) d.op = OP_ADD;
+                std::copy_n(terms.term.begin() + static_cast<std::ptrdiff_t>(from), n, d.term);
+                launch_dequantize_sum_grouped(d, ctx->stream);
+            }
+        } else {
+            add_terms(ctx, terms, 0, 1, call);
+            add_terms(ctx, terms, 1, count, GroupedDequantCall {call.group_size, dtype_in, dtype_out, OP_ADD});
+        }
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
 void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
                                            void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
                                            uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {

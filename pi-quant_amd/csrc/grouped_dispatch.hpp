@@ -1,5 +1,5 @@
 // Host code shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip,
-// kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip, kernels_grouped_reduce_ef_f32r.hip, kernels_grouped_requant*.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
+// kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip, kernels_grouped_reduce_ef_f32r.hip, kernels_grouped_requant*.hip, kernels_grouped_dequant_sum.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
 // QuantParams, the chunk table and grids, and the launch bodies of the error-feedback kernel families and of the fused reduce kernels.
 #pragma once
 
@@ -196,6 +196,38 @@ void launch_grouped_reduce(const GroupedReduceLaunch& r, hipStream_t stream) {
                         PQ_LAUNCH((Family::template kernel<DT, BITS, MODE, G>()), grid, dim3(kGroupedBlock), 0, stream, r.in, static_cast<uint8_t*>(r.out),
                                   r.numel, r.scales, r.zero_points, ngroups, p, terms);
                 });
+            });
+        });
+    });
+    PQ_HIP(hipGetLastError());
+}
+
+// Launch body of the grouped dequantize-sum, instantiated once, in kernels_grouped_dequant_sum.hip (a template like the bodies above, so that no other
+// unit instantiates its kernels).  Family::name names it in messages; Family::kernel<DT_OUT, BITS, OP, G>() returns the kernel.  The grid is the
+// fused reduce's: one wave per chunk of the GroupedQuantTile of the OUTPUT type.
+template <class Family>
+void launch_grouped_dequant_sum(const GroupedDequantSumLaunch& d, hipStream_t stream) {
+    const char* name = Family::name;
+    if (d.numel <= 0) return;
+    if (d.count < 1 || d.count > kGroupedReduceMaxTerms) panic("%s: %d terms, 1 to %d per launch", name, d.count, kGroupedReduceMaxTerms);
+    GroupedTerms terms {};
+    for (int i = 0; i < d.count; ++i) {
+        terms.in[i] = static_cast<const uint8_t*>(d.term[i].in);
+        terms.scales[i] = d.term[i].scales;
+        terms.zero_points[i] = d.term[i].zero_points;
+    }
+    terms.count = d.count;
+    const int64_t ngroups = (d.numel + d.group_size - 1) / d.group_size;
+    with_float_type(d.dt_out, [&](auto di) {
+        constexpr int DT = decltype(di)::value;
+        with_quant_bits(d.dt_in, [&](auto bi) {
+            constexpr int BITS = decltype(bi)::value;
+            with_group_size(d.group_size, name, [&](auto gi) {
+                constexpr int G = decltype(gi)::value;
+                constexpr int NG = GroupedQuantTile<DT, BITS, G>::NG;
+                const dim3 grid(grouped_blocks((ngroups + NG - 1) / NG, name));
+                if (d.op == OP_ADD) PQ_LAUNCH((Family::template kernel<DT, BITS, OP_ADD, G>()), grid, dim3(kGroupedBlock), 0, stream, d.out, d.numel, ngroups, terms);
+                else PQ_LAUNCH((Family::template kernel<DT, BITS, OP_SET, G>()), grid, dim3(kGroupedBlock), 0, stream, d.out, d.numel, ngroups, terms);
             });
         });
     });

@@ -35,6 +35,7 @@
 //   grouped_quantize_chunk        parameters, quantization and staged stores of one chunk (KEEP / REQUANT: the chunk stays readable)
 //   GroupedTermLoad, grouped_park_term / grouped_park_term_partial, grouped_term_dequant_params, grouped_add_term
 //                                 a term of the fused reduce kernels: loaded a term ahead, staged (full chunk / partial chunk), gathered, added
+//   grouped_set_term              the first term of a dequantize-sum SET (dequantize_sum_grouped_kernel, at the end): stored, not added
 //   grouped_guarded_params        the group prologue of the four guarded quantizing kernels
 //   grouped_add_residual, residual_one, grouped_parked_dequant_params, grouped_store_vector, grouped_residual_store
 //                                 the error-feedback steps around the chunk body; grouped_ef_chunk is the whole tile for both residual types
@@ -1248,6 +1249,90 @@ reduce_quantize_grouped_ef_f32r_kernel(const void* __restrict__ acc, void* resid
     grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave],
                                                                    s_c[wave]);
     grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c[wave], s_b[wave]);
+}
+
+// ---- Dequantize-sum (piquant_hip_dequantize_sum_grouped): out (op)= dequantize_grouped(term_0) + ... + dequantize_grouped(term_{k-1}), the bytes of
+// k grouped dequantize calls into out (the first with the call's op, the others ADD: the running sum rounded to out's type after every term) in
+// ONE pass over out.  The term loop of reduce_quantize_grouped_kernel on its tile -- the float rows set the chunk's size, not the packed ones --
+// with a store of the rows in place of the quantize tail.
+
+// x[r] = the dequantized packed bytes of vector r of the lane in the type DT: what a grouped dequantize SET stores (bfloat16: rounded once).  The
+// first term of a SET is stored, not added to rows of +0.0: -0.0 + 0.0 is +0.0, and a NaN would take the adder's path instead of the converter's.
+template <int DT, int BITS, int G, int NV_ = GroupedQuantTile<DT, BITS, G>::NV>
+__device__ __forceinline__ void grouped_set_term(u32x4 (&x)[NV_], const uint8_t* stage, const float* s_scale, const float* s_bias, const int32_t* s_zp,
+                                                 int lane) {
+    using T = GroupedQuantTile<DT, BITS, G>;
+    constexpr int EPV = T::EPV, NV = T::NV, RPG = T::RPG, SETS = T::SETS;
+    DequantParams p[SETS];
+    grouped_term_dequant_params<T>(p, s_scale, s_bias, s_zp, lane);
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        float f[EPV];
+        grouped_dequantize_row<DT, BITS, G>(stage, r, lane, p[r / RPG], f);
+        if constexpr (DT == DT_F32) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[r][e] = __float_as_uint(f[e]);
+        } else {
+#pragma unroll
+            for (int h = 0; h < EPV / 2; ++h) x[r][h] = f32x2_to_bf16x2_bits(f[2 * h], f[2 * h + 1]);
+        }
+    }
+}
+
+// One wave per chunk; terms.count >= 1.  ADD loads the rows of out behind the first term's loads; SET never reads out.  Term i + 1 is in flight
+// (GroupedTermLoad) while term i is added.  A chunk the tensor ends in stages its terms byte by byte (grouped_park_term_partial) and stores through
+// grouped_store_vector: nothing at or past numel is read or written in any buffer.  No scan, no atomics, no grid barrier.
+template <int DT_OUT, int BITS, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_sum_grouped_kernel(void* __restrict__ out, int64_t numel, int64_t ngroups, GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_OUT, BITS, G>;
+    using L = GroupedTermLoad<DT_OUT, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // a term's {scale, bias}
+    __shared__ int32_t s_z[WAVES][NG];                 // a term's zero point
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_in[wave];
+    const int count = terms.count;
+
+    u32x4 raw[NV];
+    L next;
+    if (full) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+    if constexpr (OP == OP_ADD) grouped_load<DT_OUT, NV>(out, numel, v0, lane, full, raw);
+    // term i into the wave's LDS slices, term i + 1 into flight
+    auto stage_term = [&](int i) {
+        if (full) {
+            const L cur = next;
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            if (i + 1 < count) next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+        } else {
+            grouped_park_term_partial<T>(terms, i, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+        }
+        wave_lds_sync();
+    };
+    int i = 0;
+    if constexpr (OP == OP_SET) {   // the first term of a SET is peeled: the loop holds the add alone
+        stage_term(0);
+        grouped_set_term<DT_OUT, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+        wave_lds_sync();
+        i = 1;
+    }
+    for (; i < count; ++i) {
+        stage_term(i);
+        grouped_add_term<DT_OUT, DT_OUT, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+        wave_lds_sync();
+    }
+#pragma unroll
+    for (int r = 0; r < NV; ++r) grouped_store_vector<DT_OUT>(out, numel, v0 + r * 64 + lane, full, raw[r]);
 }
 
 }  // namespace pq

@@ -149,6 +149,16 @@ struct GroupedReduceLaunch : GroupedTensor, GroupedQuantCall {
     int count;
 };
 
+// out (op)= sum_i dequantize_grouped(term[i]), terms added in order, the running sum rounded to dt_out after each one (grouped_kernels.hpp,
+// dequantize_sum_grouped_kernel): ONE launch for 1 .. kGroupedReduceMaxInputs terms.  `out` (numel elements of dt_out) and every term's packed
+// bytes 16-byte aligned: the caller sends anything else through launch_dequantize_grouped, term by term (the same bytes).
+struct GroupedDequantSumLaunch : GroupedDequantCall {
+    void* out;
+    int64_t numel;
+    GroupedTensor term[kGroupedReduceMaxInputs];   // in, scales and zero_points are read
+    int count;
+};
+
 // Error feedback (grouped_kernels.hpp, quantize_grouped_ef_batch_kernel): per tensor y = in + residual, (out, scales, zero_points) =
 // quantize_grouped(y) with computed parameters, residual <- y - dequantize_grouped(out), in ONE launch for up to kGroupedBatchMaxTensors tensors
 // (every buffer 16-byte aligned, every tensor non-empty; a batch of one launches quantize_grouped_ef_kernel, whose arguments are leading scalars).
@@ -185,6 +195,7 @@ void launch_quantize_grouped_ef_f32r_guarded(const GroupedEfLaunch& q, hipStream
 // The fused reduce with error feedback for that pair (kernels_grouped_reduce_ef_f32r.hip): r.dt_in == DT_BF16, r.residual float32.  Terms, residual
 // and out 16-byte aligned, the accumulator 8-byte aligned (its lane-row is four elements), at most kGroupedReduceMaxInputs terms.
 void launch_reduce_quantize_grouped_ef_f32r(const GroupedReduceLaunch& r, hipStream_t stream);
+void launch_dequantize_sum_grouped(const GroupedDequantSumLaunch& d, hipStream_t stream);   // kernels_grouped_dequant_sum.hip
 void launch_quantize_dequantize_grouped_batch(const GroupedRequantBatchLaunch& b, hipStream_t stream);
 void launch_quantize_dequantize_grouped_guarded(const GroupedRequantLaunch& q, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word

@@ -513,6 +513,17 @@ class Context:
         C.piquant_hip_reduce_quantize_grouped(self._ctx, ptr_acc, dtype_acc.value, _ptr_array(ptrs_in), _ptr_array(scales_in), _ptr_array(zero_points_in), n,
                                               ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr, round_mode.value)
 
+    def dequantize_sum_grouped_ptr(self, ptrs_in, dtype_in: DataType, scales_ptrs, zero_points_ptrs, ptr_out: int, dtype_out: DataType, numel: int,
+                                   group_size: int, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """out (op)= sum_i dequantize_grouped(input i), input i with its own per-group parameters, in one pass over ``out``
+        (``piquant_hip_dequantize_sum_grouped``: one launch for up to 16 terms); bit-identical to ``dequantize_grouped_ptr`` per term in order, the
+        first with ``reduce_op`` and the others with ADD.  At least one term is needed."""
+        n = len(ptrs_in)
+        assert dtype_in.is_quantized and dtype_out.is_dequantized and n == len(scales_ptrs) == len(zero_points_ptrs) and n > 0
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_sum_grouped(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, ptr_out,
+                                             dtype_out.value, numel, group_size, reduce_op.value)
+
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                        _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:

@@ -528,6 +528,15 @@ class _DeviceOps:
                                                            torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], group_size, [r[0] for r in recs],
                                                            [r[1] for r in recs], _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
+    def decode_sum_grouped(self, bufs, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int) -> None:
+        """out (op)= the wire buffers, added in order, one launch and one pass over ``out`` (the bytes of decode_grouped buffer by buffer, the first
+        with ``reduce_op`` and the others with 'add')."""
+        if bufs:
+            n = out.numel()
+            recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+            self._cx(out).dequantize_sum_grouped_ptr([r[2] for r in recs], torch_to_piquant_dtype(qdtype), [r[0] for r in recs], [r[1] for r in recs],
+                                                     out.data_ptr(), torch_to_piquant_dtype(out.dtype), n, group_size, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+
     def reduce_encode_grouped(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped(acc + the wire buffers, added in order) into ``buf`` as one launch (``acc`` is scratch afterwards)."""
         n = acc.numel()
@@ -1039,6 +1048,149 @@ def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, o
         else:
             ops.reduce_encode_grouped(terms, x_own, mine[:n_own], quant_dtype, round_mode, group_size)
     gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)   # not `recv`: the launch above is still reading it
+    _all_gather(mine, gathered, group)
+    full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
+    ops.decode_batch_grouped([gathered[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set',
+                             group_size)
+    return tensor
+
+
+def _check_sharded_collective(name: str, tensor: torch.Tensor, group_size, error_feedback) -> None:
+    """ValueError before anything moves, for ``quantized_reduce_scatter`` and ``quantized_all_gather``: the tensor, a group size that is no group
+    size (``None`` included: they have the grouped wire only) and a residual that does not match the tensor."""
+    if not (isinstance(tensor, torch.Tensor) and tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
+        raise ValueError(f'{name} needs a contiguous float32 or bfloat16 tensor')
+    if group_size is None:
+        raise ValueError(f'{name} has the grouped wire only: group_size= must be a power of two in [32, 4096], got None')
+    _check_all_reduce_group_size(group_size, 'collective')
+    _check_error_feedback(error_feedback, tensor, group_size, 'collective')
+
+
+def quantized_reduce_scatter(
+    tensor: torch.Tensor,
+    *,
+    quant_dtype: torch.dtype = torch.uint8,
+    round_mode: str = 'nearest',
+    group: Optional[dist.ProcessGroup] = None,
+    ctx: Optional[Context] = None,
+    group_size: int = 128,
+    error_feedback: Optional[torch.Tensor] = None,
+    _ops=None,
+    _single_rank_collectives: bool = False,
+) -> torch.Tensor:
+    """SUM reduce-scatter of a contiguous float32/bfloat16 tensor over the grouped wire: the reduce-scatter half of
+    ``quantized_all_reduce(algorithm='direct', group_size=...)`` on its own, for sharded data parallelism and for an outer optimizer that owns
+    one shard.  The chunks are ``ring_chunks(numel, world, bits)`` and chunk r belongs to rank r.  Collective transport only.
+
+    1. ONE batched ``quantize_grouped`` launch encodes this rank's values of every peer's chunk (``grouped_wire_layout`` records),
+    2. ONE all-to-all delivers them,
+    3. ONE ``dequantize_sum_grouped(..., 'add')`` launch adds the world - 1 received records, in increasing rank order, into the rank's own chunk
+       of ``tensor``, in one pass over it.
+
+    Returns the view ``tensor.view(-1)[b_r:e_r]`` of the rank's own chunk (empty when the tensor is shorter than the chunks in front of it), now
+    holding the sum in full precision: every peer's contribution was quantized once, the owner's own values never, and the sum is not quantized
+    again.  The other chunks of ``tensor`` are left as they were.  Two kernel launches per call.
+
+    ``error_feedback``: the residual of ``quantized_all_reduce`` (the tensor's dtype, device and numel; float32 also for a bfloat16 tensor).  Step 1
+    becomes one batched ``quantize_grouped_ef`` launch on the peers' chunks of the tensor and of the residual; the rank's own chunk of the
+    residual is neither read nor written.  EVERY quantization this collective performs is covered by ``error_feedback``: there is no
+    re-quantization of a partial sum here, so there is nothing for an ``error_feedback_requantize`` to add.
+
+    ``quantized_reduce_scatter`` followed by ``quantized_all_gather`` on the same inputs leaves exactly the bytes of
+    ``quantized_all_reduce(algorithm='direct', group_size=group_size)``: that schedule's ``reduce_quantize_grouped`` is defined as these ADDs
+    followed by ``quantize_grouped``.
+
+    ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
+    returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
+    of this module's multi-GPU paths.)"""
+    _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    qdt = torch_to_piquant_dtype(quant_dtype)
+    flat = tensor.view(-1)
+    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
+    b_own, e_own = chunks[rank]
+    x_own = flat[b_own:e_own]
+    if world == 1 and not _single_rank_collectives:
+        return x_own
+    ops = _ops or _DeviceOps(ctx)
+
+    def wire_len(idx):
+        b, e = chunks[idx]
+        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
+
+    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16   # every slot starts on a 16-byte boundary (vector kernels on both sides)
+    send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
+    recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
+    peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
+    if error_feedback is None:
+        ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
+                                 round_mode, group_size)
+    else:
+        rflat = error_feedback.view(-1)
+        ops.encode_batch_grouped_ef([flat[chunks[j][0]:chunks[j][1]] for j in peers], [rflat[chunks[j][0]:chunks[j][1]] for j in peers],
+                                    [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype, round_mode, group_size)
+    _all_to_all(send, recv, group)
+    n_own = wire_len(rank)
+    terms = [recv[i * slot: i * slot + n_own] for i in range(world) if i != rank]
+    if x_own.numel() and terms:
+        ops.decode_sum_grouped(terms, x_own, quant_dtype, 'add', group_size)
+    return x_own
+
+
+def quantized_all_gather(
+    tensor: torch.Tensor,
+    *,
+    quant_dtype: torch.dtype = torch.uint8,
+    round_mode: str = 'nearest',
+    group: Optional[dist.ProcessGroup] = None,
+    ctx: Optional[Context] = None,
+    group_size: int = 128,
+    error_feedback: Optional[torch.Tensor] = None,
+    _ops=None,
+    _single_rank_collectives: bool = False,
+) -> torch.Tensor:
+    """In-place all-gather of a contiguous float32/bfloat16 tensor over the grouped wire: the all-gather half of
+    ``quantized_all_reduce(algorithm='direct', group_size=...)`` on its own.  The chunks are ``ring_chunks(numel, world, bits)``; rank r's chunk r
+    of ``tensor`` is its input, whatever its other chunks hold.  Collective transport only.
+
+    1. ONE ``quantize_grouped`` launch encodes the rank's own chunk (a ``grouped_wire_layout`` record),
+    2. ONE all-gather distributes the records,
+    3. ONE batched ``dequantize_grouped(..., 'set')`` launch stores all chunks into ``tensor`` -- the own chunk included, from the same bytes
+       every other rank decodes, so all ranks end bit-identical.
+
+    Returns ``tensor``.  ``error_feedback`` (as in ``quantized_reduce_scatter``): step 1 becomes ``quantize_grouped_ef`` on the rank's own chunk of
+    the residual; no other chunk of it is touched.  A residual belongs to one collective, world size and rank: do not share one between
+    ``quantized_reduce_scatter`` (which uses the peers' chunks) and this call unless that is the intent -- together the two touch every chunk
+    exactly once, as ``quantized_all_reduce`` with ``error_feedback_requantize`` does.
+
+    ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
+    returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
+    _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    if world == 1 and not _single_rank_collectives:
+        return tensor
+    ops = _ops or _DeviceOps(ctx)
+    qdt = torch_to_piquant_dtype(quant_dtype)
+    flat = tensor.view(-1)
+    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
+
+    def wire_len(idx):
+        b, e = chunks[idx]
+        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
+
+    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16
+    b_own, e_own = chunks[rank]
+    x_own = flat[b_own:e_own]
+    n_own = wire_len(rank)
+    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
+    if x_own.numel():
+        if error_feedback is None:
+            ops.encode_grouped(x_own, mine[:n_own], quant_dtype, round_mode, group_size)
+        else:
+            ops.encode_grouped_ef(x_own, error_feedback.view(-1)[b_own:e_own], mine[:n_own], quant_dtype, round_mode, group_size)
+    gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
     _all_gather(mine, gathered, group)
     full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
     ops.decode_batch_grouped([gathered[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set',

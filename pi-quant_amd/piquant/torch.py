@@ -805,6 +805,33 @@ def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype
     return outs
 
 
+def dequantize_sum_grouped(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, reduce_op: str = 'set', ctx: Optional[Context] = None,
+                           out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
+    """out (op)= ``dequantize_grouped(tensors[0]) + ... + dequantize_grouped(tensors[k - 1])`` in one launch (up to 16 terms) and one pass over
+    ``out``.  Term i is a packed tensor (or, with ``quant_dtype=`` and ``shape=``, the raw uint8 buffer of its bytes) with its own per-group
+    ``scales[i]`` / ``zero_points[i]`` (same ``group_size`` and numel).  The bytes are exactly those of ``dequantize_grouped(tensors[i], ...,
+    out=out)`` for every i in order, the first with ``reduce_op`` and the others with 'add': the running sum is rounded to ``dtype`` after every
+    term.  ``'add'`` accumulates into ``out=``; ``'set'`` never reads it.  Returns ``out`` (``include/piquant_hip.h``,
+    piquant_hip_dequantize_sum_grouped)."""
+    _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
+    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    _require(len(tensors) > 0, 'dequantize_sum_grouped needs at least one term')
+    _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
+             f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
+    _require(out is not None or reduce_op != 'add', "reduce_op='add' accumulates into out=; pass the accumulator tensor")
+    first = tensors[0]
+    _require(isinstance(first, torch.Tensor) and (first.dtype in _QUANT_TYPES or quant_dtype is not None), 'tensors[0] must be a quantized tensor')
+    dtype_in, logical_shape = _quant_meta(first, quant_dtype, shape)
+    numel = _numel_of(logical_shape)
+    _require(first.is_cuda, 'dequantize_sum_grouped needs ROCm device tensors')
+    _check_grouped_terms(tensors, scales, zero_points, dtype_in, repeat(numel), group_size, first.device)
+    out = _float_out(out, reduce_op, dtype, logical_shape, numel, first.device)
+    ctx = _ctx_for(first, ctx)
+    ctx.dequantize_sum_grouped_ptr(_ptrs(tensors), dtype_in, _ptrs(scales), _ptrs(zero_points), out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel,
+                                   group_size, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return out
+
+
 def dequantize_sum(tensors, params, *, dtype: torch.dtype, reduce_op: str = 'set', ctx: Optional[Context] = None,
                    out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
     """out (op)= sum_i dequantize(tensors[i]) with (scale, zero_point) of input i read from the device record ``params[i]``: one pass

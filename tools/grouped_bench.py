@@ -35,7 +35,12 @@ with SET, fp32 via uint8 with ADD) next to the two calls that define it (quantiz
 same run, with the byte ratio of each row (parameter bytes counted on both sides) and the target fused / composition <= 1.15 x that ratio.  Writes
 profiles/grouped_requant_bench.json; --rows all appends these rows to its table.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows dequant_sum: the grouped dequantize-sum (dequantize_sum_grouped, G = 128: fp32 out with uint8 and uint4 terms, k = 1 and k = 7, ADD; fp32 out
+with seven uint8 terms, SET; bf16 out with seven uint4 terms, ADD) next to the composition that defines it (k grouped dequantize launches) in the
+same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio; and the per-tensor dequantize_sum of seven
+uint8 terms into fp32 as a second yardstick.  Writes profiles/grouped_dequant_sum_bench.json; --rows all appends these rows to its table.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -555,17 +560,79 @@ def requant_rows(ctx, dev, stream, args, G=128):
     return rows
 
 
+def dequant_sum_rows(ctx, dev, stream, args, G=128):
+    """dequantize_sum_grouped against the k grouped dequantize launches that define it; the per-tensor dequantize_sum beside the 7 x uint8 row"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(8)
+    for fname, qname, k, op in (("f32", "uint8", 1, "add"), ("f32", "uint8", 7, "add"), ("f32", "uint4", 1, "add"), ("f32", "uint4", 7, "add"),
+                                ("f32", "uint8", 7, "set"), ("bf16", "uint4", 7, "add")):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        rop = piquant.ReduceOp.ADD if op == "add" else piquant.ReduceOp.SET
+        nq = qdt.packed_nbytes(NUMEL)
+        fbytes = NUMEL * esize
+        fused_bytes = k * (nq + 5 * ng) + fbytes * (2 if op == "add" else 1)             # k terms in; out (ADD: in and) out
+        comp_bytes = k * (nq + 5 * ng) + fbytes * (2 * k if op == "add" else 2 * k - 1)   # out in and out per term (SET: the first only writes)
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        outs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g).to(tdt) for _ in range(nbuf)]
+        terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.dequantize_sum_grouped_ptr([t.data_ptr() for t in terms[i]], qdt, [t.data_ptr() for t in tsc[i]], [t.data_ptr() for t in tzp[i]],
+                                           outs[i].data_ptr(), fdt, NUMEL, G, rop, _device_ptrs=True)
+
+        def composition(i):   # ADD accumulates into outs[i] call after call: at most 0.5 a term and call, far from any overflow
+            for j, (t, s_, z_) in enumerate(zip(terms[i], tsc[i], tzp[i])):
+                ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, outs[i].data_ptr(), fdt, NUMEL, G, s_.data_ptr(), z_.data_ptr(),
+                                           rop if j == 0 else piquant.ReduceOp.ADD, _device_ptrs=True)
+
+        pair = f"{fname}{'+=' if op == 'add' else '='}{k}x{qname}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("dequant_sum_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("dequantize_sum_grouped", pair, G, us_f, fused_bytes, s_f)
+        fr["over_composition"] = round(us_f / us_c, 3)
+        fr["bytes_over_composition"] = round(fused_bytes / comp_bytes, 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}", flush=True)
+        rows += [cr, fr]
+        if (fname, qname, k, op) == ("f32", "uint8", 7, "add"):   # the second yardstick: the per-tensor call on the same buffers, one record per term
+            recs = [[torch.zeros(16, dtype=torch.uint8, device=dev) for _ in range(k)] for _ in range(nbuf)]
+            x0 = torch.empty(4096, device=dev).uniform_(-1, 1, generator=g)
+            for rr in recs:
+                for rec in rr:
+                    pt.compute_quant_params_device(x0, dtype=torch.uint8, out=rec)
+            us_p, s_p = timed(lambda i: ctx.dequantize_sum_ptr([t.data_ptr() for t in terms[i]], [r_.data_ptr() for r_ in recs[i]], qdt, outs[i].data_ptr(), fdt,
+                                                               NUMEL, rop, _device_ptrs=True), nbuf, args.windows, per_window, stream)
+            pr = row("dequantize_sum (per tensor)", pair, 0, us_p, k * nq + 2 * fbytes, s_p)
+            fr["over_per_tensor_dequantize_sum"] = round(us_f / us_p, 3)
+            print(f"    grouped / per-tensor dequantize_sum = {fr['over_per_tensor_dequantize_sum']:.3f}", flush=True)
+            rows.append(pr)
+            del recs
+        del outs, terms, tsc, tzp
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
-                                                   "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json"}[args.rows])
+                                                   "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
+                                                   "dequant_sum": "grouped_dequant_sum_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -587,6 +654,8 @@ def main():
         rows = reduce_ef_f32r_rows(ctx, dev, stream, args)
     if args.rows == "requant":
         rows = requant_rows(ctx, dev, stream, args)
+    if args.rows == "dequant_sum":
+        rows = dequant_sum_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
@@ -631,6 +700,7 @@ def main():
     if args.rows == "all":
         rows += reduce_ef_f32r_rows(ctx, dev, stream, args)
         rows += requant_rows(ctx, dev, stream, args)
+        rows += dequant_sum_rows(ctx, dev, stream, args)
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
