@@ -343,6 +343,44 @@ PIQUANT_EXPORT void piquant_hip_quantize_dequantize_grouped_batch(piquant_contex
                                                                   size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
                                                                   int params_given, piquant_round_mode_t mode, piquant_reduce_op_t op);
 
+/* RANDOMIZED HADAMARD ROTATION of the groups (opt-in; no other call changes).  A group is quantized against its own min and max, so one large
+ * element stretches the step of its whole group; rotating every group by a random-sign diagonal and a normalised Walsh-Hadamard matrix before it is
+ * quantized spreads such an element over the group, and the rotation is undone after dequantizing.  It is orthogonal: the L2 error is the same in
+ * both domains.  Heavy-tailed data gains (DESIGN.md 4d has the ratios), Gaussian data is unaffected, flat data gets worse.
+ * THE ROTATION of group size G = 2^k (one of the eight group sizes) with a 64-bit seed acts on float32 values, one FULL group at a time:
+ *   signs        d[j], j in [0, G), is -1 if bit (j mod 16) of floor(t * 2^24) is set, t the per-element counter-hash threshold
+ *                (piquant_hip_set_stochastic_per_element) of seed `seed` and index j div 16; otherwise +1.  The signs depend on the position inside
+ *                the group only: every group uses the same d, so a shard that starts on a group boundary rotates exactly as the whole tensor does.
+ *   butterflies  fwht(v): for h = 1, 2, 4, ..., G / 2 in this order and every pair (i, i + h) with bit h of i clear,
+ *                (v[i], v[i + h]) <- (v[i] + v[i + h], v[i] - v[i + h]), each sum and difference ONE float32 operation.  The stage order is part of
+ *                the contract: it fixes every rounding, so the result is bit-reproducible.
+ *   constant     c_G = 2^(-k / 2) as a float32: the exact power of two for even k, float32(sqrt 2) (bits 0x3FB504F3) * 2^(-(k + 1) / 2) for odd k
+ *   forward      y = c_G * fwht(d * x)            inverse      x = d * (c_G * fwht(y))          (one multiply per element behind the last stage)
+ * A ragged last group (numel % G != 0; a tensor shorter than G is one) is NOT rotated: forward and inverse are the identity on it.  Non-finite
+ * inputs propagate as IEEE says (one NaN makes its whole group NaN); NaN payloads are not specified.
+ * piquant_hip_hadamard_grouped: each full group of out is the forward (inverse == 0) or inverse rotation of that group of in; `dtype` (float32 or
+ *   bfloat16) is the type of both, and out may be exactly in.  bfloat16 is widened, transformed in float32 and rounded to bfloat16 (nearest even)
+ *   on store.
+ * piquant_hip_quantize_grouped_rotated: bit for bit piquant_hip_quantize_grouped(y, float32, ..., params_given = 0, mode), y the float32 forward
+ *   rotation of the widened tensor -- a bfloat16 tensor is never rounded back before it is quantized.  Packed bytes, scales[ngroups] and
+ *   zero_points[ngroups] are written as piquant_hip_quantize_grouped writes them; all three rounding modes (the per-element mode indexes the
+ *   global element); the parameters are always computed.  One launch that never writes y.
+ * piquant_hip_dequantize_grouped_rotated: z = the float32 inverse rotation of piquant_hip_dequantize_grouped(in, ..., float32, SET); SET stores z
+ *   converted to dtype_out, ADD stores convert(widen(out) + z) with one float32 add and one rounding.  One launch that never writes the
+ *   un-rotated intermediate.
+ * All six dtype pairs, all eight group sizes.  Buffers that are not 16-byte aligned take guarded one-wave-per-group launches that write the same
+ * bytes; a float buffer that is not aligned to its element aborts.  Nothing outside the tensors is read or written.  Device (or pinned) buffers
+ * only; stream-ordered on the context's stream -- the first two as piquant_hip_quantize_grouped is, the dequantize always behind the previous call
+ * -- no host synchronisation, no allocation, the seed travels by value (hipGraph-capturable).  numel == 0 is a no-op that draws no threshold. */
+PIQUANT_EXPORT void piquant_hip_hadamard_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype, void* out, size_t numel,
+                                                 size_t group_size, uint64_t seed, int inverse);
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out,
+                                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
+                                                         uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out,
+                                                           piquant_dtype_t dtype_out, size_t numel, size_t group_size, const float* scales,
+                                                           const uint8_t* zero_points, uint64_t seed, piquant_reduce_op_t op);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

@@ -1,5 +1,5 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, and quantize-dequantize.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// for a bfloat16 tensor, quantize-dequantize, and the three calls of the randomized Hadamard rotation.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -301,6 +301,74 @@ void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piqu
         StopEventScope completion(ctx);
         IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
         launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The three rotated calls (grouped_rot_kernels.hpp): the two entries above with the rotation's seed, and the stand-alone transform.  In and out
+// 16-byte aligned: the streaming kernels; anything else element-aligned: the guarded ones, the same bytes.
+void piquant_hip_hadamard_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype, void* out, size_t numel, size_t group_size,
+                                  uint64_t seed, int inverse) {
+    const Where w {"piquant_hip_hadamard_grouped"};
+    if (!ctx) bad(w, "context is NULL");
+    if (dtype_of(dtype).quant) panic("%s: dtype (%s) must be a dequantized type", w.entry, dtype_of(dtype).name);
+    check_group_size(group_size, w.entry);
+    if (numel == 0) return;
+    if (!in || !out) bad(w, "NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, nullptr, nullptr, numel);
+    const size_t esize = dtype == PIQUANT_DTYPE_F32 ? 4 : 2;
+    if (reinterpret_cast<uintptr_t>(t.in) % esize != 0 || reinterpret_cast<uintptr_t>(t.out) % esize != 0) bad(w, "in or out is not aligned to its element size");
+    const GroupedHadamardLaunch h {t.in, t.out, t.numel, static_cast<int64_t>(group_size), dtype, seed, inverse != 0};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, false);
+        launch_hadamard_grouped(h, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
+                                          size_t numel, size_t group_size, float* scales, uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode) {
+    const Where w {"piquant_hip_quantize_grouped_rotated"};
+    if (!ctx) bad(w, "context is NULL");
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    if (reinterpret_cast<uintptr_t>(t.in) % (dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "in is not aligned to its element size");
+    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
+    const GroupedQuantLaunch q {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, false);
+        launch_quantize_grouped_rotated(q, seed, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
+                                            size_t numel, size_t group_size, const float* scales, const uint8_t* zero_points, uint64_t seed,
+                                            piquant_reduce_op_t op) {
+    const Where w {"piquant_hip_dequantize_grouped_rotated"};
+    if (!ctx) bad(w, "context is NULL");
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size);
+    if (numel == 0) return;
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    if (reinterpret_cast<uintptr_t>(t.out) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    const GroupedDequantLaunch d {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}};
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+        launch_dequantize_grouped_rotated(d, seed, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
     }
     if (ctx->blocking) wait_stream(ctx);
 }

@@ -198,6 +198,22 @@ void launch_reduce_quantize_grouped_ef_f32r(const GroupedReduceLaunch& r, hipStr
 void launch_dequantize_sum_grouped(const GroupedDequantSumLaunch& d, hipStream_t stream);   // kernels_grouped_dequant_sum.hip
 void launch_quantize_dequantize_grouped_batch(const GroupedRequantBatchLaunch& b, hipStream_t stream);
 void launch_quantize_dequantize_grouped_guarded(const GroupedRequantLaunch& q, hipStream_t stream, int num_cu);
+// The randomized Hadamard rotation of whole groups (grouped_rot_kernels.hpp; kernels_grouped_rot.hip, kernels_grouped_rot_quant.hip).  The three
+// streaming launches need in and out 16-byte aligned; `guarded` runs the one-wave-per-group kernels instead: any element alignment, the same bytes.
+struct GroupedHadamardLaunch {
+    const void* in;
+    void* out;             // same type; may be in
+    int64_t numel;
+    int64_t group_size;
+    int dt;                // DT_F32 / DT_BF16
+    uint64_t seed;
+    bool inverse;
+};
+void launch_hadamard_grouped(const GroupedHadamardLaunch& h, bool guarded, hipStream_t stream, int num_cu);
+// quantize_grouped (computed parameters; params_given is not used) of the float32 forward rotation of the widened tensor, which is never written
+void launch_quantize_grouped_rotated(const GroupedQuantLaunch& q, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+// out (op)= the inverse rotation of the float32 grouped dequantize of in, which is never written
+void launch_dequantize_grouped_rotated(const GroupedDequantLaunch& d, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -524,6 +524,32 @@ class Context:
         C.piquant_hip_dequantize_sum_grouped(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, ptr_out,
                                              dtype_out.value, numel, group_size, reduce_op.value)
 
+    def hadamard_grouped_ptr(self, ptr_in: int, dtype: DataType, ptr_out: int, numel: int, group_size: int, seed: int, inverse: bool = False,
+                             _device_ptrs: bool = False) -> None:
+        """The randomized Hadamard rotation of every full group of ``group_size`` elements (``piquant_hip_hadamard_grouped``): forward, or its
+        inverse; ``ptr_out`` may equal ``ptr_in``.  ``seed`` is taken modulo 2^64.  A ragged last group is not rotated."""
+        assert dtype.is_dequantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_hadamard_grouped(self._ctx, ptr_in, dtype.value, ptr_out, numel, group_size, int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if inverse else 0)
+
+    def quantize_grouped_rotated_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                                     scales_ptr: int, zero_points_ptr: int, seed: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_ptr`` (computed parameters) of the float32 forward rotation of the tensor, in one launch that never writes the rotated
+        tensor (``piquant_hip_quantize_grouped_rotated``)."""
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_rotated(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
+    def dequantize_grouped_rotated_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                                       scales_ptr: int, zero_points_ptr: int, seed: int, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """out (op)= the inverse rotation of the float32 ``dequantize_grouped_ptr`` of the input, in one launch
+        (``piquant_hip_dequantize_grouped_rotated``)."""
+        assert dtype_in.is_quantized and dtype_out.is_dequantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_grouped_rotated(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                                 zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, reduce_op.value)
+
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                        _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:

@@ -545,6 +545,84 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
     return out
 
 
+def _check_seed(seed) -> int:
+    """The rotation's seed: any Python int, taken modulo 2^64 (``_NA``: the call was made without one)."""
+    _require(seed is not _NA, 'seed= is required: the rotation is defined by it, and the inverse needs the same one')
+    _require(isinstance(seed, int) and not isinstance(seed, bool), f'seed must be an int, got {seed!r}')
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def hadamard_grouped(tensor: torch.Tensor, *, group_size: int = 128, seed=_NA, inverse: bool = False, out: Optional[torch.Tensor] = None,
+                     ctx: Optional[Context] = None) -> torch.Tensor:
+    """The randomized Hadamard rotation of every full group of ``group_size`` contiguous elements of the flattened tensor: random signs drawn from
+    ``seed`` (the same for every group), the Walsh-Hadamard butterflies in float32, the factor ``group_size ** -0.5``; ``inverse=True`` undoes it
+    (``include/piquant_hip.h``, piquant_hip_hadamard_grouped, has the definition).  Orthogonal: group norms and L2 errors are those of the original
+    domain.  bfloat16 is transformed in float32 and rounded on store.  A ragged last group is not rotated.  ``out`` may be ``tensor`` (in place).
+    One asynchronous launch on the current stream."""
+    _check_modes(group_size=group_size)
+    seed = _check_seed(seed)
+    _check_float_input(tensor)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    out = _float_out(out, 'set', tensor.dtype, tensor.shape, tensor.numel(), tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.hadamard_grouped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), tensor.numel(), group_size, seed, bool(inverse),
+                             _device_ptrs=True)
+    return out
+
+
+def quantize_grouped_rotated(tensor: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, seed=_NA, round_mode: str = 'nearest',
+                             ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
+                             out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``quantize_grouped`` (computed parameters) of the rotated tensor, in one launch that never writes the rotated tensor: bit for bit
+    ``quantize_grouped(hadamard_grouped(tensor.float(), group_size=group_size, seed=seed), dtype=dtype, ...)``.  An outlier no longer stretches the
+    step of its group: heavy-tailed data loses 3 to 30 times less, Gaussian data the same, flat data more.  Returns (quantized, scales,
+    zero_points) as ``quantize_grouped`` does; ``dequantize_grouped_rotated`` with the same ``seed`` is the way back
+    (``include/piquant_hip.h``, piquant_hip_quantize_grouped_rotated)."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    seed = _check_seed(seed)
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    if out_scales is not None:
+        _check_group_params(out_scales, out_zero_points, num_groups(tensor.numel(), group_size))
+    _check_float_input(tensor)
+    scales, zero_points = _group_params_of(out_scales, out_zero_points, tensor.numel(), group_size, tensor.device, 'out_scales and out_zero_points',
+                                           shapes_checked=True)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    out = _packed_out(out, dtype, tensor, tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_grouped_rotated_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(dtype),
+                                     tensor.numel(), group_size, scales.data_ptr(), zero_points.data_ptr(), seed, _ROUND_MODES[round_mode],
+                                     _device_ptrs=True)
+    return out, scales, zero_points
+
+
+def dequantize_grouped_rotated(tensor: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor, *, dtype: torch.dtype, group_size: int,
+                               seed=_NA, reduce_op: str = 'set', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                               quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:
+    """Inverse of ``quantize_grouped_rotated``: the float32 ``dequantize_grouped`` of the tensor, rotated back with ``seed``, stored
+    (``reduce_op='set'``) or added into ``out`` (``'add'``: one float32 add, one rounding), in one launch that never writes the un-rotated
+    intermediate (``include/piquant_hip.h``, piquant_hip_dequantize_grouped_rotated).  A raw uint8 buffer of packed bytes needs ``quant_dtype=``
+    and ``shape=``."""
+    _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
+    seed = _check_seed(seed)
+    _require(isinstance(tensor, torch.Tensor) and (tensor.dtype in _QUANT_TYPES or quant_dtype is not None), 'tensor must be a quantized tensor')
+    dtype_in, logical_shape = _quant_meta(tensor, quant_dtype, shape)
+    numel = _numel_of(logical_shape)
+    _check_group_params(scales, zero_points, num_groups(numel, group_size))
+    _require(tensor.is_cuda, 'dequantize_grouped_rotated needs a ROCm device tensor')
+    _require(scales.device == tensor.device and zero_points.device == tensor.device, f'scales and zero_points must live on {tensor.device}')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    _check_packed_in(tensor, dtype_in, numel, tensor.device, 'tensor')
+    out = _float_out(out, reduce_op, dtype, logical_shape, numel, tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.dequantize_grouped_rotated_ptr(tensor.data_ptr(), dtype_in, out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, group_size,
+                                       scales.data_ptr(), zero_points.data_ptr(), seed, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return out
+
+
 def reduce_quantize_grouped(acc: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest',
                             ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
                             out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -40,7 +40,13 @@ with seven uint8 terms, SET; bf16 out with seven uint4 terms, ADD) next to the c
 same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio; and the per-tensor dequantize_sum of seven
 uint8 terms into fp32 as a second yardstick.  Writes profiles/grouped_dequant_sum_bench.json; --rows all appends these rows to its table.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows rot: the randomized Hadamard rotation of whole groups (G = 128): hadamard_grouped in place (fp32, bf16) next to quantize_dequantize_grouped of
+the same type, which moves the same bytes; quantize_grouped_rotated (fp32 -> uint8, fp32 -> uint4, bf16 -> uint4, bf16 -> uint2) next to
+hadamard_grouped into a scratch tensor + quantize_grouped; dequantize_grouped_rotated SET (uint4 -> bf16, uint8 -> fp32) next to dequantize_grouped +
+hadamard_grouped in place; all in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
+profiles/grouped_rot_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -621,18 +627,96 @@ def dequant_sum_rows(ctx, dev, stream, args, G=128):
     return rows
 
 
+def rot_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
+    """the stand-alone rotation against quantize_dequantize_grouped (the same bytes); the two rotated calls against the compositions they replace"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(9)
+
+    def ratio(fr, cr, what="composition"):
+        fr["over_composition"] = round(fr["us"] / cr["us"], 3)
+        fr["bytes_over_composition"] = round(fr["bytes"] / cr["bytes"], 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    {fr['kind']} / {what} = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte "
+              f"ratio, target 1.15 {fr['target_1.15x_byte_ratio']}", flush=True)
+
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        fbytes = NUMEL * esize
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (2 * fbytes)) + 1)
+        xs = [torch.empty(NUMEL, dtype=tdt, device=dev).normal_(generator=g) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+        # in place, call after call: the rotation is orthogonal and the fake quantization idempotent, so the values stay where they are
+        us_q, s_q = timed(lambda i: ctx.quantize_dequantize_grouped_ptr(xs[i].data_ptr(), fdt, xs[i].data_ptr(), piquant.DataType.UINT8, NUMEL, G, 0, 0, False,
+                                                                        piquant.RoundMode.NEAREST, piquant.ReduceOp.SET, _device_ptrs=True),
+                          nbuf, args.windows, per_window, stream)
+        qr = row("quantize_dequantize_grouped in place", f"{fname} via uint8", G, us_q, 2 * fbytes, s_q)
+        us_h, s_h = timed(lambda i: ctx.hadamard_grouped_ptr(xs[i].data_ptr(), fdt, xs[i].data_ptr(), NUMEL, G, seed, False, _device_ptrs=True),
+                          nbuf, args.windows, per_window, stream)
+        hr = row("hadamard_grouped in place", fname, G, us_h, 2 * fbytes, s_h)
+        ratio(hr, qr, "quantize_dequantize_grouped")
+        rows += [qr, hr]
+        rot = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        for qname in {"f32": ("uint8", "uint4"), "bf16": ("uint4", "uint2")}[fname]:
+            qdt, bits = QUANT[qname]
+            nq = qdt.packed_nbytes(NUMEL)
+            outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+
+            def composition(i):
+                ctx.hadamard_grouped_ptr(xs[i].data_ptr(), fdt, rot[i].data_ptr(), NUMEL, G, seed, False, _device_ptrs=True)
+                ctx.quantize_grouped_ptr(rot[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                         piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            def fused(i):
+                ctx.quantize_grouped_rotated_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), seed,
+                                                 piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            pair = f"{fname}->{qname}"
+            us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+            cr = row("hadamard + quantize_grouped", pair, G, us_c, 3 * fbytes + nq + 5 * ng, s_c)
+            us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+            fr = row("quantize_grouped_rotated", pair, G, us_f, fbytes + nq + 5 * ng, s_f)
+            ratio(fr, cr)
+            rows += [cr, fr]
+            if (fname, qname) in (("f32", "uint8"), ("bf16", "uint4")):   # the way back of the same pair, with this call's bytes and parameters
+                dpair = f"{qname}->{fname}"
+
+                def dcomposition(i):
+                    ctx.dequantize_grouped_ptr(outs[i].data_ptr(), qdt, rot[i].data_ptr(), fdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                               piquant.ReduceOp.SET, _device_ptrs=True)
+                    ctx.hadamard_grouped_ptr(rot[i].data_ptr(), fdt, rot[i].data_ptr(), NUMEL, G, seed, True, _device_ptrs=True)
+
+                def dfused(i):
+                    ctx.dequantize_grouped_rotated_ptr(outs[i].data_ptr(), qdt, rot[i].data_ptr(), fdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), seed,
+                                                       piquant.ReduceOp.SET, _device_ptrs=True)
+
+                us_c, s_c = timed(dcomposition, nbuf, args.windows, per_window, stream)
+                cr = row("dequantize_grouped + hadamard", dpair, G, us_c, 3 * fbytes + nq + 5 * ng, s_c)
+                us_f, s_f = timed(dfused, nbuf, args.windows, per_window, stream)
+                fr = row("dequantize_grouped_rotated", dpair, G, us_f, fbytes + nq + 5 * ng, s_f)
+                ratio(fr, cr)
+                rows += [cr, fr]
+            del outs
+        del xs, rot, sc, zs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot"), default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
                                                    "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
-                                                   "dequant_sum": "grouped_dequant_sum_bench.json"}[args.rows])
+                                                   "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -656,6 +740,8 @@ def main():
         rows = requant_rows(ctx, dev, stream, args)
     if args.rows == "dequant_sum":
         rows = dequant_sum_rows(ctx, dev, stream, args)
+    if args.rows == "rot":
+        rows = rot_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
