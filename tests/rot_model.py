@@ -92,9 +92,10 @@ def quantize_grouped_rotated(x, dt, qd, G, seed, round_mode=O.NEAREST, threshold
     return GM.quantize_grouped(rotate(widen(x, dt), G, seed), O.F32, qd, G, round_mode, threshold)
 
 
-def quantize_grouped_rotated_per_element(x, dt, qd, G, seed, elem_seed, index_base):
-    """the same in per-element stochastic mode: element i draws the threshold of index index_base + i"""
-    return PE.quantize(rotate(widen(x, dt), G, seed), O.F32, qd, G, elem_seed, index_base)
+def quantize_grouped_rotated_per_element(x, dt, qd, G, seed, elem_seed, index_base, start=0):
+    """the same in per-element stochastic mode: element i draws the threshold of index index_base + i; x may be the window [start, start + x.size) of
+    a longer tensor, start a multiple of G (the rotation depends on the position inside the group only)"""
+    return PE.quantize(rotate(widen(x, dt), G, seed), O.F32, qd, G, elem_seed, index_base, start=start)
 
 
 def dequantize_grouped_rotated(q, qd, dt_out, n, G, scales, zps, seed, reduce_op=O.SET, prev=None):

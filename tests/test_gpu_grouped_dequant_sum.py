@@ -20,6 +20,8 @@ QDT = {O.UINT8: torch.uint8, O.UINT4: torch.quint4x2, O.UINT2: torch.quint2x4}
 BITS = {O.UINT8: 8, O.UINT4: 4, O.UINT2: 2}
 PAIRS = [(O.F32, O.UINT8), (O.F32, O.UINT4), (O.F32, O.UINT2), (O.BF16, O.UINT8), (O.BF16, O.UINT4), (O.BF16, O.UINT2)]
 COUNTS = (1, 2, 7, 16, 17, 33)   # one launch, the limit of one launch, the split at 16 and a third launch
+SOME_COUNTS = (1, 2, 16, 17)     # the group sizes between 32, 128 and 4096: the instances of one and of several terms, and the split
+GROUP_SIZES = (32, 64, 128, 256, 512, 1024, 2048, 4096)
 
 
 def tile_elems(dt, qd, G):
@@ -142,13 +144,14 @@ def same(got, want, what=""):
 
 
 @pytest.mark.parametrize("dt,qd", PAIRS)
-@pytest.mark.parametrize("G", [32, 128, 4096])
+@pytest.mark.parametrize("G", GROUP_SIZES)
 def test_fused_equals_the_composition(ctx, dt, qd, G):
     fdt = FDT[dt]
+    counts = COUNTS if G in (32, 128, 4096) else SOME_COUNTS
     for i, n in enumerate(sizes(dt, qd, G)):
-        terms = make_terms(n, fdt, qd, G, max(COUNTS), 100 * i + G + qd)
+        terms = make_terms(n, fdt, qd, G, max(counts), 100 * i + G + qd)
         init = _rand(n, fdt, 7 + i)
-        for k in COUNTS:
+        for k in counts:
             for op in ("set", "add"):
                 start = init if op == "add" else None
                 same(fused(terms[:k], start, op, fdt, qd, G, n), composition(terms[:k], start, op, fdt, qd, G, n), f"n={n} k={k} {op}")
@@ -157,13 +160,17 @@ def test_fused_equals_the_composition(ctx, dt, qd, G):
 @pytest.mark.parametrize("dt,qd", PAIRS)
 def test_fused_equals_the_cpu_group_model(ctx, dt, qd):
     """Against tests/grouped_model.py directly: dequantize_grouped chained with prev=, the first term SET or ADD."""
-    G, fdt = 128, FDT[dt]
-    n = 3 * tile_elems(dt, qd, G) + G + 5
+    G = 128
+    against_the_cpu_group_model(dt, qd, G, 3 * tile_elems(dt, qd, G) + G + 5, 3)
+
+
+def against_the_cpu_group_model(dt, qd, G, n, k):
+    fdt = FDT[dt]
 
     def host(t):
         return t.view(torch.int16).cpu().numpy().view(np.uint16) if dt == O.BF16 else t.cpu().numpy()
 
-    terms = make_terms(n, fdt, qd, G, 3, 900 + qd)
+    terms = make_terms(n, fdt, qd, G, k, 900 + qd)
     init = _rand(n, fdt, 31)
     for op in ("set", "add"):
         a = host(init).copy() if op == "add" else None
@@ -172,7 +179,18 @@ def test_fused_equals_the_cpu_group_model(ctx, dt, qd):
                                    prev=a)
         got = host(fused(terms, init if op == "add" else None, op, fdt, qd, G, n))
         bad = np.flatnonzero(got.view(np.uint16 if dt == O.BF16 else np.uint32) != a.view(np.uint16 if dt == O.BF16 else np.uint32))
-        assert bad.size == 0, f"{op}: {bad.size} elements differ from the CPU model, first at {bad[:8]}"
+        assert bad.size == 0, f"G={G} n={n} k={k} {op}: {bad.size} elements differ from the CPU model, first at {bad[:8]}"
+
+
+@pytest.mark.parametrize("dt,qd", PAIRS)
+@pytest.mark.parametrize("G", GROUP_SIZES)
+def test_fused_equals_the_cpu_group_model_at_every_group_size(ctx, dt, qd, G):
+    """Every group size has its own instances of grouped_set_term, grouped_add_term and grouped_park_term_partial: one tile less one element, exactly
+    one tile, and three tiles with a ragged chunk and a ragged group; one term and three; SET and ADD."""
+    tile = tile_elems(dt, qd, G)
+    for n in (tile - 1, tile, 3 * tile + G + 5):
+        for k in (1, 3):
+            against_the_cpu_group_model(dt, qd, G, n, k)
 
 
 def edge_terms(n, qd, G, k, seed):
@@ -241,7 +259,7 @@ def test_set_does_not_read_out(ctx, dt, qd):
 def test_misaligned_buffers_give_the_same_bytes(ctx):
     """out one element into its allocation (x[1:]) and a term one byte into its own: the composition through the guarded kernel, the same bytes."""
     G = 128
-    for dt, qd in ((O.F32, O.UINT8), (O.BF16, O.UINT4)):
+    for dt, qd in PAIRS:
         fdt = FDT[dt]
         n = 3 * tile_elems(dt, qd, G) + G + 5
         terms = make_terms(n, fdt, qd, G, 3, 70 + qd)

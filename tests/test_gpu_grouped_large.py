@@ -1,5 +1,6 @@
 """The grouped kernels where 32 bits run out: tensors of 2^32 + 40 037 bfloat16 and 2^31 + 40 037 float32 elements (8.6 GB each), and one
-float32 -> uint8 quantize and one uint8 -> float32 dequantize of 2^32 + 40 037 elements.  One case is one test.  Element indices cross 2^31 and 2^32, input byte offsets 2^31, 2^32 and 2^33, output byte
+float32 -> uint8 quantize and one uint8 -> float32 dequantize of 2^32 + 40 037 elements; the rotated calls (hadamard_grouped, quantize_grouped_rotated,
+dequantize_grouped_rotated) and the grouped dequantize-sum of two terms at the same sizes.  One case is one test.  Element indices cross 2^31 and 2^32, input byte offsets 2^31, 2^32 and 2^33, output byte
 offsets 2^31 (and 2^32 for the uint8 term of the reduce and for the float outputs).  Gradient buckets of a few GB are the ordinary use of the
 grouped all-reduce; a truncated 64-bit product, chunk table entry, ctypes argument or allocation size would corrupt them silently.
 
@@ -19,6 +20,7 @@ import pytest
 
 import oracle as O
 import per_element_model as M
+import rot_model as R
 from grouped_model import PACK, dequantize_grouped, quantize_grouped
 from per_element_cases import SEED_FULL as SEED
 from test_gpu_grouped_per_element import same_bytes, same_floats, same_params
@@ -534,4 +536,135 @@ def test_guarded_kernels(ctx, entry):
                 same_floats(host(r[0], lo, hi), want[3], dt, f"residual, window [{lo}, {hi})")
     finally:
         del x, r, a, b, t, y
+        torch.cuda.empty_cache()
+
+
+# ---- 8. the randomized Hadamard rotation and the calls built on it: the streaming kernels (tests/test_gpu_grouped_rotated_edges.py takes the guarded
+# ones round their grid-stride loop).  A multiple of 4096 is a group boundary for every group size, so a shard rotates as the whole tensor does
+# ("every group, shard and chunk that starts on a group boundary uses the same d"): the shards pin that sentence of the contract too.  The windows are
+# chunks of the FLOAT32 tile, which every rotated kernel sits on.
+
+ROT_SEED = 0x9E37_79B9_7F4A_7C15   # 64 bits next to a size_t numel in the ctypes entries
+
+
+@pytest.mark.parametrize("dt,n,G,inverse,in_place", [(O.BF16, N_BF, 128, False, True), (O.BF16, N_BF, 4096, True, True), (O.F32, N_F, 32, False, False)])
+def test_hadamard_grouped(ctx, dt, n, G, inverse, in_place):
+    """G = 4096 takes the stages between the rows one lane holds"""
+    import piquant
+
+    wins = windows(n, M.tile(O.F32, O.UINT8, G).chunk, [dt])
+    x = y = None
+    try:
+        x = [filled(n, dt, G, 30, wins)]
+        before = [host(x[0], lo, hi) for lo, hi in wins]
+        if in_place:
+            x.append(x[0].clone())
+            y = x
+        else:
+            x.append(x[0])
+            y = [torch.empty(n, dtype=FDT[dt], device="cuda") for _ in range(2)]
+
+        def call(lo, hi, k):
+            ctx.hadamard_grouped_ptr(addr(x[k], lo), piquant.DataType(dt), addr(y[k], lo), hi - lo, G, ROT_SEED, inverse, _device_ptrs=True)
+
+        whole_then_shards(ctx, n, call, stochastic=False)
+        equal_ints(y[0], y[1], "out")
+        for (lo, hi), xw in zip(wins, before):
+            same_floats(host(y[0], lo, hi), R.hadamard_grouped(xw, dt, G, ROT_SEED, inverse), dt, f"window [{lo}, {hi})")
+    finally:
+        del x, y
+        torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("dt,qd,n,G,case", [(O.BF16, O.UINT4, N_BF, 128, "per-element"), (O.F32, O.UINT8, N_F, 4096, "nearest")])
+def test_quantize_grouped_rotated(ctx, dt, qd, n, G, case):
+    import piquant
+
+    wins = windows(n, M.tile(O.F32, qd, G).chunk, [dt, qd])
+    stochastic = case == "per-element"
+    x = a = b = None
+    try:
+        x = filled(n, dt, G, 31, wins)
+        a, b = outputs(n, qd, G), outputs(n, qd, G)
+
+        def call(lo, hi, k):
+            q, s, z = (a, b)[k]
+            ctx.quantize_grouped_rotated_ptr(addr(x, lo), piquant.DataType(dt), q.data_ptr() + lo // PACK[qd], piquant.DataType(qd), hi - lo, G, addr(s, lo // G),
+                                             addr(z, lo // G), ROT_SEED, piquant.RoundMode(O.STOCHASTIC if stochastic else O.NEAREST), _device_ptrs=True)
+
+        whole_then_shards(ctx, n, call, stochastic=stochastic)
+        for k, name in enumerate(("bytes", "scales", "zero points")):
+            equal_ints(a[k], b[k], name)
+        for lo, hi in wins:
+            xw, what = host(x, lo, hi), f"window [{lo}, {hi})"
+            if stochastic:
+                want = R.quantize_grouped_rotated_per_element(xw, dt, qd, G, ROT_SEED, SEED, 0, start=lo)
+            else:
+                want = R.quantize_grouped_rotated(xw, dt, qd, G, ROT_SEED)
+            same_params(*params_host(a[1], a[2], G, lo, hi), want[1], want[2], what)
+            same_bytes(packed_host(a[0], qd, lo, hi), want[0], qd, what)
+    finally:
+        del x, a, b
+        torch.cuda.empty_cache()
+
+
+def test_dequantize_grouped_rotated(ctx):
+    """uint4 -> bfloat16, ADD"""
+    import piquant
+
+    qd, dt, n, G = O.UINT4, O.BF16, N_BF, 128
+    wins = windows(n, M.tile(O.F32, qd, G).chunk, [dt, qd])
+    t = prev = ya = yb = None
+    try:
+        t = random_packed(n, qd, G, 32)
+        prev = filled(n, dt, G, 33, wins)
+        ya, yb = prev.clone(), prev.clone()
+
+        def call(lo, hi, k):
+            ctx.dequantize_grouped_rotated_ptr(t[0].data_ptr() + lo // PACK[qd], piquant.DataType(qd), addr((ya, yb)[k], lo), piquant.DataType(dt), hi - lo, G,
+                                               addr(t[1], lo // G), addr(t[2], lo // G), ROT_SEED, piquant.ReduceOp.ADD, _device_ptrs=True)
+
+        whole_then_shards(ctx, n, call, stochastic=False)
+        equal_ints(ya, yb, "out")
+        for lo, hi in wins:
+            s, z = params_host(t[1], t[2], G, lo, hi)
+            want = R.dequantize_grouped_rotated(packed_host(t[0], qd, lo, hi), qd, dt, hi - lo, G, s, z, ROT_SEED, O.ADD, host(prev, lo, hi))
+            same_floats(host(ya, lo, hi), want, dt, f"window [{lo}, {hi})")
+    finally:
+        del t, prev, ya, yb
+        torch.cuda.empty_cache()
+
+
+# ---- 9. the grouped dequantize-sum, two terms: the windows are chunks of the tile of the OUTPUT type
+
+@pytest.mark.parametrize("qd,dt,n,op", [(O.UINT4, O.BF16, N_BF, O.ADD), (O.UINT8, O.F32, N_F, O.SET)])
+def test_dequantize_sum_grouped(ctx, qd, dt, n, op):
+    import piquant
+
+    G = 128
+    wins = windows(n, M.tile(dt, qd, G).chunk, [dt, qd])
+    terms = prev = ya = yb = None
+    try:
+        terms = [random_packed(n, qd, G, 34 + i) for i in range(2)]
+        if op == O.ADD:
+            prev = filled(n, dt, G, 36, wins)
+            ya, yb = prev.clone(), prev.clone()
+        else:
+            ya, yb = (torch.empty(n, dtype=FDT[dt], device="cuda") for _ in range(2))
+
+        def call(lo, hi, k):
+            ctx.dequantize_sum_grouped_ptr([t[0].data_ptr() + lo // PACK[qd] for t in terms], piquant.DataType(qd), [addr(t[1], lo // G) for t in terms],
+                                           [addr(t[2], lo // G) for t in terms], addr((ya, yb)[k], lo), piquant.DataType(dt), hi - lo, G, piquant.ReduceOp(op),
+                                           _device_ptrs=True)
+
+        whole_then_shards(ctx, n, call, stochastic=False)
+        equal_ints(ya, yb, f"op={op}")
+        for lo, hi in wins:
+            want = host(prev, lo, hi) if op == O.ADD else None
+            for i, t in enumerate(terms):
+                s, z = params_host(t[1], t[2], G, lo, hi)
+                want = dequantize_grouped(packed_host(t[0], qd, lo, hi), qd, dt, hi - lo, G, s, z, op if i == 0 else O.ADD, want)
+            same_floats(host(ya, lo, hi), want, dt, f"op={op}, window [{lo}, {hi})")
+    finally:
+        del terms, prev, ya, yb
         torch.cuda.empty_cache()
