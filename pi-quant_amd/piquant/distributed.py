@@ -683,6 +683,145 @@ def ring_chunks(numel: int, world_size: int, packed_bits: int = 8, align: int = 
     return [(bounds[i], bounds[i + 1]) for i in range(world_size)]
 
 
+class _Wire:
+    """What every record of one collective call has in common -- the ops object, the quantized dtype, the rounding mode, the record format
+    (``group_size`` None: 16-byte header + packed bytes; else ``grouped_wire_layout``), the flattened residual (or None) and whether the
+    re-quantizations of partial sums feed it (``requantize``) -- and the only place that knows which ``ops.*`` method a step of a schedule maps
+    to.  The schedules below are written once, on a wire.  ``chunk`` is the ``(begin, end)`` of the values a step works on: where a residual
+    takes part, the step works on that slice of it."""
+
+    def __init__(self, ops, quant_dtype: torch.dtype, round_mode: str, group_size: Optional[int] = None, residual: Optional[torch.Tensor] = None,
+                 requantize: bool = False):
+        self.ops, self.round_mode, self.group_size = ops, round_mode, group_size
+        self.quant_dtype, self.qdt = quant_dtype, torch_to_piquant_dtype(quant_dtype)     # the torch dtype the ops take, its DataType for the lengths
+        self.residual = None if residual is None else residual.view(-1)
+        self.requantize = requantize
+
+    def nbytes(self, numel: int) -> int:
+        """Length of the record of ``numel`` elements."""
+        if self.group_size is None:
+            return _HEADER_BYTES + self.qdt.packed_nbytes(numel)
+        return grouped_wire_layout(numel, self.group_size, self.qdt.bit_size).nbytes
+
+    def encode(self, x, buf, chunk) -> None:
+        if self.group_size is None:
+            self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
+        elif self.residual is None:
+            self.ops.encode_grouped(x, buf, self.quant_dtype, self.round_mode, self.group_size)
+        else:
+            self.ops.encode_grouped_ef(x, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size)
+
+    def encode_batch(self, xs, bufs, chunks) -> None:
+        if self.group_size is None:
+            self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
+        elif self.residual is None:
+            self.ops.encode_batch_grouped(xs, bufs, self.quant_dtype, self.round_mode, self.group_size)
+        else:
+            self.ops.encode_batch_grouped_ef(xs, [self.residual[b:e] for b, e in chunks], bufs, self.quant_dtype, self.round_mode, self.group_size)
+
+    def reduce_encode(self, terms, acc, buf, chunk) -> None:
+        """encode(acc + the records in ``terms``, added in order) into ``buf``, one launch; the residual takes part only with ``requantize``."""
+        if self.group_size is None:
+            self.ops.reduce_encode(terms, acc, buf, self.quant_dtype, self.round_mode)
+        elif not self.requantize:
+            self.ops.reduce_encode_grouped(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size)
+        else:
+            self.ops.reduce_encode_grouped_ef(terms, acc, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size)
+
+    def decode(self, buf, out, op: str) -> None:
+        if self.group_size is None:
+            self.ops.decode(buf, out, self.quant_dtype, op)
+        else:
+            self.ops.decode_grouped(buf, out, self.quant_dtype, op, self.group_size)
+
+    def decode_batch(self, bufs, outs, op: str) -> None:
+        if self.group_size is None:
+            self.ops.decode_batch(bufs, outs, self.quant_dtype, op)
+        else:
+            self.ops.decode_batch_grouped(bufs, outs, self.quant_dtype, op, self.group_size)
+
+    def decode_sum(self, terms, out, op: str) -> None:
+        """The grouped wire's only: nothing sums per-chunk records under a ``reduce_op``."""
+        self.ops.decode_sum_grouped(terms, out, self.quant_dtype, op, self.group_size)
+
+
+class _Chunks(NamedTuple):
+    """The chunk and slot arithmetic of one call: chunk j of the flat tensor, the length of its record, and the slot of the mesh's buffers."""
+    bounds: list             # ring_chunks: (begin, end) per chunk
+    views: list              # flat[begin:end] per chunk
+    nbytes: list             # the record length per chunk (an empty chunk's per-chunk record is its header, its grouped record is empty)
+    slot: int                # the longest record, rounded up: every slot starts on a 16-byte boundary (vector kernels on both sides)
+
+    @classmethod
+    def of(cls, wire: _Wire, flat: torch.Tensor, world: int) -> '_Chunks':
+        bounds = ring_chunks(flat.numel(), world, wire.qdt.bit_size)
+        nbytes = [wire.nbytes(e - b) for b, e in bounds]
+        return cls(bounds, [flat[b:e] for b, e in bounds], nbytes, -(-max(nbytes) // 16) * 16)
+
+    def record(self, buf: torch.Tensor, i: int, j: int) -> torch.Tensor:
+        """The bytes of a record of chunk j in slot i of ``buf``."""
+        return buf[i * self.slot: i * self.slot + self.nbytes[j]]
+
+
+def _ring(wire: _Wire, ch: _Chunks, group, world: int, rank: int, device: torch.device) -> None:
+    """The ring schedule of ``quantized_all_reduce`` on either wire."""
+    nxt = dist.get_global_rank(group, (rank + 1) % world) if group is not None else (rank + 1) % world
+    prv = dist.get_global_rank(group, (rank - 1) % world) if group is not None else (rank - 1) % world
+    views, lens = ch.views, ch.nbytes
+    send, recv, nxt_send = (torch.empty(max(lens), dtype=torch.uint8, device=device) for _ in range(3))
+    # ---- reduce-scatter: after G-1 hops rank r owns the complete sum of chunk (r+1) % G ----
+    # What arrives at a hop is added to the local chunk and the sum is what the next hop forwards: that is ONE call (and one
+    # launch), reduce_encode = quantize(local + dequantize(received)); the local chunk itself need not be updated, the forwarded
+    # buffer carries the sum and every chunk is overwritten by the all-gather at the end.  With a residual the first encode (chunk
+    # ``rank``, this rank's own values) feeds that chunk of it; with ``requantize`` every hop feeds its chunk, each chunk exactly once.
+    n_cur = lens[rank]
+    if views[rank].numel():
+        wire.encode(views[rank], send[:n_cur], ch.bounds[rank])
+    for step in range(world - 1):
+        j = (rank - step - 1) % world
+        _exchange(send[:n_cur], recv[:lens[j]], nxt, prv, group)
+        if views[j].numel():
+            wire.reduce_encode([recv[:lens[j]]], views[j], nxt_send[:lens[j]], ch.bounds[j])
+        send, nxt_send = nxt_send, send
+        n_cur = lens[j]
+    if world == 1 and n_cur:   # test hook only: the encoded chunk makes one trip through the transport, to this rank itself
+        _exchange(send[:n_cur], recv[:n_cur], nxt, prv, group)
+        send, recv = recv, send
+    # ---- all-gather: the finished chunk's bytes (now in `send`) circulate unchanged ----
+    own = (rank + 1) % world
+    assert n_cur == lens[own]
+    if views[own].numel():
+        wire.decode(send[:n_cur], views[own], 'set')   # the owner keeps exactly what everyone else will see
+    for step in range(world - 1):
+        j = (rank - step) % world
+        _exchange(send[:n_cur], recv[:lens[j]], nxt, prv, group)
+        if views[j].numel():
+            wire.decode(recv[:lens[j]], views[j], 'set')
+        send, recv = recv, send          # forward the received bytes as they are
+        n_cur = lens[j]
+
+
+def _mesh_scatter(wire: _Wire, ch: _Chunks, group, world: int, rank: int, device: torch.device):
+    """Reduce-scatter over the mesh up to the owner's step: this rank's values of every peer's non-empty chunk are encoded in ONE batched call
+    (with a residual: feeding the peers' chunks of it), slot j of ``send`` goes to rank j, and what comes back -- the peers' records of this
+    rank's own chunk, in increasing rank order -- is returned."""
+    send = torch.zeros(world * ch.slot, dtype=torch.uint8, device=device)     # zeros: the padding between the records travels
+    recv = torch.empty(world * ch.slot, dtype=torch.uint8, device=device)
+    peers = [j for j in range(world) if j != rank and ch.views[j].numel()]
+    wire.encode_batch([ch.views[j] for j in peers], [ch.record(send, j, j) for j in peers], [ch.bounds[j] for j in peers])
+    _all_to_all(send, recv, group)
+    return [ch.record(recv, i, rank) for i in range(world) if i != rank]
+
+
+def _mesh_gather(wire: _Wire, ch: _Chunks, mine: torch.Tensor, group, world: int, device: torch.device) -> None:
+    """All-gather over the mesh: ``mine`` (one slot holding the owner's finished record) is gathered and every non-empty chunk is stored from
+    the gathered bytes in ONE batched SET decode -- the own chunk included, so all ranks end bit-identical."""
+    gathered = torch.empty(world * ch.slot, dtype=torch.uint8, device=device)   # a fresh buffer: the owner's launch may still be reading the scatter's
+    _all_gather(mine, gathered, group)
+    full = [j for j in range(world) if ch.views[j].numel()]
+    wire.decode_batch([ch.record(gathered, j, j) for j in full], [ch.views[j] for j in full], 'set')
+
+
 def quantized_all_reduce(
     tensor: torch.Tensor,
     *,
@@ -780,54 +919,8 @@ def quantized_all_reduce(
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    ops = _ops or _DeviceOps(ctx)
-    qdt = torch_to_piquant_dtype(quant_dtype)
-    flat = tensor.view(-1)
-    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
-    nxt = dist.get_global_rank(group, (rank + 1) % world) if group is not None else (rank + 1) % world
-    prv = dist.get_global_rank(group, (rank - 1) % world) if group is not None else (rank - 1) % world
-    if group_size is not None:
-        return _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, error_feedback, error_feedback_requantize)
-    max_bytes = max(qdt.packed_nbytes(e - b) for b, e in chunks) + _HEADER_BYTES
-    send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-    recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-
-    def wire(idx):
-        b, e = chunks[idx]
-        return flat[b:e], _HEADER_BYTES + qdt.packed_nbytes(e - b)
-
-    # ---- reduce-scatter: after G-1 hops rank r owns the complete sum of chunk (r+1) % G ----
-    # What arrives at a hop is added to the local chunk and the sum is what the next hop forwards: that is ONE call (and one
-    # launch), reduce_encode = quantize(local + dequantize(received)); the local chunk itself need not be updated, the forwarded
-    # buffer carries the sum and every chunk is overwritten by the all-gather at the end.
-    nxt_send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-    x_first, n_first = wire(rank)
-    if x_first.numel():
-        ops.encode(x_first, send[:n_first], quant_dtype, round_mode)
-    n_cur = n_first
-    for step in range(world - 1):
-        x_recv, n_recv = wire((rank - step - 1) % world)
-        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
-        if x_recv.numel():
-            ops.reduce_encode([recv[:n_recv]], x_recv, nxt_send[:n_recv], quant_dtype, round_mode)
-        send, nxt_send = nxt_send, send
-        n_cur = n_recv
-    if world == 1 and n_cur:   # test hook only: the encoded chunk makes one trip through the transport, to this rank itself
-        _exchange(send[:n_cur], recv[:n_cur], nxt, prv, group)
-        send, recv = recv, send
-
-    # ---- all-gather: the finished chunk's bytes (now in `send`) circulate unchanged ----
-    x_own, n_own = wire((rank + 1) % world)
-    assert n_cur == n_own
-    if x_own.numel():
-        ops.decode(send[:n_own], x_own, quant_dtype, 'set')   # the owner keeps exactly what everyone else will see
-    for step in range(world - 1):
-        x_recv, n_recv = wire((rank - step) % world)
-        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
-        if x_recv.numel():
-            ops.decode(recv[:n_recv], x_recv, quant_dtype, 'set')
-        send, recv = recv, send          # forward the received bytes as they are
-        n_cur = n_recv
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize)
+    _ring(wire, _Chunks.of(wire, tensor.view(-1), world), group, world, rank, tensor.device)
     return tensor
 
 
@@ -888,44 +981,22 @@ def quantized_all_reduce_direct(
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    ops = _ops or _DeviceOps(ctx)
-    qdt = torch_to_piquant_dtype(quant_dtype)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize)
     flat = tensor.view(-1)
-    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
-    slot = _HEADER_BYTES + max(qdt.packed_nbytes(e - b) for b, e in chunks)
-    slot = -(-slot // 16) * 16                       # every slot starts on a 16-byte boundary (vector kernels on both sides)
+    ch = _Chunks.of(wire, flat, world)
     if transport == 'p2p':
         if world == 1:
             raise ValueError("transport='p2p' needs peers (a one-rank group has none)")
-        return _all_reduce_direct_p2p(tensor, flat, chunks, slot, quant_dtype, qdt, round_mode, group, ctx, ops, world, rank, _p2p_timeout_us(timeout))
+        return _all_reduce_direct_p2p(tensor, flat, ch.bounds, ch.slot, quant_dtype, wire.qdt, round_mode, group, ctx, wire.ops, world, rank, _p2p_timeout_us(timeout))
     if transport != 'collective':
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
-    if group_size is not None:
-        return _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, error_feedback, error_feedback_requantize)
-    send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
-    recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
-
-    def wire_len(idx):
-        b, e = chunks[idx]
-        return _HEADER_BYTES + qdt.packed_nbytes(e - b)
-
-    # ---- reduce-scatter over the mesh ----
-    peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
-    ops.encode_batch([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype, round_mode)
-    _all_to_all(send, recv, group)
-    b_own, e_own = chunks[rank]
-    x_own = flat[b_own:e_own]
-    n_own = wire_len(rank)
+    terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
     # ---- the owner's sum, quantized for the all-gather in the same launch (the sum itself is never stored: the final value of the
-    # own chunk, too, comes from decoding the gathered bytes) ----
-    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
-    if x_own.numel():
-        ops.reduce_encode([recv[i * slot: i * slot + n_own] for i in range(world) if i != rank], x_own, mine[:n_own], quant_dtype, round_mode)
-    gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)   # not `recv`: the launch above is still reading it
-    _all_gather(mine, gathered, group)
-    recv = gathered
-    full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
-    ops.decode_batch([recv[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set')
+    # own chunk, too, comes from decoding the gathered bytes); with ``requantize`` it feeds the rank's own chunk of the residual ----
+    mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
+    if ch.views[rank].numel():
+        wire.reduce_encode(terms, ch.views[rank], ch.record(mine, 0, rank), ch.bounds[rank])
+    _mesh_gather(wire, ch, mine, group, world, tensor.device)
     return tensor
 
 
@@ -965,94 +1036,6 @@ def _check_error_feedback_requantize(requantize: bool, residual, group_size, tra
         raise ValueError('error_feedback_requantize=True needs the grouped wire: pass group_size=')
     if transport == 'p2p':
         raise ValueError("error_feedback_requantize=True is not supported with transport='p2p'; use transport='collective'")
-
-
-def _ring_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, nxt, prv, group_size, residual=None, requantize=False):
-    """The ring of ``quantized_all_reduce`` on the grouped wire: the same hops with quantize_grouped / reduce_quantize_grouped (one term) /
-    dequantize_grouped (SET) in place of the per-chunk calls.  ``residual``: the first encode (chunk ``rank``, this rank's own values) is
-    quantize_grouped_ef on that chunk of the residual; no other chunk of it is touched -- unless ``requantize``: then every hop is
-    reduce_quantize_grouped_ef on its chunk of the residual, and each chunk of it is used exactly once."""
-    def wire(idx):
-        b, e = chunks[idx]
-        return flat[b:e], grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
-
-    max_bytes = max(wire(i)[1] for i in range(world))
-    send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-    recv = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-    nxt_send = torch.empty(max_bytes, dtype=torch.uint8, device=tensor.device)
-    # ---- reduce-scatter ----
-    x_first, n_cur = wire(rank)
-    if x_first.numel():
-        if residual is None:
-            ops.encode_grouped(x_first, send[:n_cur], quant_dtype, round_mode, group_size)
-        else:
-            b, e = chunks[rank]
-            ops.encode_grouped_ef(x_first, residual.view(-1)[b:e], send[:n_cur], quant_dtype, round_mode, group_size)
-    for step in range(world - 1):
-        x_recv, n_recv = wire((rank - step - 1) % world)
-        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
-        if x_recv.numel():
-            if requantize:
-                b, e = chunks[(rank - step - 1) % world]
-                ops.reduce_encode_grouped_ef([recv[:n_recv]], x_recv, residual.view(-1)[b:e], nxt_send[:n_recv], quant_dtype, round_mode, group_size)
-            else:
-                ops.reduce_encode_grouped([recv[:n_recv]], x_recv, nxt_send[:n_recv], quant_dtype, round_mode, group_size)
-        send, nxt_send = nxt_send, send
-        n_cur = n_recv
-    if world == 1 and n_cur:   # test hook only: the encoded chunk makes one trip through the transport, to this rank itself
-        _exchange(send[:n_cur], recv[:n_cur], nxt, prv, group)
-        send, recv = recv, send
-    # ---- all-gather ----
-    x_own, n_own = wire((rank + 1) % world)
-    if x_own.numel():
-        ops.decode_grouped(send[:n_own], x_own, quant_dtype, 'set', group_size)
-    for step in range(world - 1):
-        x_recv, n_recv = wire((rank - step) % world)
-        _exchange(send[:n_cur], recv[:n_recv], nxt, prv, group)
-        if x_recv.numel():
-            ops.decode_grouped(recv[:n_recv], x_recv, quant_dtype, 'set', group_size)
-        send, recv = recv, send
-        n_cur = n_recv
-    return tensor
-
-
-def _direct_grouped(tensor, flat, chunks, quant_dtype, qdt, round_mode, group, ops, world, rank, group_size, residual=None, requantize=False):
-    """The mesh schedule of ``quantized_all_reduce_direct`` on the grouped wire: one batched quantize_grouped, the all-to-all, ONE
-    reduce_quantize_grouped over the G-1 received chunks (increasing rank order), the all-gather, one batched dequantize_grouped.
-    ``residual``: the batched encode is quantize_grouped_ef on the peers' chunks of the residual; the rank's own chunk of it is not touched --
-    unless ``requantize``: then the owner's launch is reduce_quantize_grouped_ef on that chunk."""
-    def wire_len(idx):
-        b, e = chunks[idx]
-        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
-
-    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16   # every slot starts on a 16-byte boundary (vector kernels on both sides)
-    send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
-    recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
-    peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
-    if residual is None:
-        ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
-                                 round_mode, group_size)
-    else:
-        rflat = residual.view(-1)
-        ops.encode_batch_grouped_ef([flat[chunks[j][0]:chunks[j][1]] for j in peers], [rflat[chunks[j][0]:chunks[j][1]] for j in peers],
-                                    [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype, round_mode, group_size)
-    _all_to_all(send, recv, group)
-    b_own, e_own = chunks[rank]
-    x_own = flat[b_own:e_own]
-    n_own = wire_len(rank)
-    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
-    if x_own.numel():
-        terms = [recv[i * slot: i * slot + n_own] for i in range(world) if i != rank]
-        if requantize:
-            ops.reduce_encode_grouped_ef(terms, x_own, residual.view(-1)[b_own:e_own], mine[:n_own], quant_dtype, round_mode, group_size)
-        else:
-            ops.reduce_encode_grouped(terms, x_own, mine[:n_own], quant_dtype, round_mode, group_size)
-    gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)   # not `recv`: the launch above is still reading it
-    _all_gather(mine, gathered, group)
-    full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
-    ops.decode_batch_grouped([gathered[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set',
-                             group_size)
-    return tensor
 
 
 def _check_sharded_collective(name: str, tensor: torch.Tensor, group_size, error_feedback) -> None:
@@ -1106,35 +1089,16 @@ def quantized_reduce_scatter(
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
-    qdt = torch_to_piquant_dtype(quant_dtype)
     flat = tensor.view(-1)
-    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
-    b_own, e_own = chunks[rank]
-    x_own = flat[b_own:e_own]
     if world == 1 and not _single_rank_collectives:
-        return x_own
-    ops = _ops or _DeviceOps(ctx)
-
-    def wire_len(idx):
-        b, e = chunks[idx]
-        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
-
-    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16   # every slot starts on a 16-byte boundary (vector kernels on both sides)
-    send = torch.zeros(world * slot, dtype=torch.uint8, device=tensor.device)
-    recv = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
-    peers = [j for j in range(world) if j != rank and chunks[j][1] > chunks[j][0]]
-    if error_feedback is None:
-        ops.encode_batch_grouped([flat[chunks[j][0]:chunks[j][1]] for j in peers], [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype,
-                                 round_mode, group_size)
-    else:
-        rflat = error_feedback.view(-1)
-        ops.encode_batch_grouped_ef([flat[chunks[j][0]:chunks[j][1]] for j in peers], [rflat[chunks[j][0]:chunks[j][1]] for j in peers],
-                                    [send[j * slot: j * slot + wire_len(j)] for j in peers], quant_dtype, round_mode, group_size)
-    _all_to_all(send, recv, group)
-    n_own = wire_len(rank)
-    terms = [recv[i * slot: i * slot + n_own] for i in range(world) if i != rank]
+        b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
+        return flat[b_own:e_own]
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback)
+    ch = _Chunks.of(wire, flat, world)
+    x_own = ch.views[rank]
+    terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
     if x_own.numel() and terms:
-        ops.decode_sum_grouped(terms, x_own, quant_dtype, 'add', group_size)
+        wire.decode_sum(terms, x_own, 'add')
     return x_own
 
 
@@ -1171,30 +1135,12 @@ def quantized_all_gather(
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    ops = _ops or _DeviceOps(ctx)
-    qdt = torch_to_piquant_dtype(quant_dtype)
-    flat = tensor.view(-1)
-    chunks = ring_chunks(flat.numel(), world, qdt.bit_size)
-
-    def wire_len(idx):
-        b, e = chunks[idx]
-        return grouped_wire_layout(e - b, group_size, qdt.bit_size).nbytes
-
-    slot = -(-max(wire_len(j) for j in range(world)) // 16) * 16
-    b_own, e_own = chunks[rank]
-    x_own = flat[b_own:e_own]
-    n_own = wire_len(rank)
-    mine = torch.zeros(slot, dtype=torch.uint8, device=tensor.device)
-    if x_own.numel():
-        if error_feedback is None:
-            ops.encode_grouped(x_own, mine[:n_own], quant_dtype, round_mode, group_size)
-        else:
-            ops.encode_grouped_ef(x_own, error_feedback.view(-1)[b_own:e_own], mine[:n_own], quant_dtype, round_mode, group_size)
-    gathered = torch.empty(world * slot, dtype=torch.uint8, device=tensor.device)
-    _all_gather(mine, gathered, group)
-    full = [j for j in range(world) if chunks[j][1] > chunks[j][0]]
-    ops.decode_batch_grouped([gathered[j * slot: j * slot + wire_len(j)] for j in full], [flat[chunks[j][0]:chunks[j][1]] for j in full], quant_dtype, 'set',
-                             group_size)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback)
+    ch = _Chunks.of(wire, tensor.view(-1), world)
+    mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
+    if ch.views[rank].numel():
+        wire.encode(ch.views[rank], ch.record(mine, 0, rank), ch.bounds[rank])
+    _mesh_gather(wire, ch, mine, group, world, tensor.device)
     return tensor
 
 
