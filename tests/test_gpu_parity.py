@@ -1443,7 +1443,7 @@ def test_batched_dynamic_quantize_and_dequantize_equal_single_calls(O):
         [3_407_872] * 7,                                  # the chunks of an 8-way all-reduce of the BASELINE tensor
         [1, 7, 1000, 4099, 65_536, 300_001, 5],
         [2000 + 17 * i for i in range(19)],               # more than one launch's worth
-        [5_000_000, 100, 5_000_000],                      # too large for a third of the chip each -> single calls
+        [5_000_000, 100, 5_000_000],                      # 15 rounds per block of a third of a 256-CU chip: one launch (a batch is refused from 65 rounds on, kFusedMaxRounds: tests/test_gpu_dynamic_wire_edges.py)
     ]
     for sizes in size_sets:
         for dt_f, fdt in ((0, torch.float32), (1, torch.bfloat16)):
