@@ -381,6 +381,42 @@ PIQUANT_EXPORT void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ct
                                                            piquant_dtype_t dtype_out, size_t numel, size_t group_size, const float* scales,
                                                            const uint8_t* zero_points, uint64_t seed, piquant_reduce_op_t op);
 
+/* THE GROUPED COLLECTIVES' STEPS IN THE ROTATED DOMAIN.  The rotation is linear and the same on every rank for the same seed, so records made by
+ * piquant_hip_quantize_grouped_rotated are summed as they are: only the local accumulator is rotated forward (reduce), or only the finished sum is
+ * rotated back (dequantize-sum) -- ONE rotation a call, whatever the number of terms.  Both calls work in float32 whatever the tensor's type.
+ * Term i is a packed tensor of numel elements with its own per-group parameters input_scales[i] / input_zero_points[i] (one group_size for all).
+ * piquant_hip_reduce_quantize_grouped_rotated writes to out, scales and zero_points exactly the bytes of this composition of public calls:
+ *   1. y = piquant_hip_hadamard_grouped(widen(acc) as float32, forward, seed): a float32 tensor; a bfloat16 acc is widened and never rounded back;
+ *   2. piquant_hip_dequantize_grouped(inputs[i], dtype_out -> float32, ..., PIQUANT_REDUCE_OP_ADD) into y for i = 0 .. count - 1 in order: one
+ *      separately rounded float32 add per term;
+ *   3. piquant_hip_quantize_grouped(y, float32 -> dtype_out, params_given = 0, mode): all three rounding modes, the per-element mode indexing the
+ *      global element.
+ *   acc is const and is NOT written (piquant_hip_reduce_quantize_grouped leaves its accumulator unspecified).  That call rounds the running sum to
+ *   bfloat16 after every term of a bfloat16 accumulator; this one never does: the sum stays float32 until it is quantized.  count == 0 is bit for
+ *   bit piquant_hip_quantize_grouped_rotated.  Every hop of a rotated grouped ring (count = 1); a mesh owner that needs the sum itself takes the call
+ *   below.
+ * piquant_hip_dequantize_sum_grouped_rotated: s = piquant_hip_dequantize_grouped(inputs[0] -> float32, SET) -- the first term is stored, not added
+ *   to zero --, s += piquant_hip_dequantize_grouped(inputs[i] -> float32) for i = 1 .. count - 1 in order, in float32;
+ *   z = piquant_hip_hadamard_grouped(s, inverse, seed).  SET stores convert(z) and never reads out; ADD stores convert(widen(out) + z) with one
+ *   float32 add and one rounding.  count == 1 is bit for bit piquant_hip_dequantize_grouped_rotated; count == 0 aborts like a NULL argument.  The
+ *   owner's step of a rotated grouped reduce-scatter and, followed by piquant_hip_quantize_grouped_rotated, of a rotated grouped mesh all-reduce.
+ * Both: at most 16 terms -- more abort with a message: there is no scratch to spill a float32 running sum into, and the library never allocates.
+ * All six dtype pairs, all eight group sizes; a ragged last group is not rotated (its terms are still added); NaN payloads are not specified.
+ * acc / out and every term's packed bytes 16-byte aligned: ONE streaming launch (no LDS traffic for the butterflies, no scan, no atomics, no grid
+ * barrier); anything else element-aligned: ONE guarded one-wave-per-group launch that writes the same bytes; a float buffer that is not aligned to
+ * its element aborts.  Nothing at or past a tensor's end is read or written; out must not overlap a term or acc.  Device (or pinned) buffers only;
+ * stream-ordered on the context's stream, always behind the previous call whatever piquant_hip_set_independent_calls says; no host
+ * synchronisation, no allocation on the device, the seed travels by value (hipGraph-capturable).  numel == 0 is a no-op that draws no threshold. */
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_rotated(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc,
+                                                                const void* const* inputs, const float* const* input_scales,
+                                                                const uint8_t* const* input_zero_points, size_t count, void* out,
+                                                                piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
+                                                                uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                               const float* const* input_scales, const uint8_t* const* input_zero_points,
+                                                               size_t count, void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size,
+                                                               uint64_t seed, piquant_reduce_op_t op);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

@@ -1,5 +1,5 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, quantize-dequantize, and the three calls of the randomized Hadamard rotation.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, and the reduce and dequantize-sum in the rotated domain.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -369,6 +369,66 @@ void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ctx, const void* 
         StopEventScope completion(ctx);
         IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
         launch_dequantize_grouped_rotated(d, seed, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The two steps of a grouped collective in the rotated domain: ONE launch each, streaming when acc / out and every term's packed bytes are 16-byte
+// aligned, guarded otherwise.  More than kGroupedReduceMaxInputs terms abort: the float32 running sum has nowhere to be spilled to.
+void piquant_hip_reduce_quantize_grouped_rotated(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
+                                                 const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                                 piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                                 uint64_t seed, piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_reduce_quantize_grouped_rotated";
+    const Where w {entry};
+    if (!ctx) bad(w, "context is NULL");
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    check_group_size(group_size, entry);
+    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    check_tensor(w, false, acc, nullptr, out, scales, zero_points);
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, acc, nullptr, out, scales, zero_points, numel);
+    if (reinterpret_cast<uintptr_t>(t.in) % (dtype_acc == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "acc is not aligned to its element size");
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, t.out, numel);
+    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
+    GroupedReduceLaunch r {t, {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)}, {}, static_cast<int>(count)};
+    std::copy(terms.term.begin(), terms.term.end(), r.term);
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // terms and parameters are written by what was enqueued before: always behind it
+        launch_reduce_quantize_grouped_rotated(r, seed, !(terms.aligned && aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
+                                                piquant_dtype_t dtype_out, size_t numel, size_t group_size, uint64_t seed, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_sum_grouped_rotated";
+    const Where w {entry};
+    if (!ctx) bad(w, "context is NULL");
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size, entry);
+    if (count == 0) bad(w, "no terms (count must be at least 1)");
+    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
+    if (!inputs || !input_scales || !input_zero_points) bad(w, "NULL term list");
+    if (numel == 0) return;   // a no-op whatever the buffers are: an empty tensor's address may be NULL
+    if (!out) bad(w, "NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    void* out_dev = device_ptr(w, ctx->resolve_ptr(out));
+    if (reinterpret_cast<uintptr_t>(out_dev) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, out_dev, numel);
+    GroupedDequantSumLaunch d {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, out_dev,
+                               static_cast<int64_t>(numel), {}, static_cast<int>(count)};
+    std::copy(terms.term.begin(), terms.term.end(), d.term);
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
+        launch_dequantize_sum_grouped_rotated(d, seed, !(terms.aligned && aligned16(out_dev)), ctx->stream, ctx->num_cu);
     }
     if (ctx->blocking) wait_stream(ctx);
 }

@@ -307,6 +307,124 @@ dequantize_grouped_rotated_kernel(const uint8_t* __restrict__ in, void* __restri
     }
 }
 
+// ---- reduce_quantize_grouped_rotated: the bytes, scales and zero points of quantize_grouped(y) with computed parameters, y = the float32 forward
+// rotation of the widened accumulator + dequantize_grouped(term_0 -> float32) + ... in order, each term one separately rounded float32 add.  The
+// terms are records of rotated values already, so ONE rotation serves the sum: the accumulator's, in front of the adds (it fixes the roundings).
+// The term loop is reduce_quantize_grouped_kernel's on the float32 tile: term i + 1 in flight while term i is added, and the first term's loads
+// issued in front of the accumulator's, so that the butterflies run under them.  acc is only read; y never reaches memory.
+template <int DT_ACC, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+reduce_quantize_grouped_rotated_kernel(const void* __restrict__ acc, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                       uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0,
+                                       GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    using L = GroupedTermLoad<DT_F32, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // a term's {scale, bias}; then {min, max} of the chunk's groups, then {1/scale, zero point}
+    __shared__ int32_t s_z[WAVES][NG];                 // a term's zero point
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_out[wave];
+    const int count = terms.count;
+
+    u32x4 raw[NV];
+    u32x2 t[NV];
+    L next;
+    if (full && count > 0) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+    grouped_rot_load<DT_ACC, NV>(acc, numel, v0, lane, full, raw, t);
+    grouped_rotate_chunk<BITS, G, false>(raw, numel, g0, full, lane, rot_lo, rot_hi);
+    for (int i = 0; i < count; ++i) {
+        if (full) {
+            const L cur = next;
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            if (i + 1 < count) next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+        } else {
+            grouped_park_term_partial<T>(terms, i, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+        }
+        wave_lds_sync();
+        grouped_add_term<DT_F32, DT_F32, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+        wave_lds_sync();
+    }
+    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a[wave], s_b[wave]);
+}
+
+// ---- dequantize_sum_grouped_rotated: s = dequantize_grouped(term_0 -> float32, SET) + dequantize_grouped(term_i -> float32) for i >= 1 in order,
+// z = the float32 inverse rotation of s; out = convert(z) (SET) or convert(widen(out) + z) (ADD: one float32 add, one rounding).  It is
+// dequantize_grouped_rotated_kernel with a term list: the first term is stored, the others are added (term i + 1 in flight meanwhile), and ONE
+// rotation serves the sum.  terms.count >= 1; with one term the bytes are dequantize_grouped_rotated_kernel's.
+template <int DT_OUT, int BITS, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_sum_grouped_rotated_kernel(void* __restrict__ out, int64_t numel, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi, GroupedTerms terms) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    using L = GroupedTermLoad<DT_F32, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // a term's {scale, bias}
+    __shared__ int32_t s_z[WAVES][NG];                 // a term's zero point
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    const int64_t v0 = g0 * T::V;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    const int64_t gj = g0 + lane;
+    const bool has_group = lane < NG && gj < ngroups;
+    uint8_t* stage = s_in[wave];
+    const int count = terms.count;
+
+    L next;
+    if (full) next.load(terms.in[0], terms.scales[0], terms.zero_points[0], v0, gj, has_group, lane);
+    [[maybe_unused]] u32x4 old[NV];
+    [[maybe_unused]] u32x2 told[NV];
+    if constexpr (OP == OP_ADD) grouped_rot_load<DT_OUT, NV>(out, numel, v0, lane, full, old, told);
+    // term i into the wave's LDS slices, term i + 1 into flight
+    auto stage_term = [&](int i) {
+        if (full) {
+            const L cur = next;
+            grouped_park_term(cur, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+            if (i + 1 < count) next.load(terms.in[i + 1], terms.scales[i + 1], terms.zero_points[i + 1], v0, gj, has_group, lane);
+        } else {
+            grouped_park_term_partial<T>(terms, i, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+        }
+        wave_lds_sync();
+    };
+
+    u32x4 raw[NV];
+    stage_term(0);
+    grouped_set_term<DT_F32, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+    for (int i = 1; i < count; ++i) {
+        wave_lds_sync();   // every lane has read term i - 1
+        stage_term(i);
+        grouped_add_term<DT_F32, DT_F32, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+    }
+    grouped_rotate_chunk<BITS, G, true>(raw, numel, g0, full, lane, rot_lo, rot_hi);
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        if constexpr (OP == OP_ADD) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) raw[r][e] = __float_as_uint(__fadd_rn(__uint_as_float(raw[r][e]), __uint_as_float(old[r][e])));
+        }
+        if constexpr (DT_OUT == DT_F32) {
+            grouped_store_vector<DT_F32>(out, numel, v0 + r * 64 + lane, full, raw[r]);
+        } else {
+            const u32x2 o {f32x2_to_bf16x2_bits(__uint_as_float(raw[r][0]), __uint_as_float(raw[r][1])),
+                           f32x2_to_bf16x2_bits(__uint_as_float(raw[r][2]), __uint_as_float(raw[r][3]))};
+            grouped_rot_store_bf16x4(out, numel, v0 + r * 64 + lane, full, o);
+        }
+    }
+}
+
 // ---- The guarded kernels, for buffers that are not 16-byte aligned: one wave per group, the group's float32 values in the block's LDS, element by
 // element, the same bytes.  Correct, not fast.
 
@@ -413,6 +531,94 @@ dequantize_grouped_rotated_scalar_kernel(const uint8_t* __restrict__ in, void* _
         for (int o = lane; o < len; o += 64) {
             const int64_t bit = (b + o) * BITS;
             buf[o] = dequant_one<FORM>((in[bit >> 3] >> (bit & 7)) & ((1u << BITS) - 1u), p);
+        }
+        if (len == group_size) grouped_rot_guarded<true>(buf, len, lane, rot_lo, rot_hi);
+        else wave_lds_sync();
+        for (int o = lane; o < len; o += 64) {
+            const float z = buf[o];
+            if constexpr (DT_OUT == DT_F32) {
+                float* dst = static_cast<float*>(out);
+                dst[b + o] = OP == OP_ADD ? __fadd_rn(z, dst[b + o]) : z;
+            } else {
+                uint16_t* dst = static_cast<uint16_t*>(out);
+                dst[b + o] = static_cast<uint16_t>(f32_to_bf16_bits(OP == OP_ADD ? __fadd_rn(z, bf16_bits_to_f32(dst[b + o])) : z));
+            }
+        }
+        wave_lds_sync();
+    }
+}
+
+// element o of group g of term i of a term list, dequantized to float32 with the group's parameters (what dequantize_grouped -> float32 stores)
+template <int BITS>
+struct GroupedRotGuardedTerm {
+    static constexpr int FORM = DequantForm<BITS, DT_F32>::value;
+    DequantParams p {};
+    const uint8_t* in;
+
+    __device__ __forceinline__ GroupedRotGuardedTerm(const GroupedTerms& terms, int i, int64_t g) : in(terms.in[i]) {
+        p.scale = terms.scales[i][g];
+        p.zp32 = terms.zero_points[i][g];
+        p.zp64 = p.zp32;
+        p.bias = __fmul_rn(-static_cast<float>(p.zp32), p.scale);
+    }
+
+    __device__ __forceinline__ float operator()(int64_t element) const {
+        const int64_t bit = element * BITS;
+        return dequant_one<FORM>((in[bit >> 3] >> (bit & 7)) & ((1u << BITS) - 1u), p);
+    }
+};
+
+// reduce_quantize_grouped_rotated, guarded: the accumulator's group widened into LDS and rotated (a whole group only), the terms added in order
+// element by element -- a lane adds into the elements it holds --, then the tail of quantize_grouped_rotated_scalar_kernel.
+template <int DT_ACC, int BITS, int MODE>
+__global__ void __launch_bounds__(kGroupedRotGuardedBlock)
+reduce_quantize_grouped_rotated_scalar_kernel(const void* __restrict__ acc, uint8_t* __restrict__ out, int64_t numel, int64_t group_size,
+                                              float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi,
+                                              float threshold, uint32_t seed_lo, uint32_t seed_hi, uint64_t index_base, GroupedTerms terms) {
+    constexpr int PACK = 8 / BITS, QMAX = (1 << BITS) - 1;
+    __shared__ float buf[kGroupedMaxG];
+    const int lane = threadIdx.x;
+    for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int64_t b = g * group_size;
+        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);
+        for (int o = lane; o < len; o += 64) buf[o] = InVec<DT_ACC>::load_scalar(acc, b + o);
+        if (len == group_size) grouped_rot_guarded<false>(buf, len, lane, rot_lo, rot_hi);
+        for (int i = 0; i < terms.count; ++i) {
+            const GroupedRotGuardedTerm<BITS> term(terms, i, g);
+            for (int o = lane; o < len; o += 64) buf[o] = __fadd_rn(term(b + o), buf[o]);
+        }
+        wave_lds_sync();
+        QuantParams p;
+        DequantParams d;   // not used: nothing is read back here
+        grouped_guarded_params<BITS>([&](int o) { return buf[o]; }, len, lane, false, scales, zero_points, g, threshold, seed_lo, seed_hi, index_base, p, d);
+        uint8_t* og = out + b / PACK;   // a group starts on a whole packed byte
+        for (int by = lane; by * PACK < len; by += 64) {
+            uint32_t q = 0;
+            for (int k = 0; k < PACK; ++k) {
+                const int o = by * PACK + k;
+                if (o >= len) break;
+                q |= quant_one<MODE, QMAX>(buf[o], p, static_cast<uint64_t>(b + o)) << (k * BITS);
+            }
+            og[by] = static_cast<uint8_t>(q);
+        }
+        wave_lds_sync();
+    }
+}
+
+// dequantize_sum_grouped_rotated, guarded: the first term stored into LDS, the others added in order, the sum rotated back (a whole group only),
+// then the stores of dequantize_grouped_rotated_scalar_kernel.  terms.count >= 1.
+template <int DT_OUT, int BITS, int OP>
+__global__ void __launch_bounds__(kGroupedRotGuardedBlock)
+dequantize_sum_grouped_rotated_scalar_kernel(void* __restrict__ out, int64_t numel, int64_t group_size, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi,
+                                             GroupedTerms terms) {
+    __shared__ float buf[kGroupedMaxG];
+    const int lane = threadIdx.x;
+    for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+        const int64_t b = g * group_size;
+        const int len = static_cast<int>(b + group_size < numel ? group_size : numel - b);
+        for (int i = 0; i < terms.count; ++i) {
+            const GroupedRotGuardedTerm<BITS> term(terms, i, g);
+            for (int o = lane; o < len; o += 64) buf[o] = i == 0 ? term(b + o) : __fadd_rn(term(b + o), buf[o]);
         }
         if (len == group_size) grouped_rot_guarded<true>(buf, len, lane, rot_lo, rot_hi);
         else wave_lds_sync();

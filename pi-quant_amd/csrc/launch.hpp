@@ -214,6 +214,13 @@ void launch_hadamard_grouped(const GroupedHadamardLaunch& h, bool guarded, hipSt
 void launch_quantize_grouped_rotated(const GroupedQuantLaunch& q, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 // out (op)= the inverse rotation of the float32 grouped dequantize of in, which is never written
 void launch_dequantize_grouped_rotated(const GroupedDequantLaunch& d, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+// The two steps of a grouped collective in the rotated domain (kernels_grouped_rot_reduce.hip, kernels_grouped_rot_dequant_sum.hip), ONE launch
+// each for at most kGroupedReduceMaxInputs terms (the dequantize-sum: at least one); the streaming launches need the accumulator / out and every
+// term's packed bytes 16-byte aligned, `guarded` takes any element alignment: the same bytes.
+// out, scales, zero_points = quantize_grouped(rotate(widen(in)) + sum_i dequantize_grouped(term[i] -> float32)), in float32; in is only read
+void launch_reduce_quantize_grouped_rotated(const GroupedReduceLaunch& r, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+// out (op)= the inverse rotation of the float32 sum of the terms' grouped dequantizes
+void launch_dequantize_sum_grouped_rotated(const GroupedDequantSumLaunch& d, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -550,6 +550,34 @@ class Context:
         C.piquant_hip_dequantize_grouped_rotated(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
                                                  zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, reduce_op.value)
 
+    def reduce_quantize_grouped_rotated_ptr(self, ptr_acc: int, dtype_acc: DataType, ptrs_in, scales_in, zero_points_in, ptr_out: int,
+                                            dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, seed: int,
+                                            round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """out, scales, zero_points = quantize_grouped(rotate(acc) + sum_i dequantize_grouped(input i)) in float32, input i a record of rotated
+        values with its own per-group parameters (``piquant_hip_reduce_quantize_grouped_rotated``: one launch, at most 16 terms).  ``acc`` is only
+        read."""
+        n = len(ptrs_in)
+        assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
+        if n > 16:
+            raise ValueError(f'reduce_quantize_grouped_rotated takes at most 16 terms, not {n}')
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_reduce_quantize_grouped_rotated(self._ctx, ptr_acc, dtype_acc.value, _ptr_array(ptrs_in), _ptr_array(scales_in),
+                                                      _ptr_array(zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                                      zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
+    def dequantize_sum_grouped_rotated_ptr(self, ptrs_in, dtype_in: DataType, scales_ptrs, zero_points_ptrs, ptr_out: int, dtype_out: DataType,
+                                           numel: int, group_size: int, seed: int, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """out (op)= the inverse rotation of the float32 sum of the inputs' ``dequantize_grouped_ptr``, input i a record of rotated values with its
+        own per-group parameters (``piquant_hip_dequantize_sum_grouped_rotated``: one launch, 1 to 16 terms)."""
+        n = len(ptrs_in)
+        assert dtype_in.is_quantized and dtype_out.is_dequantized and n == len(scales_ptrs) == len(zero_points_ptrs) and n > 0
+        if n > 16:
+            raise ValueError(f'dequantize_sum_grouped_rotated takes at most 16 terms, not {n}')
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_sum_grouped_rotated(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(scales_ptrs),
+                                                     _ptr_array(zero_points_ptrs), n, ptr_out, dtype_out.value, numel, group_size,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, reduce_op.value)
+
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                        _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:

@@ -557,6 +557,48 @@ class _DeviceOps:
                                                      [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp,
                                                      self._mode(round_mode), _device_ptrs=True, residual_dtype=_residual_dtype(residual, acc))
 
+    # ---- the grouped wire in the rotated domain (``rotation_seed``): the same records, holding the rotated values ----
+    def encode_grouped_rotated(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
+        sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
+        self._cx(x).quantize_grouped_rotated_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), data, torch_to_piquant_dtype(qdtype), x.numel(), group_size,
+                                                 sc, zp, seed, self._mode(round_mode), _device_ptrs=True)
+
+    def decode_grouped_rotated(self, buf: torch.Tensor, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int, seed: int) -> None:
+        sc, zp, data = self._record(buf, out.numel(), qdtype, group_size)
+        self._cx(out).dequantize_grouped_rotated_ptr(data, torch_to_piquant_dtype(qdtype), out.data_ptr(), torch_to_piquant_dtype(out.dtype), out.numel(),
+                                                     group_size, sc, zp, seed, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+
+    def encode_batch_grouped_rotated(self, xs, bufs, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
+        """encode_grouped_rotated(xs[i], bufs[i]) for all i, one launch EACH: there is no batched rotated quantize yet."""
+        for x, b in zip(xs, bufs):
+            self.encode_grouped_rotated(x, b, qdtype, round_mode, group_size, seed)
+
+    def decode_batch_grouped_rotated(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int, seed: int) -> None:
+        """decode_grouped_rotated(bufs[i], outs[i]) for all i, one launch EACH: there is no batched rotated dequantize yet."""
+        for b, o in zip(bufs, outs):
+            self.decode_grouped_rotated(b, o, qdtype, reduce_op, group_size, seed)
+
+    def reduce_encode_grouped_rotated(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int,
+                                      seed: int) -> None:
+        """encode_grouped(rotate(acc) + the wire buffers, added in order, in float32) into ``buf`` as one launch (at most 16 buffers; ``acc`` is
+        only read)."""
+        n = acc.numel()
+        recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+        sc, zp, data = self._record(buf, n, qdtype, group_size)
+        self._cx(acc).reduce_quantize_grouped_rotated_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [r[2] for r in recs], [r[0] for r in recs],
+                                                          [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp, seed,
+                                                          self._mode(round_mode), _device_ptrs=True)
+
+    def decode_sum_grouped_rotated(self, bufs, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int, seed: int) -> None:
+        """out (op)= the inverse rotation of the float32 sum of the wire buffers, added in order: one launch (at most 16 buffers) and one pass
+        over ``out``."""
+        if bufs:
+            n = out.numel()
+            recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+            self._cx(out).dequantize_sum_grouped_rotated_ptr([r[2] for r in recs], torch_to_piquant_dtype(qdtype), [r[0] for r in recs],
+                                                             [r[1] for r in recs], out.data_ptr(), torch_to_piquant_dtype(out.dtype), n, group_size, seed,
+                                                             _REDUCE_OPS[reduce_op], _device_ptrs=True)
+
 
 def _exchange(send: torch.Tensor, recv: torch.Tensor, nxt: int, prv: int, group) -> None:
     """Send `send` to the next rank of the ring while receiving `recv` from the previous one.  RCCL (backend nccl)
@@ -686,13 +728,15 @@ def ring_chunks(numel: int, world_size: int, packed_bits: int = 8, align: int = 
 class _Wire:
     """What every record of one collective call has in common -- the ops object, the quantized dtype, the rounding mode, the record format
     (``group_size`` None: 16-byte header + packed bytes; else ``grouped_wire_layout``), the flattened residual (or None) and whether the
-    re-quantizations of partial sums feed it (``requantize``) -- and the only place that knows which ``ops.*`` method a step of a schedule maps
+    re-quantizations of partial sums feed it (``requantize``), the rotation's seed (``rotation_seed``, or None: the grouped wire then carries the
+    records of the rotated values, with no residual) -- and the only place that knows which ``ops.*`` method a step of a schedule maps
     to.  The schedules below are written once, on a wire.  ``chunk`` is the ``(begin, end)`` of the values a step works on: where a residual
     takes part, the step works on that slice of it."""
 
     def __init__(self, ops, quant_dtype: torch.dtype, round_mode: str, group_size: Optional[int] = None, residual: Optional[torch.Tensor] = None,
-                 requantize: bool = False):
+                 requantize: bool = False, rotation_seed: Optional[int] = None):
         self.ops, self.round_mode, self.group_size = ops, round_mode, group_size
+        self.seed = rotation_seed
         self.quant_dtype, self.qdt = quant_dtype, torch_to_piquant_dtype(quant_dtype)     # the torch dtype the ops take, its DataType for the lengths
         self.residual = None if residual is None else residual.view(-1)
         self.requantize = requantize
@@ -706,6 +750,8 @@ class _Wire:
     def encode(self, x, buf, chunk) -> None:
         if self.group_size is None:
             self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
+        elif self.seed is not None:
+            self.ops.encode_grouped_rotated(x, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif self.residual is None:
             self.ops.encode_grouped(x, buf, self.quant_dtype, self.round_mode, self.group_size)
         else:
@@ -714,6 +760,8 @@ class _Wire:
     def encode_batch(self, xs, bufs, chunks) -> None:
         if self.group_size is None:
             self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
+        elif self.seed is not None:
+            self.ops.encode_batch_grouped_rotated(xs, bufs, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif self.residual is None:
             self.ops.encode_batch_grouped(xs, bufs, self.quant_dtype, self.round_mode, self.group_size)
         else:
@@ -723,26 +771,47 @@ class _Wire:
         """encode(acc + the records in ``terms``, added in order) into ``buf``, one launch; the residual takes part only with ``requantize``."""
         if self.group_size is None:
             self.ops.reduce_encode(terms, acc, buf, self.quant_dtype, self.round_mode)
+        elif self.seed is not None:
+            self.ops.reduce_encode_grouped_rotated(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif not self.requantize:
             self.ops.reduce_encode_grouped(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size)
         else:
             self.ops.reduce_encode_grouped_ef(terms, acc, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size)
 
+    def owner_encode(self, terms, acc, buf, chunk) -> None:
+        """The mesh owner's step: ``reduce_encode``.  In the rotated domain it is the reduce-scatter's step followed by the all-gather's --
+        ``decode_sum(terms, acc, 'add')``, which leaves the sum in ``acc``, then ``encode(acc)`` -- two launches: only so do reduce-scatter +
+        all-gather leave the bytes of the direct all-reduce (the one-launch rotated reduce keeps the sum in the rotated domain, the two halves
+        pass it through the original one and the tensor's type: equal in exact arithmetic, not in float32)."""
+        if self.seed is None:
+            self.reduce_encode(terms, acc, buf, chunk)
+        else:
+            if terms:
+                self.decode_sum(terms, acc, 'add')
+            self.encode(acc, buf, chunk)
+
     def decode(self, buf, out, op: str) -> None:
         if self.group_size is None:
             self.ops.decode(buf, out, self.quant_dtype, op)
+        elif self.seed is not None:
+            self.ops.decode_grouped_rotated(buf, out, self.quant_dtype, op, self.group_size, self.seed)
         else:
             self.ops.decode_grouped(buf, out, self.quant_dtype, op, self.group_size)
 
     def decode_batch(self, bufs, outs, op: str) -> None:
         if self.group_size is None:
             self.ops.decode_batch(bufs, outs, self.quant_dtype, op)
+        elif self.seed is not None:
+            self.ops.decode_batch_grouped_rotated(bufs, outs, self.quant_dtype, op, self.group_size, self.seed)
         else:
             self.ops.decode_batch_grouped(bufs, outs, self.quant_dtype, op, self.group_size)
 
     def decode_sum(self, terms, out, op: str) -> None:
         """The grouped wire's only: nothing sums per-chunk records under a ``reduce_op``."""
-        self.ops.decode_sum_grouped(terms, out, self.quant_dtype, op, self.group_size)
+        if self.seed is not None:
+            self.ops.decode_sum_grouped_rotated(terms, out, self.quant_dtype, op, self.group_size, self.seed)
+        else:
+            self.ops.decode_sum_grouped(terms, out, self.quant_dtype, op, self.group_size)
 
 
 class _Chunks(NamedTuple):
@@ -835,6 +904,7 @@ def quantized_all_reduce(
     group_size: Optional[int] = None,
     error_feedback: Optional[torch.Tensor] = None,
     error_feedback_requantize: bool = False,
+    rotation_seed: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -873,6 +943,22 @@ def quantized_all_reduce(
     results differs from the sum of the inputs by what the ranks' residuals hold (up to roundings in the tensor's dtype): the all-reduce is
     conservative over steps.  ValueError before anything moves without ``error_feedback``, without ``group_size`` or with ``transport='p2p'``.
 
+    ``rotation_seed`` (``group_size`` only; default None: every byte, every launch and every ``_ops`` call as without it): an int, taken modulo
+    2^64, runs the whole collective in the domain of the randomized Hadamard rotation (``piquant.torch.hadamard_grouped``), for heavy-tailed
+    values whose outliers would stretch their groups' steps.  Every encode becomes ``quantize_grouped_rotated``; every hop of the ring ONE
+    ``reduce_quantize_grouped_rotated`` launch (the received record holds rotated values already: only the local chunk is rotated, and the sum
+    stays float32 until it is quantized, also for a bfloat16 tensor); the mesh owner's step ``dequantize_sum_grouped_rotated(..., 'add')`` of
+    the world - 1 received records into the own chunk followed by ``quantize_grouped_rotated`` of it -- the reduce-scatter's step and the
+    all-gather's, two launches, so that ``quantized_reduce_scatter`` + ``quantized_all_gather`` leave exactly the bytes of the direct
+    all-reduce (the one-launch reduce would not: it keeps the sum in the rotated domain); every decode ``dequantize_grouped_rotated`` 'set' of
+    the same gathered bytes on every rank, the owner included: all ranks end bit-identical.  The wire format is unchanged; ``ring_chunks`` keeps
+    every interior boundary on a multiple of 4096 elements, so every chunk rotates exactly as the whole tensor does.  ALL RANKS MUST PASS THE SAME
+    SEED: the library does not check it, and ranks that disagree sum values of different domains.  There is no batched rotated launch yet: the
+    mesh encodes its world - 1 chunks, and decodes its world chunks, with one launch each.  uint2 records gain nothing from the rotation in the
+    all-reduce.  ValueError before anything moves: without ``group_size``, with ``transport='p2p'``, with ``error_feedback``
+    (the residual lives in the original domain; feeding it needs a kernel that rotates both ways), and in the direct schedule with more than
+    17 ranks (the owner's one launch sums at most 16 records).
+
     ``transport='p2p'`` (``algorithm='direct'`` only, one node; EXPERIMENTAL until it has run between two GPUs): no collective at all -- the
     encode kernels store into the peers' receive buffers over xGMI and flags order the steps (``quantized_all_reduce_direct``).  ``timeout``
     (seconds; default ``PIQUANT_P2P_TIMEOUT_S`` or 10 minutes) bounds every wait for a peer; a rank that is later than that does not fault the
@@ -909,17 +995,18 @@ def quantized_all_reduce(
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
     _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
+    seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
-                                           group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize, _ops=_ops,
-                                           _single_rank_collectives=_single_rank_collectives)
+                                           group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize,
+                                           rotation_seed=rotation_seed, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize, seed)
     _ring(wire, _Chunks.of(wire, tensor.view(-1), world), group, world, rank, tensor.device)
     return tensor
 
@@ -936,6 +1023,7 @@ def quantized_all_reduce_direct(
     group_size: Optional[int] = None,
     error_feedback: Optional[torch.Tensor] = None,
     error_feedback_requantize: bool = False,
+    rotation_seed: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -971,17 +1059,24 @@ def quantized_all_reduce_direct(
     ``error_feedback_requantize``: steps 3-4 become one ``reduce_quantize_grouped_ef`` launch on the rank's own chunk of the residual (added
     after the G-1 received chunks), which then holds what the owner's quantization lost; every slice of the residual is used.  A residual
     belongs to one (world size, rank, algorithm, ``error_feedback_requantize``).
+
+    ``rotation_seed``: the rotated domain of ``quantized_all_reduce`` (the same seed on all ranks; not checked) -- step 1 is world - 1
+    ``quantize_grouped_rotated`` launches, steps 3-4 ``dequantize_sum_grouped_rotated(..., 'add')`` into the own chunk and
+    ``quantize_grouped_rotated`` of it (the steps of ``quantized_reduce_scatter`` and ``quantized_all_gather``: the same bytes), the decode world
+    ``dequantize_grouped_rotated`` launches.  At most 17 ranks; not with ``error_feedback`` or ``transport='p2p'``.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
     _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
+    seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
+    _check_rotated_terms(seed, world, 'the direct schedule')
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize, seed)
     flat = tensor.view(-1)
     ch = _Chunks.of(wire, flat, world)
     if transport == 'p2p':
@@ -995,7 +1090,7 @@ def quantized_all_reduce_direct(
     # own chunk, too, comes from decoding the gathered bytes); with ``requantize`` it feeds the rank's own chunk of the residual ----
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
     if ch.views[rank].numel():
-        wire.reduce_encode(terms, ch.views[rank], ch.record(mine, 0, rank), ch.bounds[rank])
+        wire.owner_encode(terms, ch.views[rank], ch.record(mine, 0, rank), ch.bounds[rank])
     _mesh_gather(wire, ch, mine, group, world, tensor.device)
     return tensor
 
@@ -1038,6 +1133,32 @@ def _check_error_feedback_requantize(requantize: bool, residual, group_size, tra
         raise ValueError("error_feedback_requantize=True is not supported with transport='p2p'; use transport='collective'")
 
 
+_ROTATED_MAX_TERMS = 16   # piquant_hip_reduce_quantize_grouped_rotated / piquant_hip_dequantize_sum_grouped_rotated: one launch, no spill
+
+
+def _check_rotation_seed(seed, group_size, transport: str, error_feedback) -> Optional[int]:
+    """ValueError before anything moves: a rotation without the grouped wire, over the peer-to-peer transport or with a residual (which lives in
+    the original domain: feeding it needs a kernel that rotates both ways).  Returns the seed modulo 2^64, or None."""
+    if seed is None:
+        return None
+    if not isinstance(seed, int) or isinstance(seed, bool):
+        raise ValueError(f'rotation_seed must be an int or None, got {seed!r}')
+    if group_size is None:
+        raise ValueError('rotation_seed= needs the grouped wire: pass group_size= (whole groups are what is rotated)')
+    if transport == 'p2p':
+        raise ValueError("rotation_seed= is not supported with transport='p2p'; use transport='collective'")
+    if error_feedback is not None:
+        raise ValueError('rotation_seed= is not supported with error_feedback= (the residual lives in the original domain)')
+    return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def _check_rotated_terms(seed, world: int, what: str) -> None:
+    """ValueError before anything moves: the owner's step of a rotated mesh schedule is one launch over world - 1 records, at most 16."""
+    if seed is not None and world - 1 > _ROTATED_MAX_TERMS:
+        raise ValueError(f'rotation_seed= with {what} takes at most {_ROTATED_MAX_TERMS + 1} ranks (the owner sums world - 1 records in one launch), '
+                         f'got {world}')
+
+
 def _check_sharded_collective(name: str, tensor: torch.Tensor, group_size, error_feedback) -> None:
     """ValueError before anything moves, for ``quantized_reduce_scatter`` and ``quantized_all_gather``: the tensor, a group size that is no group
     size (``None`` included: they have the grouped wire only) and a residual that does not match the tensor."""
@@ -1058,6 +1179,7 @@ def quantized_reduce_scatter(
     ctx: Optional[Context] = None,
     group_size: int = 128,
     error_feedback: Optional[torch.Tensor] = None,
+    rotation_seed: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1083,17 +1205,24 @@ def quantized_reduce_scatter(
     ``quantized_all_reduce(algorithm='direct', group_size=group_size)``: that schedule's ``reduce_quantize_grouped`` is defined as these ADDs
     followed by ``quantize_grouped``.
 
+    ``rotation_seed`` (the same int on all ranks; not checked): the peers' chunks are encoded by ``quantize_grouped_rotated`` (one launch each),
+    and step 3 is ONE ``dequantize_sum_grouped_rotated(..., 'add')`` launch: the received records are summed in float32 in the rotated domain
+    and the sum is rotated back once and added into the own chunk.  Followed by ``quantized_all_gather`` with the same seed it leaves exactly the bytes
+    of ``quantized_all_reduce(algorithm='direct', rotation_seed=...)``, whose owner's step is these two.  At most 17 ranks; not with ``error_feedback``.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
     of this module's multi-GPU paths.)"""
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
+    seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
+    _check_rotated_terms(seed, world, 'quantized_reduce_scatter')
     flat = tensor.view(-1)
     if world == 1 and not _single_rank_collectives:
         b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
         return flat[b_own:e_own]
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, rotation_seed=seed)
     ch = _Chunks.of(wire, flat, world)
     x_own = ch.views[rank]
     terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
@@ -1111,6 +1240,7 @@ def quantized_all_gather(
     ctx: Optional[Context] = None,
     group_size: int = 128,
     error_feedback: Optional[torch.Tensor] = None,
+    rotation_seed: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1128,14 +1258,18 @@ def quantized_all_gather(
     ``quantized_reduce_scatter`` (which uses the peers' chunks) and this call unless that is the intent -- together the two touch every chunk
     exactly once, as ``quantized_all_reduce`` with ``error_feedback_requantize`` does.
 
+    ``rotation_seed`` (the same int on all ranks; not checked): step 1 is ``quantize_grouped_rotated``, step 3 one
+    ``dequantize_grouped_rotated(..., 'set')`` launch per chunk.  Not with ``error_feedback``.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
     _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
+    seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, rotation_seed=seed)
     ch = _Chunks.of(wire, tensor.view(-1), world)
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
     if ch.views[rank].numel():

@@ -635,10 +635,26 @@ def reduce_quantize_grouped(acc: torch.Tensor, tensors, scales, zero_points, *, 
     return _reduce_quantize_grouped(acc, _NA, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points)
 
 
-def _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points):
-    """``reduce_quantize_grouped`` (``residual`` is ``_NA``) and ``reduce_quantize_grouped_ef``: the second checks the residual and makes the ``_ef`` call."""
+def reduce_quantize_grouped_rotated(acc: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int = 128, seed=_NA,
+                                    round_mode: str = 'nearest', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                                    out_scales: Optional[torch.Tensor] = None,
+                                    out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``reduce_quantize_grouped`` in the rotated domain, in one launch (at most 16 terms; more raise): the terms are records made by
+    ``quantize_grouped_rotated`` with the same ``seed``, so only ``acc`` is rotated.  Bit for bit ``y = hadamard_grouped(acc.float(), seed=seed)``,
+    ``dequantize_grouped(tensors[i], ..., dtype=torch.float32, reduce_op='add', out=y)`` for every i in order, ``quantize_grouped(y)``: the sum
+    stays float32 until it is quantized, also for a bfloat16 ``acc``, which -- unlike ``reduce_quantize_grouped``'s -- is only read.  No terms is
+    ``quantize_grouped_rotated(acc)``.  Returns (out, out_scales, out_zero_points) (``include/piquant_hip.h``,
+    piquant_hip_reduce_quantize_grouped_rotated)."""
+    seed = _check_seed(seed)
+    return _reduce_quantize_grouped(acc, _NA, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points, seed)
+
+
+def _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points, seed=None):
+    """``reduce_quantize_grouped`` (``residual`` is ``_NA``) and ``reduce_quantize_grouped_ef``: the second checks the residual and makes the ``_ef`` call.
+    With a ``seed`` (and no residual): ``reduce_quantize_grouped_rotated``, which takes at most 16 terms."""
     _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
     tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    _require(seed is None or len(tensors) <= 16, f'reduce_quantize_grouped_rotated takes at most 16 terms, got {len(tensors)}')
     _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
              f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
     if residual is not _NA:
@@ -653,7 +669,11 @@ def _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype,
     out = _packed_out(out, dtype, acc, acc.device)
     out_scales, out_zero_points = _group_params_of(out_scales, out_zero_points, numel, group_size, acc.device, 'out_scales and out_zero_points')
     ctx = _ctx_for(acc, ctx)
-    if residual is _NA:
+    if seed is not None:
+        ctx.reduce_quantize_grouped_rotated_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), _ptrs(tensors), _ptrs(scales), _ptrs(zero_points),
+                                                out.data_ptr(), qdt, numel, group_size, out_scales.data_ptr(), out_zero_points.data_ptr(), seed,
+                                                _ROUND_MODES[round_mode], _device_ptrs=True)
+    elif residual is _NA:
         ctx.reduce_quantize_grouped_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), _ptrs(tensors), _ptrs(scales), _ptrs(zero_points), out.data_ptr(), qdt,
                                         numel, group_size, out_scales.data_ptr(), out_zero_points.data_ptr(), _ROUND_MODES[round_mode], _device_ptrs=True)
     else:
@@ -891,9 +911,27 @@ def dequantize_sum_grouped(tensors, scales, zero_points, *, dtype: torch.dtype, 
     out=out)`` for every i in order, the first with ``reduce_op`` and the others with 'add': the running sum is rounded to ``dtype`` after every
     term.  ``'add'`` accumulates into ``out=``; ``'set'`` never reads it.  Returns ``out`` (``include/piquant_hip.h``,
     piquant_hip_dequantize_sum_grouped)."""
+    return _dequantize_sum_grouped(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, out, quant_dtype, shape)
+
+
+def dequantize_sum_grouped_rotated(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, seed=_NA, reduce_op: str = 'set',
+                                   ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, quant_dtype: Optional[torch.dtype] = None,
+                                   shape=None) -> torch.Tensor:
+    """``dequantize_sum_grouped`` in the rotated domain, in one launch (1 to 16 terms; more raise): the terms are records made by
+    ``quantize_grouped_rotated`` or ``reduce_quantize_grouped_rotated`` with the same ``seed``; they are summed in float32 (the first stored, the
+    others added in order) and only the sum is rotated back.  ``'set'`` stores it converted to ``dtype`` and never reads ``out``; ``'add'`` adds it
+    into ``out=`` with one float32 add and one rounding.  One term is ``dequantize_grouped_rotated``.  Returns ``out``
+    (``include/piquant_hip.h``, piquant_hip_dequantize_sum_grouped_rotated)."""
+    seed = _check_seed(seed)
+    return _dequantize_sum_grouped(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, out, quant_dtype, shape, seed)
+
+
+def _dequantize_sum_grouped(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, out, quant_dtype, shape, seed=None):
+    """``dequantize_sum_grouped`` and, with a ``seed``, ``dequantize_sum_grouped_rotated``, which takes at most 16 terms."""
     _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
     tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
     _require(len(tensors) > 0, 'dequantize_sum_grouped needs at least one term')
+    _require(seed is None or len(tensors) <= 16, f'dequantize_sum_grouped_rotated takes at most 16 terms, got {len(tensors)}')
     _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
              f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
     _require(out is not None or reduce_op != 'add', "reduce_op='add' accumulates into out=; pass the accumulator tensor")
@@ -905,6 +943,10 @@ def dequantize_sum_grouped(tensors, scales, zero_points, *, dtype: torch.dtype, 
     _check_grouped_terms(tensors, scales, zero_points, dtype_in, repeat(numel), group_size, first.device)
     out = _float_out(out, reduce_op, dtype, logical_shape, numel, first.device)
     ctx = _ctx_for(first, ctx)
+    if seed is not None:
+        ctx.dequantize_sum_grouped_rotated_ptr(_ptrs(tensors), dtype_in, _ptrs(scales), _ptrs(zero_points), out.data_ptr(),
+                                               torch_to_piquant_dtype(out.dtype), numel, group_size, seed, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+        return out
     ctx.dequantize_sum_grouped_ptr(_ptrs(tensors), dtype_in, _ptrs(scales), _ptrs(zero_points), out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel,
                                    group_size, _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return out

@@ -46,7 +46,12 @@ hadamard_grouped into a scratch tensor + quantize_grouped; dequantize_grouped_ro
 hadamard_grouped in place; all in the same run, with the byte ratio of each row and the target fused / composition <= 1.15 x that ratio.  Writes
 profiles/grouped_rot_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows rot_reduce: the two steps of a grouped collective in the rotated domain (G = 128), each next to the composition of public calls that defines
+it, in the same run: reduce_quantize_grouped_rotated (fp32 + 1 and + 7 uint8 terms, fp32 + 7 uint4 terms, bf16 + 1 and + 7 uint4 terms) and
+dequantize_sum_grouped_rotated (1 and 7 uint8 terms into fp32, SET and ADD; 7 uint4 terms into bf16, ADD).  Every fused row must be faster than its
+composition; fused / composition against the byte ratio is reported as met or missed.  Writes profiles/grouped_rot_reduce_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -705,18 +710,129 @@ def rot_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
     return rows
 
 
+def rot_reduce_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
+    """the two steps of a grouped collective in the rotated domain, each next to the composition of public calls that defines it:
+    reduce_quantize_grouped_rotated against hadamard_grouped into a float32 scratch (a bfloat16 accumulator is widened into it first), k grouped
+    dequantize ADD launches and quantize_grouped; dequantize_sum_grouped_rotated against dequantize_sum_grouped into a float32 scratch,
+    hadamard_grouped inverse in place and the add or the convert (float32 SET: the scratch is out itself)"""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(10)
+    f32 = piquant.DataType.F32
+
+    def ratio(fr, cr):
+        fr["over_composition"] = round(fr["us"] / cr["us"], 3)
+        fr["faster_than_composition"] = bool(fr["us"] < cr["us"])
+        fr["bytes_over_composition"] = round(fr["bytes"] / cr["bytes"], 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}; faster than its composition: {fr['faster_than_composition']}", flush=True)
+
+    def make_terms(nbuf, k, nq, bits):
+        terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        return terms, tsc, tzp
+
+    for fname, qname, k in (("f32", "uint8", 1), ("f32", "uint8", 7), ("f32", "uint4", 7), ("bf16", "uint4", 1), ("bf16", "uint4", 7)):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(NUMEL)
+        rec = nq + 5 * ng
+        fused_bytes = NUMEL * esize + (k + 1) * rec
+        comp_bytes = (6 * NUMEL if fname == "bf16" else 0) + 8 * NUMEL + k * (rec + 8 * NUMEL) + 4 * NUMEL + rec
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        accs = [torch.empty(NUMEL, device=dev).normal_(generator=g).to(tdt) for _ in range(nbuf)]
+        scratch = [torch.empty(NUMEL, device=dev) for _ in range(nbuf)]
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        terms, tsc, tzp = make_terms(nbuf, k, nq, bits)
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.reduce_quantize_grouped_rotated_ptr(accs[i].data_ptr(), fdt, [t.data_ptr() for t in terms[i]], [t.data_ptr() for t in tsc[i]],
+                                                    [t.data_ptr() for t in tzp[i]], outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), seed,
+                                                    piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def composition(i):
+            src = accs[i]
+            if fname == "bf16":
+                scratch[i].copy_(accs[i])
+                src = scratch[i]
+            ctx.hadamard_grouped_ptr(src.data_ptr(), f32, scratch[i].data_ptr(), NUMEL, G, seed, False, _device_ptrs=True)
+            for t, s_, z_ in zip(terms[i], tsc[i], tzp[i]):
+                ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, scratch[i].data_ptr(), f32, NUMEL, G, s_.data_ptr(), z_.data_ptr(), piquant.ReduceOp.ADD,
+                                           _device_ptrs=True)
+            ctx.quantize_grouped_ptr(scratch[i].data_ptr(), f32, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                     piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        pair = f"{fname}+{k}x{qname}->{qname}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("rot_reduce_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("reduce_quantize_grouped_rotated", pair, G, us_f, fused_bytes, s_f)
+        ratio(fr, cr)
+        rows += [cr, fr]
+        del accs, scratch, outs, sc, zs, terms, tsc, tzp
+        torch.cuda.empty_cache()
+
+    for fname, qname, k, op in (("f32", "uint8", 1, "set"), ("f32", "uint8", 1, "add"), ("f32", "uint8", 7, "set"), ("f32", "uint8", 7, "add"),
+                                ("bf16", "uint4", 7, "add")):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        rop = piquant.ReduceOp.ADD if op == "add" else piquant.ReduceOp.SET
+        nq = qdt.packed_nbytes(NUMEL)
+        rec = nq + 5 * ng
+        fbytes = NUMEL * esize
+        fused_bytes = k * rec + fbytes * (2 if op == "add" else 1)
+        direct = fname == "f32" and op == "set"      # the scratch is out itself: two launches
+        comp_bytes = k * rec + 4 * NUMEL + 8 * NUMEL + (0 if direct else 4 * NUMEL + 2 * fbytes)
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        outs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=g).to(tdt) for _ in range(nbuf)]
+        scratch = outs if direct else [torch.empty(NUMEL, device=dev) for _ in range(nbuf)]
+        terms, tsc, tzp = make_terms(nbuf, k, nq, bits)
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            ctx.dequantize_sum_grouped_rotated_ptr([t.data_ptr() for t in terms[i]], qdt, [t.data_ptr() for t in tsc[i]], [t.data_ptr() for t in tzp[i]],
+                                                   outs[i].data_ptr(), fdt, NUMEL, G, seed, rop, _device_ptrs=True)
+
+        def composition(i):
+            ctx.dequantize_sum_grouped_ptr([t.data_ptr() for t in terms[i]], qdt, [t.data_ptr() for t in tsc[i]], [t.data_ptr() for t in tzp[i]],
+                                           scratch[i].data_ptr(), f32, NUMEL, G, piquant.ReduceOp.SET, _device_ptrs=True)
+            ctx.hadamard_grouped_ptr(scratch[i].data_ptr(), f32, scratch[i].data_ptr(), NUMEL, G, seed, True, _device_ptrs=True)
+            if not direct:
+                outs[i].add_(scratch[i]) if op == "add" else outs[i].copy_(scratch[i])
+
+        pair = f"{fname}{'+=' if op == 'add' else '='}{k}x{qname}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("rot_dequant_sum_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("dequantize_sum_grouped_rotated", pair, G, us_f, fused_bytes, s_f)
+        ratio(fr, cr)
+        rows += [cr, fr]
+        del outs, scratch, terms, tsc, tzp
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot"), default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce"),
+                    default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
                                                    "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
-                                                   "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json"}[args.rows])
+                                                   "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json",
+                                                   "rot_reduce": "grouped_rot_reduce_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -742,6 +858,8 @@ def main():
         rows = dequant_sum_rows(ctx, dev, stream, args)
     if args.rows == "rot":
         rows = rot_rows(ctx, dev, stream, args)
+    if args.rows == "rot_reduce":
+        rows = rot_reduce_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
