@@ -417,6 +417,42 @@ PIQUANT_EXPORT void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t
                                                                size_t count, void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size,
                                                                uint64_t seed, piquant_reduce_op_t op);
 
+/* ERROR FEEDBACK IN THE ROTATED DOMAIN.  The rotation is orthogonal and linear, and for one seed it is the same on every step and every rank, so
+ * the residual of error feedback need never leave the rotated domain: sum_t D_t = sum_t H(x_t) + R_0 - R_K holds there and maps back through the
+ * inverse rotation unchanged.  `residual` is numel float32 values -- float32 also for a bfloat16 tensor -- that belong to ONE (seed, group size):
+ * a record of rotated values, not interchangeable with the residual of piquant_hip_quantize_grouped_ef.
+ * piquant_hip_quantize_grouped_rotated_ef writes exactly the packed bytes, scales, zero points and residual of this composition of public calls:
+ *   1. Y = piquant_hip_hadamard_grouped(widen(in) as float32, forward, seed): a bfloat16 tensor is widened and never rounded back; a ragged last
+ *      group is not rotated;
+ *   2. piquant_hip_quantize_grouped_ef(Y, float32, residual, ...): per element y = rn_f32(Y + R); quantize_grouped(y) with computed parameters;
+ *      d = the float32 SET dequantize; R <- rn_f32(y - d).
+ *   It never writes Y, and `in` is only read.
+ * piquant_hip_reduce_quantize_grouped_rotated_ef writes exactly what this sequence writes:
+ *   1. steps 1 and 2 of piquant_hip_reduce_quantize_grouped_rotated: Y = the rotation of widen(acc), then one separately rounded float32
+ *      dequantize ADD per term, in order;
+ *   2. piquant_hip_quantize_grouped_ef(Y, float32, residual, ...): the residual is added BEHIND the terms, as in
+ *      piquant_hip_reduce_quantize_grouped_ef.
+ *   acc is const and only read.  count == 0 is bit for bit the first call; more than 16 terms abort with a message.
+ * Both: all six dtype pairs, all eight group sizes, all three rounding modes -- one threshold per call, which
+ * piquant_hip_set_stochastic_threshold pins; the per-element mode indexes the global element.  in / acc 16-byte (float32) or 8-byte (bfloat16)
+ * aligned and residual, out and every term's packed bytes 16-byte aligned: ONE streaming launch (no scan, no atomics, no grid barrier, no LDS
+ * traffic for the butterflies); anything else element-aligned: ONE guarded one-wave-per-group launch that writes the same bytes; a float buffer
+ * that is not aligned to its element aborts.  Nothing at or past a tensor's end is read or written; the buffers must not overlap.  Device (or
+ * pinned) buffers only; stream-ordered on the context's stream, always behind the previous call whatever piquant_hip_set_independent_calls
+ * says; no host synchronisation, no allocation, the seed travels by value (hipGraph-capturable).  numel == 0 is a no-op that draws no threshold.
+ * QUIRKS.  One NaN in a full group makes the whole rotated group NaN, so that group's residual is NaN from then on: it stays NaN until the caller
+ * zeroes it (the un-rotated calls lose one element only).  A group of nothing but NaNs gets the parameters (1.0, qmax >> 1) as everywhere.
+ * LEAVING THE ROTATED DOMAIN.  piquant_hip_hadamard_grouped(residual, float32, inverse = 1, seed) gives the residual of the original domain up to
+ * float32 rounding, and the forward call takes it back: that is the way to change the seed or to stop rotating without dropping what is owed. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, float* residual,
+                                                            void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
+                                                            uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc,
+                                                                   float* residual, const void* const* inputs, const float* const* input_scales,
+                                                                   const uint8_t* const* input_zero_points, size_t count, void* out,
+                                                                   piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
+                                                                   uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

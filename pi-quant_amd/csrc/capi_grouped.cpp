@@ -1,5 +1,5 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, and the reduce and dequantize-sum in the rotated domain.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, and the two error-feedback calls of the rotated domain.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -402,6 +402,50 @@ void piquant_hip_reduce_quantize_grouped_rotated(piquant_context_t* ctx, const v
         launch_reduce_quantize_grouped_rotated(r, seed, !(terms.aligned && aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
     }
     if (ctx->blocking) wait_stream(ctx);
+}
+
+// Error feedback in the rotated domain: the two quantizing calls above with a float32 residual of rotated values (grouped_rot_ef_kernels.hpp).
+// ONE launch each: streaming when the tensor is aligned as its rows are loaded (16 bytes; 8 for bfloat16) and residual, out and every term's packed
+// bytes are 16-byte aligned, guarded otherwise.  Without terms the reduce IS the quantize: one body serves both entries.
+void piquant_hip_reduce_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, float* residual,
+                                                    const void* const* inputs, const float* const* input_scales,
+                                                    const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out,
+                                                    size_t numel, size_t group_size, float* scales, uint8_t* zero_points, uint64_t seed,
+                                                    piquant_round_mode_t mode) {
+    const char* entry = count == 0 ? "piquant_hip_quantize_grouped_rotated_ef" : "piquant_hip_reduce_quantize_grouped_rotated_ef";
+    const Where w {entry};
+    if (!ctx) bad(w, "context is NULL");
+    check_dynamic_types(dtype_acc, dtype_out, mode);
+    check_group_size(group_size, entry);
+    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    check_tensor(w, true, acc, residual, out, scales, zero_points);
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const GroupedTensor t = resolve_tensor(ctx, w, acc, residual, out, scales, zero_points, numel);
+    const bool f32 = dtype_acc == PIQUANT_DTYPE_F32;
+    if (reinterpret_cast<uintptr_t>(t.in) % (f32 ? 4 : 2) != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0)
+        bad(w, "the tensor or its residual is not aligned to its element size");
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, t.out, numel);
+    const bool streams = terms.aligned && (reinterpret_cast<uintptr_t>(t.in) & (f32 ? 15u : 7u)) == 0 && aligned16(t.residual) && aligned16(t.out);
+    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
+    GroupedReduceLaunch r {t, {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)}, {}, static_cast<int>(count)};
+    std::copy(terms.term.begin(), terms.term.end(), r.term);
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
+        if (count == 0) launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, r}, seed, !streams, ctx->stream, ctx->num_cu);
+        else launch_reduce_quantize_grouped_rotated_ef(r, seed, !streams, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, float* residual, void* out,
+                                             piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                             uint64_t seed, piquant_round_mode_t mode) {
+    piquant_hip_reduce_quantize_grouped_rotated_ef(ctx, in, dtype_in, residual, nullptr, nullptr, nullptr, 0, out, dtype_out, numel, group_size, scales,
+                                                   zero_points, seed, mode);
 }
 
 void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,

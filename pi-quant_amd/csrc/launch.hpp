@@ -221,6 +221,13 @@ void launch_dequantize_grouped_rotated(const GroupedDequantLaunch& d, uint64_t r
 void launch_reduce_quantize_grouped_rotated(const GroupedReduceLaunch& r, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 // out (op)= the inverse rotation of the float32 sum of the terms' grouped dequantizes
 void launch_dequantize_sum_grouped_rotated(const GroupedDequantSumLaunch& d, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+// Error feedback in the rotated domain (grouped_rot_ef_kernels.hpp; kernels_grouped_rot_ef_quant.hip, kernels_grouped_rot_ef_reduce.hip): the two
+// rotated quantizing launches above with `residual` set -- numel float32 values of the ROTATED domain whatever dt_in is, read and written:
+// y = rotate(widen(in)) [+ terms] + residual, (out, scales, zero_points) = quantize_grouped(y), residual <- y - dequantize_grouped(out), ONE launch.
+// Streaming: residual, out and every term's packed bytes 16-byte aligned, in 16-byte (float32) or 8-byte (bfloat16) aligned; `guarded`: anything
+// element-aligned, the same bytes.
+void launch_quantize_grouped_rotated_ef(const GroupedEfLaunch& q, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+void launch_reduce_quantize_grouped_rotated_ef(const GroupedReduceLaunch& r, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

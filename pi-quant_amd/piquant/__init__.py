@@ -578,6 +578,31 @@ class Context:
                                                      _ptr_array(zero_points_ptrs), n, ptr_out, dtype_out.value, numel, group_size,
                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, reduce_op.value)
 
+    def quantize_grouped_rotated_ef_ptr(self, ptr_in: int, dtype_in: DataType, ptr_residual: int, ptr_out: int, dtype_out: DataType, numel: int,
+                                        group_size: int, scales_ptr: int, zero_points_ptr: int, seed: int, round_mode: RoundMode,
+                                        _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_rotated_ptr`` with error feedback, the residual (``numel`` float32 values, whatever ``dtype_in`` is) kept in the rotated
+        domain: the bytes of ``quantize_grouped_ef_ptr`` of the float32 forward rotation of the tensor, in one launch
+        (``piquant_hip_quantize_grouped_rotated_ef``)."""
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_rotated_ef(self._ctx, ptr_in, dtype_in.value, ptr_residual, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                                  zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
+    def reduce_quantize_grouped_rotated_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
+                                               dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, seed: int,
+                                               round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``reduce_quantize_grouped_rotated_ptr`` with error feedback on the re-quantization, the float32 residual kept in the rotated domain and
+        added behind the terms (``piquant_hip_reduce_quantize_grouped_rotated_ef``: one launch, at most 16 terms).  ``acc`` is only read."""
+        n = len(ptrs_in)
+        assert dtype_acc.is_dequantized and dtype_out.is_quantized and n == len(scales_in) == len(zero_points_in)
+        if n > 16:
+            raise ValueError(f'reduce_quantize_grouped_rotated_ef takes at most 16 terms, not {n}')
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_reduce_quantize_grouped_rotated_ef(self._ctx, ptr_acc, dtype_acc.value, ptr_residual, _ptr_array(ptrs_in), _ptr_array(scales_in),
+                                                         _ptr_array(zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
+                                                         zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                        _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:

@@ -72,6 +72,9 @@ _DECLS = [
                                                            _sz, _sz, _vp, _vp, C.c_uint64, _int]),
     ('piquant_hip_dequantize_sum_grouped_rotated', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _int, _sz,
                                                           _sz, C.c_uint64, _int]),
+    ('piquant_hip_quantize_grouped_rotated_ef', None, [_vp, _vp, _int, _vp, _vp, _int, _sz, _sz, _vp, _vp, C.c_uint64, _int]),
+    ('piquant_hip_reduce_quantize_grouped_rotated_ef', None, [_vp, _vp, _int, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp,
+                                                              _int, _sz, _sz, _vp, _vp, C.c_uint64, _int]),
     ('piquant_hip_reduce_quantize_grouped_ef', None, [_vp, _vp, _int, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _int,
                                                       _sz, _sz, _vp, _vp, _int]),
     ('piquant_hip_quantize_grouped_ef', None, [_vp, _vp, _int, _vp, _vp, _int, _sz, _sz, _vp, _vp, _int]),

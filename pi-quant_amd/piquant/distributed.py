@@ -589,6 +589,30 @@ class _DeviceOps:
                                                           [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp, seed,
                                                           self._mode(round_mode), _device_ptrs=True)
 
+    def encode_grouped_rotated_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int,
+                                  seed: int) -> None:
+        """encode_grouped_rotated(x) with error feedback in the rotated domain: the float32 ``residual`` (rotated values, whatever ``x``'s dtype) is
+        added behind the rotation and then holds what the record lost, one launch."""
+        sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
+        self._cx(x).quantize_grouped_rotated_ef_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), residual.data_ptr(), data, torch_to_piquant_dtype(qdtype),
+                                                    x.numel(), group_size, sc, zp, seed, self._mode(round_mode), _device_ptrs=True)
+
+    def encode_batch_grouped_rotated_ef(self, xs, residuals, bufs, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
+        """encode_grouped_rotated_ef(xs[i], residuals[i], bufs[i]) for all i, one launch EACH, as encode_batch_grouped_rotated."""
+        for x, r, b in zip(xs, residuals, bufs):
+            self.encode_grouped_rotated_ef(x, r, b, qdtype, round_mode, group_size, seed)
+
+    def reduce_encode_grouped_rotated_ef(self, bufs, acc: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str,
+                                         group_size: int, seed: int) -> None:
+        """reduce_encode_grouped_rotated with error feedback on the re-quantization: the terms are added first, then the float32 ``residual`` of the
+        rotated domain, which then holds what the record lost; one launch (at most 16 buffers; ``acc`` is only read)."""
+        n = acc.numel()
+        recs = [self._record(b, n, qdtype, group_size) for b in bufs]
+        sc, zp, data = self._record(buf, n, qdtype, group_size)
+        self._cx(acc).reduce_quantize_grouped_rotated_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[2] for r in recs],
+                                                             [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size,
+                                                             sc, zp, seed, self._mode(round_mode), _device_ptrs=True)
+
     def decode_sum_grouped_rotated(self, bufs, out: torch.Tensor, qdtype: torch.dtype, reduce_op: str, group_size: int, seed: int) -> None:
         """out (op)= the inverse rotation of the float32 sum of the wire buffers, added in order: one launch (at most 16 buffers) and one pass
         over ``out``."""
@@ -729,7 +753,7 @@ class _Wire:
     """What every record of one collective call has in common -- the ops object, the quantized dtype, the rounding mode, the record format
     (``group_size`` None: 16-byte header + packed bytes; else ``grouped_wire_layout``), the flattened residual (or None) and whether the
     re-quantizations of partial sums feed it (``requantize``), the rotation's seed (``rotation_seed``, or None: the grouped wire then carries the
-    records of the rotated values, with no residual) -- and the only place that knows which ``ops.*`` method a step of a schedule maps
+    records of the rotated values, and a residual is then the float32 one of the rotated domain, ``rotated_error_feedback``) -- and the only place that knows which ``ops.*`` method a step of a schedule maps
     to.  The schedules below are written once, on a wire.  ``chunk`` is the ``(begin, end)`` of the values a step works on: where a residual
     takes part, the step works on that slice of it."""
 
@@ -747,11 +771,14 @@ class _Wire:
             return _HEADER_BYTES + self.qdt.packed_nbytes(numel)
         return grouped_wire_layout(numel, self.group_size, self.qdt.bit_size).nbytes
 
-    def encode(self, x, buf, chunk) -> None:
+    def encode(self, x, buf, chunk, ef: bool = True) -> None:
+        """``ef`` False: the rotated owner's encode without ``requantize``, which leaves the residual alone."""
         if self.group_size is None:
             self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
-        elif self.seed is not None:
+        elif self.seed is not None and (self.residual is None or not ef):
             self.ops.encode_grouped_rotated(x, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
+        elif self.seed is not None:
+            self.ops.encode_grouped_rotated_ef(x, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif self.residual is None:
             self.ops.encode_grouped(x, buf, self.quant_dtype, self.round_mode, self.group_size)
         else:
@@ -760,8 +787,11 @@ class _Wire:
     def encode_batch(self, xs, bufs, chunks) -> None:
         if self.group_size is None:
             self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
-        elif self.seed is not None:
+        elif self.seed is not None and self.residual is None:
             self.ops.encode_batch_grouped_rotated(xs, bufs, self.quant_dtype, self.round_mode, self.group_size, self.seed)
+        elif self.seed is not None:
+            self.ops.encode_batch_grouped_rotated_ef(xs, [self.residual[b:e] for b, e in chunks], bufs, self.quant_dtype, self.round_mode, self.group_size,
+                                                     self.seed)
         elif self.residual is None:
             self.ops.encode_batch_grouped(xs, bufs, self.quant_dtype, self.round_mode, self.group_size)
         else:
@@ -771,8 +801,11 @@ class _Wire:
         """encode(acc + the records in ``terms``, added in order) into ``buf``, one launch; the residual takes part only with ``requantize``."""
         if self.group_size is None:
             self.ops.reduce_encode(terms, acc, buf, self.quant_dtype, self.round_mode)
-        elif self.seed is not None:
+        elif self.seed is not None and not self.requantize:
             self.ops.reduce_encode_grouped_rotated(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
+        elif self.seed is not None:
+            self.ops.reduce_encode_grouped_rotated_ef(terms, acc, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size,
+                                                      self.seed)
         elif not self.requantize:
             self.ops.reduce_encode_grouped(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size)
         else:
@@ -782,13 +815,14 @@ class _Wire:
         """The mesh owner's step: ``reduce_encode``.  In the rotated domain it is the reduce-scatter's step followed by the all-gather's --
         ``decode_sum(terms, acc, 'add')``, which leaves the sum in ``acc``, then ``encode(acc)`` -- two launches: only so do reduce-scatter +
         all-gather leave the bytes of the direct all-reduce (the one-launch rotated reduce keeps the sum in the rotated domain, the two halves
-        pass it through the original one and the tensor's type: equal in exact arithmetic, not in float32)."""
+        pass it through the original one and the tensor's type: equal in exact arithmetic, not in float32).  That encode feeds the owner's own
+        chunk of a rotated residual only with ``requantize``."""
         if self.seed is None:
             self.reduce_encode(terms, acc, buf, chunk)
         else:
             if terms:
                 self.decode_sum(terms, acc, 'add')
-            self.encode(acc, buf, chunk)
+            self.encode(acc, buf, chunk, ef=self.requantize)
 
     def decode(self, buf, out, op: str) -> None:
         if self.group_size is None:
@@ -905,6 +939,7 @@ def quantized_all_reduce(
     error_feedback: Optional[torch.Tensor] = None,
     error_feedback_requantize: bool = False,
     rotation_seed: Optional[int] = None,
+    rotated_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -955,9 +990,21 @@ def quantized_all_reduce(
     every interior boundary on a multiple of 4096 elements, so every chunk rotates exactly as the whole tensor does.  ALL RANKS MUST PASS THE SAME
     SEED: the library does not check it, and ranks that disagree sum values of different domains.  There is no batched rotated launch yet: the
     mesh encodes its world - 1 chunks, and decodes its world chunks, with one launch each.  uint2 records gain nothing from the rotation in the
-    all-reduce.  ValueError before anything moves: without ``group_size``, with ``transport='p2p'``, with ``error_feedback``
-    (the residual lives in the original domain; feeding it needs a kernel that rotates both ways), and in the direct schedule with more than
-    17 ranks (the owner's one launch sums at most 16 records).
+    all-reduce without error feedback.  ValueError before anything moves: without ``group_size``, with ``transport='p2p'``, with
+    ``error_feedback`` (that residual lives in the original domain; ``rotated_error_feedback`` is the one that goes with a rotation), and in the
+    direct schedule with more than 17 ranks (the owner's one launch sums at most 16 records).
+
+    ``rotated_error_feedback`` (``group_size`` and ``rotation_seed`` only; default None: every byte, every launch and every ``_ops`` call as
+    without it): error feedback with the residual kept in the ROTATED domain -- a contiguous FLOAT32 tensor (float32 also for a bfloat16 tensor)
+    of the tensor's device and numel that the caller keeps between steps (zeros before the first).  It is a keyword of its own because it is a
+    different object from ``error_feedback``'s residual: a record of rotated values.  Every encode of this rank's own contribution becomes
+    ``quantize_grouped_rotated_ef`` on the matching slice (the ring's first encode, the mesh's peer chunks, one launch each); with
+    ``error_feedback_requantize`` every hop of the ring becomes ONE ``reduce_quantize_grouped_rotated_ef`` launch on the hop's chunk, and the
+    mesh owner's ``quantize_grouped_rotated`` becomes ``quantize_grouped_rotated_ef`` on the rank's own chunk: each chunk of the residual is then
+    touched exactly once per call.  The residual belongs to one (world size, rank, algorithm, ``error_feedback_requantize``, SEED, GROUP SIZE):
+    ``piquant.torch.hadamard_grouped(residual, seed=..., inverse=True)`` takes it to the original domain to change either.  One NaN makes its
+    whole group's residual NaN until the caller zeroes it.  ValueError before anything moves: without ``group_size`` or ``rotation_seed``, with
+    ``error_feedback``, with ``transport='p2p'``, or a residual that is not float32, contiguous, on the tensor's device and of its numel.
 
     ``transport='p2p'`` (``algorithm='direct'`` only, one node; EXPERIMENTAL until it has run between two GPUs): no collective at all -- the
     encode kernels store into the peers' receive buffers over xGMI and flags order the steps (``quantized_all_reduce_direct``).  ``timeout``
@@ -994,19 +1041,22 @@ def quantized_all_reduce(
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
-    _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
+    _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
+                                     transport)
     seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
+    _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, transport, error_feedback)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
                                            group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize,
-                                           rotation_seed=rotation_seed, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
+                                           rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize, seed)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+                 error_feedback_requantize, seed)
     _ring(wire, _Chunks.of(wire, tensor.view(-1), world), group, world, rank, tensor.device)
     return tensor
 
@@ -1024,6 +1074,7 @@ def quantized_all_reduce_direct(
     error_feedback: Optional[torch.Tensor] = None,
     error_feedback_requantize: bool = False,
     rotation_seed: Optional[int] = None,
+    rotated_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1064,19 +1115,27 @@ def quantized_all_reduce_direct(
     ``quantize_grouped_rotated`` launches, steps 3-4 ``dequantize_sum_grouped_rotated(..., 'add')`` into the own chunk and
     ``quantize_grouped_rotated`` of it (the steps of ``quantized_reduce_scatter`` and ``quantized_all_gather``: the same bytes), the decode world
     ``dequantize_grouped_rotated`` launches.  At most 17 ranks; not with ``error_feedback`` or ``transport='p2p'``.
+
+    ``rotated_error_feedback``: the float32 rotated-domain residual of ``quantized_all_reduce`` -- step 1's launches become
+    ``quantize_grouped_rotated_ef`` on the peers' chunks of it; with ``error_feedback_requantize`` the owner's ``quantize_grouped_rotated`` becomes
+    ``quantize_grouped_rotated_ef`` on the rank's own chunk.  It belongs to one (world size, rank, algorithm, ``error_feedback_requantize``, seed,
+    group size).
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
-    _check_error_feedback_requantize(error_feedback_requantize, error_feedback, group_size, transport)
+    _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
+                                     transport)
     seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
+    _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, transport, error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     _check_rotated_terms(seed, world, 'the direct schedule')
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, error_feedback_requantize, seed)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+                 error_feedback_requantize, seed)
     flat = tensor.view(-1)
     ch = _Chunks.of(wire, flat, world)
     if transport == 'p2p':
@@ -1138,7 +1197,7 @@ _ROTATED_MAX_TERMS = 16   # piquant_hip_reduce_quantize_grouped_rotated / piquan
 
 def _check_rotation_seed(seed, group_size, transport: str, error_feedback) -> Optional[int]:
     """ValueError before anything moves: a rotation without the grouped wire, over the peer-to-peer transport or with a residual (which lives in
-    the original domain: feeding it needs a kernel that rotates both ways).  Returns the seed modulo 2^64, or None."""
+    the original domain; ``rotated_error_feedback=`` is the residual that goes with a rotation).  Returns the seed modulo 2^64, or None."""
     if seed is None:
         return None
     if not isinstance(seed, int) or isinstance(seed, bool):
@@ -1148,8 +1207,30 @@ def _check_rotation_seed(seed, group_size, transport: str, error_feedback) -> Op
     if transport == 'p2p':
         raise ValueError("rotation_seed= is not supported with transport='p2p'; use transport='collective'")
     if error_feedback is not None:
-        raise ValueError('rotation_seed= is not supported with error_feedback= (the residual lives in the original domain)')
+        raise ValueError('rotation_seed= is not supported with error_feedback= (the residual lives in the original domain); '
+                         'rotated_error_feedback= takes a float32 residual of the rotated domain')
     return seed & 0xFFFFFFFFFFFFFFFF
+
+
+def _check_rotated_error_feedback(residual, tensor: torch.Tensor, group_size, rotation_seed, transport: str, error_feedback) -> None:
+    """ValueError before anything moves: a rotated-domain residual without the grouped wire, without a rotation, over the peer-to-peer transport,
+    next to ``error_feedback=`` (a residual of the original domain: a different object), or one that does not match the tensor -- float32 whatever
+    the tensor's dtype, contiguous, of its device and numel (it is written by raw pointer)."""
+    if residual is None:
+        return
+    if group_size is None:
+        raise ValueError('rotated_error_feedback= needs the grouped wire: pass group_size=')
+    if rotation_seed is None:
+        raise ValueError('rotated_error_feedback= needs rotation_seed= (the residual holds values of that rotation; error_feedback= is the residual '
+                         'of the original domain)')
+    if transport == 'p2p':
+        raise ValueError("rotated_error_feedback= is not supported with transport='p2p'; use transport='collective'")
+    if error_feedback is not None:
+        raise ValueError('rotated_error_feedback= cannot be combined with error_feedback= (one residual a call: of the rotated domain or of the '
+                         'original one)')
+    from .torch import _check_rotated_residual
+
+    _check_rotated_residual(residual, tensor, 'rotated_error_feedback')
 
 
 def _check_rotated_terms(seed, world: int, what: str) -> None:
@@ -1180,6 +1261,7 @@ def quantized_reduce_scatter(
     group_size: int = 128,
     error_feedback: Optional[torch.Tensor] = None,
     rotation_seed: Optional[int] = None,
+    rotated_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1210,11 +1292,17 @@ def quantized_reduce_scatter(
     and the sum is rotated back once and added into the own chunk.  Followed by ``quantized_all_gather`` with the same seed it leaves exactly the bytes
     of ``quantized_all_reduce(algorithm='direct', rotation_seed=...)``, whose owner's step is these two.  At most 17 ranks; not with ``error_feedback``.
 
+    ``rotated_error_feedback`` (``rotation_seed`` only): the float32 rotated-domain residual of ``quantized_all_reduce``; the peers' chunks are
+    encoded by ``quantize_grouped_rotated_ef`` on their chunks of it, the rank's own chunk of it is neither read nor written.  Followed by
+    ``quantized_all_gather`` with the same residual it leaves exactly the tensor bytes and residual bytes of ``quantized_all_reduce(algorithm='direct',
+    error_feedback_requantize=True)``.  The residual belongs to one (world size, rank, seed, group size).
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
     of this module's multi-GPU paths.)"""
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
+    _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     _check_rotated_terms(seed, world, 'quantized_reduce_scatter')
@@ -1222,7 +1310,8 @@ def quantized_reduce_scatter(
     if world == 1 and not _single_rank_collectives:
         b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
         return flat[b_own:e_own]
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, rotation_seed=seed)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+                 rotation_seed=seed)
     ch = _Chunks.of(wire, flat, world)
     x_own = ch.views[rank]
     terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
@@ -1241,6 +1330,7 @@ def quantized_all_gather(
     group_size: int = 128,
     error_feedback: Optional[torch.Tensor] = None,
     rotation_seed: Optional[int] = None,
+    rotated_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1261,15 +1351,21 @@ def quantized_all_gather(
     ``rotation_seed`` (the same int on all ranks; not checked): step 1 is ``quantize_grouped_rotated``, step 3 one
     ``dequantize_grouped_rotated(..., 'set')`` launch per chunk.  Not with ``error_feedback``.
 
+    ``rotated_error_feedback`` (``rotation_seed`` only): the float32 rotated-domain residual of ``quantized_all_reduce``; step 1 becomes
+    ``quantize_grouped_rotated_ef`` on the rank's own chunk of it, no other chunk is touched.  It belongs to one (world size, rank, seed, group
+    size).
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
     _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
+    _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback, rotation_seed=seed)
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+                 rotation_seed=seed)
     ch = _Chunks.of(wire, tensor.view(-1), world)
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
     if ch.views[rank].numel():

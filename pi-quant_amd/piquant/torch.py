@@ -866,6 +866,80 @@ def reduce_quantize_grouped_ef(acc: torch.Tensor, residual: torch.Tensor, tensor
     return _reduce_quantize_grouped(acc, residual, tensors, scales, zero_points, dtype, group_size, round_mode, ctx, out, out_scales, out_zero_points)
 
 
+def _check_rotated_residual(residual, tensor: torch.Tensor, what: str = 'residual') -> None:
+    """The residual of an error-feedback call in the rotated domain: float32 whatever the tensor's dtype, contiguous, of the tensor's device and
+    numel (it is updated in place by raw pointer)."""
+    _require(isinstance(residual, torch.Tensor), f'{what} must be a torch.Tensor')
+    _require(residual.dtype == torch.float32, f'{what} must be torch.float32 (a record of rotated float32 values, also for a bfloat16 tensor), got '
+             f'{residual.dtype}')
+    _require(residual.numel() == tensor.numel(), f'{what} must have the numel of the tensor ({tensor.numel()}), got {residual.numel()}')
+    _require(residual.device == tensor.device, f'{what} must live on the device of the tensor ({tensor.device}), got {residual.device}')
+    _require(residual.is_contiguous(), f'{what} must be contiguous (it is updated in place)')
+
+
+def quantize_grouped_rotated_ef(tensor: torch.Tensor, residual: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, seed=_NA,
+                                round_mode: str = 'nearest', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                                out_scales: Optional[torch.Tensor] = None,
+                                out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``quantize_grouped_rotated`` with error feedback, the residual kept in the ROTATED domain, in one launch that never writes the rotated
+    tensor: bit for bit ``quantize_grouped_ef(hadamard_grouped(tensor.float(), group_size=group_size, seed=seed), residual, ...)``.  ``residual``
+    is a contiguous float32 tensor (float32 also for a bfloat16 ``tensor``) of the tensor's device and numel that the caller keeps between steps
+    (zeros before the first); it belongs to one (``seed``, ``group_size``) and is not the residual ``quantize_grouped_ef`` keeps.
+    ``hadamard_grouped(residual, seed=seed, inverse=True)`` is the original-domain residual up to float32 rounding: the way to change the seed or
+    to stop rotating.  One NaN makes its whole rotated group NaN, and that group's residual stays NaN until the caller zeroes it.  ``tensor`` is
+    not written.  Returns (quantized, scales, zero_points) (``include/piquant_hip.h``, piquant_hip_quantize_grouped_rotated_ef)."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    seed = _check_seed(seed)
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    _check_rotated_residual(residual, tensor)
+    if out_scales is not None:
+        _check_group_params(out_scales, out_zero_points, num_groups(tensor.numel(), group_size))
+    _check_float_input(tensor)
+    out_scales, out_zero_points = _group_params_of(out_scales, out_zero_points, tensor.numel(), group_size, tensor.device, 'out_scales and out_zero_points',
+                                                   shapes_checked=True)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    out = _packed_out(out, dtype, tensor, tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_grouped_rotated_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), out.data_ptr(),
+                                        torch_to_piquant_dtype(dtype), tensor.numel(), group_size, out_scales.data_ptr(), out_zero_points.data_ptr(), seed,
+                                        _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, out_scales, out_zero_points
+
+
+def reduce_quantize_grouped_rotated_ef(acc: torch.Tensor, residual: torch.Tensor, tensors, scales, zero_points, *, dtype: torch.dtype,
+                                       group_size: int = 128, seed=_NA, round_mode: str = 'nearest', ctx: Optional[Context] = None,
+                                       out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
+                                       out_zero_points: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``reduce_quantize_grouped_rotated`` with error feedback on the re-quantization, the residual kept in the rotated domain, in one launch (at
+    most 16 terms; more raise).  Bit for bit ``y = hadamard_grouped(acc.float(), seed=seed)``, ``dequantize_grouped(tensors[i], ...,
+    dtype=torch.float32, reduce_op='add', out=y)`` for every i in order, ``quantize_grouped_ef(y, residual)``: the residual is added AFTER the
+    terms.  ``residual`` is as for ``quantize_grouped_rotated_ef``; ``acc`` is only read.  No terms is ``quantize_grouped_rotated_ef(acc,
+    residual)``.  Returns (out, out_scales, out_zero_points) (``include/piquant_hip.h``, piquant_hip_reduce_quantize_grouped_rotated_ef)."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    seed = _check_seed(seed)
+    tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
+    _require(len(tensors) <= 16, f'reduce_quantize_grouped_rotated_ef takes at most 16 terms, got {len(tensors)}')
+    _require(len(tensors) == len(scales) == len(zero_points), f'tensors, scales and zero_points must have the same length, got '
+             f'{len(tensors)}, {len(scales)} and {len(zero_points)}')
+    _require(isinstance(acc, torch.Tensor) and acc.dtype in _DEQUANT_TYPES, 'acc must be a float32 or bfloat16 tensor')
+    _check_rotated_residual(residual, acc)
+    _check_float_input(acc, 'acc')
+    _require(acc.is_contiguous(), 'acc must be contiguous (it is the accumulator)')
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
+    numel = acc.numel()
+    qdt = torch_to_piquant_dtype(dtype)
+    _check_grouped_terms(tensors, scales, zero_points, qdt, repeat(numel), group_size, acc.device)
+    out = _packed_out(out, dtype, acc, acc.device)
+    out_scales, out_zero_points = _group_params_of(out_scales, out_zero_points, numel, group_size, acc.device, 'out_scales and out_zero_points')
+    ctx = _ctx_for(acc, ctx)
+    ctx.reduce_quantize_grouped_rotated_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), _ptrs(tensors), _ptrs(scales),
+                                               _ptrs(zero_points), out.data_ptr(), qdt, numel, group_size, out_scales.data_ptr(),
+                                               out_zero_points.data_ptr(), seed, _ROUND_MODES[round_mode], _device_ptrs=True)
+    return out, out_scales, out_zero_points
+
+
 def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_size: int = 128, round_mode: str = 'nearest', ctx: Optional[Context] = None,
                               outs=None, out_scales=None, out_zero_points=None):
     """``quantize_grouped_ef`` of several independent (tensor, residual) pairs (one dtype pair, group size and round mode) with one kernel launch

@@ -51,7 +51,14 @@ it, in the same run: reduce_quantize_grouped_rotated (fp32 + 1 and + 7 uint8 ter
 dequantize_sum_grouped_rotated (1 and 7 uint8 terms into fp32, SET and ADD; 7 uint4 terms into bf16, ADD).  Every fused row must be faster than its
 composition; fused / composition against the byte ratio is reported as met or missed.  Writes profiles/grouped_rot_reduce_bench.json.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows rot_ef: error feedback in the rotated domain (G = 128), each fused call next to the composition of public calls that defines it, in the
+same run: quantize_grouped_rotated_ef (fp32 -> uint8, fp32 -> uint4, bf16 -> uint4, bf16 -> uint8) against hadamard_grouped of the widened tensor
+into a float32 scratch + quantize_grouped_ef; reduce_quantize_grouped_rotated_ef (fp32 + 1 uint8 term, fp32 + 7 uint4 terms, bf16 + 1 uint4 term)
+against the rotation, k float32 grouped dequantize ADD launches and quantize_grouped_ef.  Every fused row must be faster than its composition;
+fused / composition against the byte ratio is reported as met or missed.  Writes profiles/grouped_rot_ef_bench.json; --rows all appends these
+rows to its table.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce|rot_ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -819,11 +826,83 @@ def rot_reduce_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
     return rows
 
 
+def rot_ef_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
+    """error feedback in the rotated domain, each fused call next to the composition of public calls that defines it: hadamard_grouped into a
+    float32 scratch (a bfloat16 tensor is widened into it first), k float32 grouped dequantize ADD launches, quantize_grouped_ef of the scratch
+    with the float32 residual.  k = 0: quantize_grouped_rotated_ef."""
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    f32 = piquant.DataType.F32
+
+    def ratio(fr, cr):
+        fr["over_composition"] = round(fr["us"] / cr["us"], 3)
+        fr["faster_than_composition"] = bool(fr["us"] < cr["us"])
+        fr["bytes_over_composition"] = round(fr["bytes"] / cr["bytes"], 3)
+        fr["over_byte_ratio"] = round(fr["over_composition"] / fr["bytes_over_composition"], 3)
+        fr["target_1.15x_byte_ratio"] = "met" if fr["over_byte_ratio"] <= 1.15 else "missed"
+        print(f"    fused / composition = {fr['over_composition']:.3f} (bytes {fr['bytes_over_composition']:.3f}): {fr['over_byte_ratio']:.3f} x the byte ratio, "
+              f"target 1.15 {fr['target_1.15x_byte_ratio']}; faster than its composition: {fr['faster_than_composition']}", flush=True)
+
+    for fname, qname, k in (("f32", "uint8", 0), ("f32", "uint4", 0), ("bf16", "uint4", 0), ("bf16", "uint8", 0), ("f32", "uint8", 1), ("f32", "uint4", 7),
+                            ("bf16", "uint4", 1)):
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(NUMEL)
+        rec = nq + 5 * ng
+        fused_bytes = NUMEL * esize + 8 * NUMEL + (k + 1) * rec
+        comp_bytes = (6 * NUMEL if fname == "bf16" else 0) + 8 * NUMEL + k * (rec + 8 * NUMEL) + 12 * NUMEL + rec
+        nbuf = max(3, int(args.rotate_gb * 1e9 / fused_bytes) + 1)
+        accs = [torch.empty(NUMEL, device=dev).normal_(generator=g).to(tdt) for _ in range(nbuf)]
+        res = [torch.empty(NUMEL, device=dev).normal_(generator=g).mul_(0.01) for _ in range(nbuf)]
+        scratch = [torch.empty(NUMEL, device=dev) for _ in range(nbuf)]
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        terms = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tsc = [[torch.empty(ng, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        tzp = [[torch.randint(0, 1 << bits, (ng,), dtype=torch.uint8, device=dev, generator=g) for _ in range(k)] for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+
+        def fused(i):
+            if k == 0:
+                ctx.quantize_grouped_rotated_ef_ptr(accs[i].data_ptr(), fdt, res[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(),
+                                                    zs[i].data_ptr(), seed, piquant.RoundMode.NEAREST, _device_ptrs=True)
+            else:
+                ctx.reduce_quantize_grouped_rotated_ef_ptr(accs[i].data_ptr(), fdt, res[i].data_ptr(), [t.data_ptr() for t in terms[i]],
+                                                           [t.data_ptr() for t in tsc[i]], [t.data_ptr() for t in tzp[i]], outs[i].data_ptr(), qdt, NUMEL, G,
+                                                           sc[i].data_ptr(), zs[i].data_ptr(), seed, piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        def composition(i):
+            src = accs[i]
+            if fname == "bf16":
+                scratch[i].copy_(accs[i])
+                src = scratch[i]
+            ctx.hadamard_grouped_ptr(src.data_ptr(), f32, scratch[i].data_ptr(), NUMEL, G, seed, False, _device_ptrs=True)
+            for t, s_, z_ in zip(terms[i], tsc[i], tzp[i]):
+                ctx.dequantize_grouped_ptr(t.data_ptr(), qdt, scratch[i].data_ptr(), f32, NUMEL, G, s_.data_ptr(), z_.data_ptr(), piquant.ReduceOp.ADD,
+                                           _device_ptrs=True)
+            ctx.quantize_grouped_ef_ptr(scratch[i].data_ptr(), f32, res[i].data_ptr(), outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(),
+                                        piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        pair = f"{fname}->{qname}" if k == 0 else f"{fname}+{k}x{qname}->{qname}"
+        us_c, s_c = timed(composition, nbuf, args.windows, per_window, stream)
+        cr = row("rot_ef_composition" if k == 0 else "rot_reduce_ef_composition", pair, G, us_c, comp_bytes, s_c)
+        us_f, s_f = timed(fused, nbuf, args.windows, per_window, stream)
+        fr = row("quantize_grouped_rotated_ef" if k == 0 else "reduce_quantize_grouped_rotated_ef", pair, G, us_f, fused_bytes, s_f)
+        ratio(fr, cr)
+        rows += [cr, fr]
+        del accs, res, scratch, outs, sc, zs, terms, tsc, tzp
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce"),
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce", "rot_ef"),
                     default="all")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -832,7 +911,7 @@ def main():
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
                                                    "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
                                                    "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json",
-                                                   "rot_reduce": "grouped_rot_reduce_bench.json"}[args.rows])
+                                                   "rot_reduce": "grouped_rot_reduce_bench.json", "rot_ef": "grouped_rot_ef_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -860,6 +939,8 @@ def main():
         rows = rot_rows(ctx, dev, stream, args)
     if args.rows == "rot_reduce":
         rows = rot_reduce_rows(ctx, dev, stream, args)
+    if args.rows == "rot_ef":
+        rows = rot_ef_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
@@ -905,6 +986,7 @@ def main():
         rows += reduce_ef_f32r_rows(ctx, dev, stream, args)
         rows += requant_rows(ctx, dev, stream, args)
         rows += dequant_sum_rows(ctx, dev, stream, args)
+        rows += rot_ef_rows(ctx, dev, stream, args)
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
