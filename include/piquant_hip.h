@@ -453,6 +453,41 @@ PIQUANT_EXPORT void piquant_hip_reduce_quantize_grouped_rotated_ef(piquant_conte
                                                                    piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
                                                                    uint8_t* zero_points, uint64_t seed, piquant_round_mode_t mode);
 
+/* BATCHES OF THE ROTATED CALLS: what piquant_hip_quantize_grouped_batch, piquant_hip_dequantize_grouped_batch and
+ * piquant_hip_quantize_grouped_ef_batch are to their single calls.  Tensor i has its own input, output, scales, zero_points and numels[i] (and
+ * residuals[i]: numels[i] float32 values, float32 also for bfloat16 tensors); all share the dtype pair, group_size, the rotation's seed and the
+ * round mode / op.  The bytes each call writes are those of this composition of public calls, for i = 0 .. count - 1 in order:
+ *   piquant_hip_quantize_grouped_rotated_batch     piquant_hip_quantize_grouped_rotated(inputs[i], ..., outputs[i], numels[i], scales[i],
+ *                                                  zero_points[i], seed, mode)
+ *   piquant_hip_dequantize_grouped_rotated_batch   piquant_hip_dequantize_grouped_rotated(inputs[i], ..., outputs[i], numels[i], scales[i],
+ *                                                  zero_points[i], seed, op)
+ *   piquant_hip_quantize_grouped_rotated_ef_batch  piquant_hip_quantize_grouped_rotated_ef(inputs[i], ..., residuals[i], outputs[i], numels[i],
+ *                                                  scales[i], zero_points[i], seed, mode)
+ *   with ONE stochastic threshold (or per-element seed and base) for the whole batch where the loop of single calls would draw one per call: the
+ *   batch draws once whenever count > 0, also when every member is empty; count == 0 returns before anything is drawn.  In per-element mode every
+ *   member indexes its own elements from 0.  A batch is its members, not their concatenation: the ragged last group of EACH member is not rotated.
+ * The parameters are always computed.  Empty members are skipped; up to 16 members go out in ONE streaming launch (more: one launch per 16); a
+ * member that fails the single call's alignment rule (quantize and dequantize: in and out 16-byte aligned; error feedback: in 16-byte, or 8-byte
+ * for bfloat16, residual and out 16-byte aligned) runs alone, in its place in the sequence, through the guarded one-wave-per-group launch of the
+ * single call: the same bytes.  A float buffer that is not aligned to its element aborts with the member's index.  Nothing outside a member's
+ * buffers is read or written; the buffers must not overlap.  Device (or pinned) buffers only; stream-ordered on the context's stream -- the
+ * quantize as piquant_hip_quantize_grouped_batch with computed parameters, the dequantize and the error-feedback batch always behind the previous
+ * call whatever piquant_hip_set_independent_calls says --; no host synchronisation, no allocation, the seed travels by value
+ * (hipGraph-capturable).  One encode and one decode launch is what a rotated grouped mesh all-reduce of up to 17 ranks makes of them. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                               void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                               size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                                                               uint64_t seed, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_dequantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                                 void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                                 size_t group_size, const float* const* scales, const uint8_t* const* zero_points,
+                                                                 size_t count, uint64_t seed, piquant_reduce_op_t op);
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                                  float* const* residuals, void* const* outputs, piquant_dtype_t dtype_out,
+                                                                  const size_t* numels, size_t group_size, float* const* scales,
+                                                                  uint8_t* const* zero_points, size_t count, uint64_t seed,
+                                                                  piquant_round_mode_t mode);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

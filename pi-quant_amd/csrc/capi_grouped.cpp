@@ -1,5 +1,5 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, and the two error-feedback calls of the rotated domain.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, the two error-feedback calls of the rotated domain, and the batches of the rotated quantize, dequantize and error-feedback quantize.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -529,6 +529,103 @@ void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* co
         [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
         [&](const GroupedTensor& t) { launch_dequantize_grouped(GroupedDequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
         [&] { launch_dequantize_grouped_batch(b, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The batches of the three rotated calls: the rules of the two batches above and of quantize_grouped_ef_batch (ONE threshold, or per-element seed and
+// base, per batch, drawn whenever count > 0; empty members skipped; one streaming launch per kGroupedBatchMaxTensors members), with the rotation's
+// seed.  A member that fails its single call's alignment rule runs alone, in its place in the sequence, through that call's guarded launch.
+void piquant_hip_quantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                                piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                                uint8_t* const* zero_points, size_t count, uint64_t seed, piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_rotated_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
+    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
+    const size_t esize = dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, false);
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0) bad(w, "in is not aligned to its element size");
+            return t;
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_quantize_grouped_rotated(GroupedQuantLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
+        [&] { launch_quantize_grouped_rotated_batch(b, seed, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                                  piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales,
+                                                  const uint8_t* const* zero_points, size_t count, uint64_t seed, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_grouped_rotated_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dequant_types(dtype_in, dtype_out, op);
+    check_group_size(group_size);
+    if (count == 0) return;
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    GroupedDequantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, {}, 0};
+    const size_t esize = dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+            if (reinterpret_cast<uintptr_t>(t.out) % esize != 0) bad(w, "out is not aligned to its element size");
+            return t;
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_dequantize_grouped_rotated(GroupedDequantLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
+        [&] { launch_dequantize_grouped_rotated_batch(b, seed, ctx->stream); });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, float* const* residuals,
+                                                   void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size,
+                                                   float* const* scales, uint8_t* const* zero_points, size_t count, uint64_t seed,
+                                                   piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_rotated_ef_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size, entry);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
+    GroupedEfBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
+    const bool f32 = dtype_in == PIQUANT_DTYPE_F32;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, true, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i]);
+            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i], numels[i]);
+            if (reinterpret_cast<uintptr_t>(t.in) % (f32 ? 4 : 2) != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0)
+                bad(w, "the tensor or its residual is not aligned to its element size");
+            return t;
+        },
+        [&](const GroupedTensor& t) { return (reinterpret_cast<uintptr_t>(t.in) & (f32 ? 15u : 7u)) == 0 && aligned16(t.residual) && aligned16(t.out); },
+        [&](const GroupedTensor& t) { launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
+        [&] { launch_quantize_grouped_rotated_ef_batch(b, seed, ctx->stream); });
     if (ctx->blocking) wait_stream(ctx);
 }
 

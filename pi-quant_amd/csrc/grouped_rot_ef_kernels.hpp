@@ -49,21 +49,16 @@ __device__ __forceinline__ void grouped_rot_ef_add_batched(u32x4 (&raw)[NV], con
 
 constexpr int kGroupedRotEfBatchRows = 4;
 
+// One wave's chunk (NG groups of the float32 tile from group g0 on) of one (tensor, residual) pair: the body of the single-tensor kernel and of the
+// batch kernel; the wave's LDS slices as in grouped_quantize_chunk with KEEP.
 template <int DT_IN, int BITS, int MODE, int G>
-__global__ void __launch_bounds__(kGroupedBlock)
-quantize_grouped_rotated_ef_kernel(const void* __restrict__ in, float* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
-                                   uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0) {
+__device__ __forceinline__ void grouped_rot_ef_chunk(const void* __restrict__ in, float* residual, uint8_t* __restrict__ out, int64_t numel,
+                                                     float* __restrict__ scales, uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo,
+                                                     uint32_t rot_hi, const QuantParams& p0, int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b,
+                                                     float* s_c) {
     using T = GroupedQuantTile<DT_F32, BITS, G>;
-    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64;
+    constexpr int NV = T::NV, NG = T::NG;
     constexpr bool EARLY = GroupedRotEfEarly<NV>::value;
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
-    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // {min, max}, then {1/scale, zero point, scale} of the chunk's groups
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    const int64_t g0 = chunk * NG;
-    if (g0 >= ngroups) return;
     const int64_t v0 = g0 * T::V;
     const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
 
@@ -80,9 +75,47 @@ quantize_grouped_rotated_ef_kernel(const void* __restrict__ in, float* residual,
     grouped_rotate_chunk<BITS, G, false>(raw, numel, g0, full, lane, rot_lo, rot_hi);
     if constexpr (EARLY) grouped_add_residual<DT_F32, NV>(raw, res);
     else grouped_rot_ef_add_batched<NV, kGroupedRotEfBatchRows>(raw, residual, numel, v0, lane, full);
-    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, s_out[wave], s_a[wave],
-                                                                   s_b[wave], s_c[wave]);
-    grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, s_out[wave], s_c[wave], s_b[wave]);
+    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false, NV, true>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b, s_c);
+    grouped_residual_store<DT_F32, BITS, G>(raw, residual, numel, v0, full, lane, stage, s_c, s_b);
+}
+
+template <int DT_IN, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_rotated_ef_kernel(const void* __restrict__ in, float* residual, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                   uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];   // {min, max}, then {1/scale, zero point, scale} of the chunk's groups
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    grouped_rot_ef_chunk<DT_IN, BITS, MODE, G>(in, residual, out, numel, scales, zero_points, ngroups, rot_lo, rot_hi, p0, g0, lane, s_out[wave], s_a[wave],
+                                               s_b[wave], s_c[wave]);
+}
+
+// Batch: up to kGroupedBatchMax independent (tensor, residual) pairs in ONE launch, found through the prefix table of quantize_grouped_batch_kernel
+// (unit: the chunk of the float32 tile, G * NG elements).  The residuals of the table are float32, whatever the tensors' type.
+template <int DT_IN, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_rotated_ef_batch_kernel(GroupedEfBatchArgs a, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG], s_c[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
+    const int64_t numel = a.numel[t];
+    grouped_rot_ef_chunk<DT_IN, BITS, MODE, G>(a.in[t], static_cast<float*>(a.residual[t]), a.out[t], numel, a.scales[t], a.zero_points[t],
+                                               (numel + G - 1) / G, rot_lo, rot_hi, p0, (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave],
+                                               s_b[wave], s_c[wave]);
 }
 
 // The term loop is reduce_quantize_grouped_rotated_kernel's: the first term's loads in front of the accumulator's, term i + 1 in flight while term

@@ -222,12 +222,28 @@ hadamard_grouped_kernel(const void* in, void* out, int64_t numel, int64_t ngroup
 
 // ---- quantize_grouped_rotated: the bytes, scales and zero points of quantize_grouped(y) with computed parameters, y the float32 forward rotation of
 // the widened tensor -- the float32 pipeline whatever the tensor's type; y never reaches memory.
+// One wave's chunk (NG groups of the float32 tile from group g0 on) of one tensor: the body of the single-tensor kernel and of the batch kernel.
+template <int DT_IN, int BITS, int MODE, int G>
+__device__ __forceinline__ void grouped_rot_quantize_chunk(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
+                                                           uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi,
+                                                           const QuantParams& p0, int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NV = T::NV, NG = T::NG;
+    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+
+    u32x4 raw[NV];
+    u32x2 t[NV];
+    grouped_rot_load<DT_IN, NV>(in, numel, g0 * T::V, lane, full, raw, t);
+    grouped_rotate_chunk<BITS, G, false>(raw, numel, g0, full, lane, rot_lo, rot_hi);
+    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, stage, s_a, s_b);
+}
+
 template <int DT_IN, int BITS, int MODE, int G>
 __global__ void __launch_bounds__(kGroupedBlock)
 quantize_grouped_rotated_kernel(const void* __restrict__ in, uint8_t* __restrict__ out, int64_t numel, float* __restrict__ scales,
                                 uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0) {
     using T = GroupedQuantTile<DT_F32, BITS, G>;
-    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
     __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
     __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // {min, max} of the chunk's groups, then {1/scale, zero point}
 
@@ -236,13 +252,28 @@ quantize_grouped_rotated_kernel(const void* __restrict__ in, uint8_t* __restrict
     const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
     const int64_t g0 = chunk * NG;
     if (g0 >= ngroups) return;
-    const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
+    grouped_rot_quantize_chunk<DT_IN, BITS, MODE, G>(in, out, numel, scales, zero_points, ngroups, rot_lo, rot_hi, p0, g0, lane, s_out[wave], s_a[wave],
+                                                     s_b[wave]);
+}
 
-    u32x4 raw[NV];
-    u32x2 t[NV];
-    grouped_rot_load<DT_IN, NV>(in, numel, g0 * T::V, lane, full, raw, t);
-    grouped_rotate_chunk<BITS, G, false>(raw, numel, g0, full, lane, rot_lo, rot_hi);
-    grouped_quantize_chunk<DT_F32, BITS, MODE, G, false>(raw, out, numel, scales, zero_points, ngroups, p0, g0, full, lane, s_out[wave], s_a[wave], s_b[wave]);
+// Batch: up to kGroupedBatchMax independent tensors in ONE launch, found through the prefix table of quantize_grouped_batch_kernel.  The table's
+// unit is the chunk of the FLOAT32 tile, G * NG elements, whatever the tensors' type; numel, ngroups and the ragged last group are each member's own.
+template <int DT_IN, int BITS, int MODE, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_grouped_rotated_batch_kernel(GroupedQuantBatchArgs a, uint32_t rot_lo, uint32_t rot_hi, QuantParams p0) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
+    const int64_t numel = a.numel[t];
+    grouped_rot_quantize_chunk<DT_IN, BITS, MODE, G>(a.in[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, rot_lo, rot_hi, p0,
+                                                     (c - a.chunk_begin[t]) * NG, lane, s_out[wave], s_a[wave], s_b[wave]);
 }
 
 // ---- dequantize_grouped_rotated: z = the float32 inverse rotation of dequantize_grouped(in -> float32, SET); out = convert(z) (SET) or
@@ -253,35 +284,27 @@ struct GroupedRotTerm {   // what grouped_park_term_partial reads of a term list
     const uint8_t* zero_points[1];
 };
 
+// One wave's chunk (NG groups of the float32 tile from group g0 on) of one tensor: the body of the single-tensor kernel and of the batch kernel.
 template <int DT_OUT, int BITS, int OP, int G>
-__global__ void __launch_bounds__(kGroupedBlock)
-dequantize_grouped_rotated_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
-                                  const uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi) {
+__device__ __forceinline__ void grouped_rot_dequantize_chunk(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel,
+                                                             const float* __restrict__ scales, const uint8_t* __restrict__ zero_points, int64_t ngroups,
+                                                             uint32_t rot_lo, uint32_t rot_hi, int64_t g0, int lane, uint8_t* stage, float* s_a, float* s_b,
+                                                             int32_t* s_z) {
     using T = GroupedQuantTile<DT_F32, BITS, G>;
     using L = GroupedTermLoad<DT_F32, BITS, G>;
-    constexpr int NV = T::NV, NG = T::NG, WAVES = kGroupedBlock / 64, PACK = 8 / BITS;
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::OUT_BYTES];
-    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // the groups' {scale, bias}
-    __shared__ int32_t s_z[WAVES][NG];                 // their zero points
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    const int64_t g0 = chunk * NG;
-    if (g0 >= ngroups) return;
+    constexpr int NV = T::NV, NG = T::NG, PACK = 8 / BITS;
     const int64_t v0 = g0 * T::V;
     const bool full = (g0 + NG) * G <= numel;                       // wave-uniform
     const int64_t gj = g0 + lane;
     const bool has_group = lane < NG && gj < ngroups;
-    uint8_t* stage = s_in[wave];
 
     if (full) {
         L term;
         term.load(in, scales, zero_points, v0, gj, has_group, lane);
-        grouped_park_term(term, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+        grouped_park_term(term, stage, s_a, s_b, s_z, has_group, lane);
     } else {
         const GroupedRotTerm one {{in}, {scales}, {zero_points}};
-        grouped_park_term_partial<T>(one, 0, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a[wave], s_b[wave], s_z[wave], has_group, lane);
+        grouped_park_term_partial<T>(one, 0, v0, (numel + PACK - 1) / PACK - v0 * T::OB, gj, stage, s_a, s_b, s_z, has_group, lane);
     }
     [[maybe_unused]] u32x4 old[NV];
     [[maybe_unused]] u32x2 told[NV];
@@ -289,7 +312,7 @@ dequantize_grouped_rotated_kernel(const uint8_t* __restrict__ in, void* __restri
     wave_lds_sync();
 
     u32x4 raw[NV];
-    grouped_set_term<DT_F32, BITS, G>(raw, stage, s_a[wave], s_b[wave], s_z[wave], lane);
+    grouped_set_term<DT_F32, BITS, G>(raw, stage, s_a, s_b, s_z, lane);
     grouped_rotate_chunk<BITS, G, true>(raw, numel, g0, full, lane, rot_lo, rot_hi);
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
@@ -305,6 +328,47 @@ dequantize_grouped_rotated_kernel(const uint8_t* __restrict__ in, void* __restri
             grouped_rot_store_bf16x4(out, numel, v0 + r * 64 + lane, full, o);
         }
     }
+}
+
+template <int DT_OUT, int BITS, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_rotated_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, int64_t numel, const float* __restrict__ scales,
+                                  const uint8_t* __restrict__ zero_points, int64_t ngroups, uint32_t rot_lo, uint32_t rot_hi) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];   // the groups' {scale, bias}
+    __shared__ int32_t s_z[WAVES][NG];                 // their zero points
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t chunk = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t g0 = chunk * NG;
+    if (g0 >= ngroups) return;
+    grouped_rot_dequantize_chunk<DT_OUT, BITS, OP, G>(in, out, numel, scales, zero_points, ngroups, rot_lo, rot_hi, g0, lane, s_in[wave], s_a[wave],
+                                                      s_b[wave], s_z[wave]);
+}
+
+// Batch: up to kGroupedBatchMax independent packed tensors in ONE launch, found through the prefix table of quantize_grouped_batch_kernel.  The
+// table's unit is again the chunk of the FLOAT32 quantize tile, G * NG elements -- NOT GroupedDequantTile's CHUNK_ELEMS, the unit of
+// dequantize_grouped_batch_kernel: this kernel sits on the quantize tile, as the single-tensor one does.
+template <int DT_OUT, int BITS, int OP, int G>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_grouped_rotated_batch_kernel(GroupedDequantBatchArgs a, uint32_t rot_lo, uint32_t rot_hi) {
+    using T = GroupedQuantTile<DT_F32, BITS, G>;
+    constexpr int NG = T::NG, WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[WAVES][T::OUT_BYTES];
+    __shared__ float s_a[WAVES][NG], s_b[WAVES][NG];
+    __shared__ int32_t s_z[WAVES][NG];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
+    const int64_t numel = a.numel[t];
+    grouped_rot_dequantize_chunk<DT_OUT, BITS, OP, G>(a.in[t], a.out[t], numel, a.scales[t], a.zero_points[t], (numel + G - 1) / G, rot_lo, rot_hi,
+                                                      (c - a.chunk_begin[t]) * NG, lane, s_in[wave], s_a[wave], s_b[wave], s_z[wave]);
 }
 
 // ---- reduce_quantize_grouped_rotated: the bytes, scales and zero points of quantize_grouped(y) with computed parameters, y = the float32 forward

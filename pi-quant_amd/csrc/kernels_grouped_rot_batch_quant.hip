@@ -1,0 +1,54 @@
+// Instantiation and launch of the batched rotated grouped quantize (grouped_rot_kernels.hpp: quantize_grouped_rotated_batch_kernel): its 144
+// instances (two tensor types, three widths, three rounding modes, eight group sizes) compile next to the other kernel units, on the same flags.
+// A batch of one goes to launch_quantize_grouped_rotated (kernels_grouped_rot_quant.hip), so the single-tensor kernels are instantiated there only.
+#define PQ_MINMAX_HELPERS_ONLY   // the scan state kernels are defined in kernels.hip
+#include "launch.hpp"
+
+#include "grouped_dispatch.hpp"
+#include "grouped_rot_kernels.hpp"
+#include "stop_event.hpp"
+
+namespace pq {
+
+// The chunk table's unit is the chunk of the FLOAT32 tile, whatever the tensors' type: the pipeline is the float32 one.
+void launch_quantize_grouped_rotated_batch(const GroupedQuantBatchLaunch& b, uint64_t rot_seed, hipStream_t stream) {
+    const char* name = "quantize_grouped_rotated";
+    static_assert(kGroupedBatchMaxTensors == kGroupedBatchMax, "host and device batch limits");
+    if (b.count <= 0) return;
+    if (b.count > kGroupedBatchMax) panic("%s_batch: %d tensors, at most %d per launch", name, b.count, kGroupedBatchMax);
+    if (b.count == 1) {   // the single call: its arguments arrive as leading scalars, no table
+        launch_quantize_grouped_rotated(GroupedQuantLaunch {b.t[0], b}, rot_seed, false, stream, 0);
+        return;
+    }
+    const QuantParams p = grouped_call_params(b.rm);
+    const uint32_t lo = static_cast<uint32_t>(rot_seed), hi = static_cast<uint32_t>(rot_seed >> 32);
+    with_float_type(b.dt_in, [&](auto di) {
+        constexpr int DT_IN = decltype(di)::value;
+        with_quant_bits(b.dt_out, [&](auto bi) {
+            constexpr int BITS = decltype(bi)::value;
+            with_round_mode<DT_F32, BITS>(b.rm.round_mode, [&](auto mi) {
+                constexpr int MODE = decltype(mi)::value;
+                with_group_size(b.group_size, name, [&](auto gi) {
+                    constexpr int G = decltype(gi)::value;
+                    constexpr int NG = GroupedQuantTile<DT_F32, BITS, G>::NG;
+                    GroupedQuantBatchArgs a {};
+                    for (int t = 0; t < b.count; ++t) {
+                        a.in[t] = b.t[t].in;
+                        a.out[t] = static_cast<uint8_t*>(b.t[t].out);
+                        a.scales[t] = b.t[t].scales;
+                        a.zero_points[t] = b.t[t].zero_points;
+                        a.numel[t] = b.t[t].numel;
+                    }
+                    a.count = b.count;
+                    const int64_t chunks = fill_chunk_table(a, static_cast<int64_t>(G) * NG);
+                    if (chunks == 0) return;
+                    const dim3 grid(grouped_blocks(chunks, name));
+                    PQ_LAUNCH((quantize_grouped_rotated_batch_kernel<DT_IN, BITS, MODE, G>), grid, dim3(kGroupedBlock), 0, stream, a, lo, hi, p);
+                });
+            });
+        });
+    });
+    PQ_HIP(hipGetLastError());
+}
+
+}  // namespace pq

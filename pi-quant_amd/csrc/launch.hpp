@@ -228,6 +228,13 @@ void launch_dequantize_sum_grouped_rotated(const GroupedDequantSumLaunch& d, uin
 // element-aligned, the same bytes.
 void launch_quantize_grouped_rotated_ef(const GroupedEfLaunch& q, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
 void launch_reduce_quantize_grouped_rotated_ef(const GroupedReduceLaunch& r, uint64_t rot_seed, bool guarded, hipStream_t stream, int num_cu);
+// The batched rotated launches (kernels_grouped_rot_batch*.hip): up to kGroupedBatchMaxTensors tensors of one dtype pair, group size, round mode and
+// rotation seed in ONE launch of the streaming kernel -- every member non-empty and aligned as the single streaming launch needs it (the caller
+// sends anything else through the guarded single launches); member i gets the bytes of the single launch on member i.  A batch of one launches the
+// single-tensor kernel.  Every t[i].residual of the error-feedback batch is float32.
+void launch_quantize_grouped_rotated_batch(const GroupedQuantBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
+void launch_dequantize_grouped_rotated_batch(const GroupedDequantBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
+void launch_quantize_grouped_rotated_ef_batch(const GroupedEfBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

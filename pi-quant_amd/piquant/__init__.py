@@ -603,6 +603,47 @@ class Context:
                                                          _ptr_array(zero_points_in), n, ptr_out, dtype_out.value, numel, group_size, scales_ptr,
                                                          zero_points_ptr, int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
 
+    def quantize_grouped_rotated_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
+                                           zero_points_ptrs, seed: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_rotated_ptr`` for several independent tensors (own parameter arrays each), up to 16 per kernel launch
+        (``piquant_hip_quantize_grouped_rotated_batch``); one rotation seed and one stochastic threshold for the batch."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and dtype_out.is_quantized and n == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_rotated_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value,
+                                                     _size_array(numels), group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n,
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
+    def dequantize_grouped_rotated_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
+                                             zero_points_ptrs, seed: int, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
+        """``dequantize_grouped_rotated_ptr`` for several independent tensors, up to 16 per kernel launch
+        (``piquant_hip_dequantize_grouped_rotated_batch``); one rotation seed for the batch."""
+        n = len(ptrs_in)
+        assert dtype_in.is_quantized and dtype_out.is_dequantized and n == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_grouped_rotated_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value,
+                                                       _size_array(numels), group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n,
+                                                       int(seed) & 0xFFFFFFFFFFFFFFFF, reduce_op.value)
+
+    def quantize_grouped_rotated_ef_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_residual, ptrs_out, dtype_out: DataType, numels, group_size: int,
+                                              scales_ptrs, zero_points_ptrs, seed: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_rotated_ef_ptr`` for several independent (tensor, residual) pairs, up to 16 per kernel launch
+        (``piquant_hip_quantize_grouped_rotated_ef_batch``); every residual is float32, whatever ``dtype_in`` is; one rotation seed and one
+        stochastic threshold for the batch."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        assert n == len(ptrs_residual) == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_rotated_ef_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_residual), _ptr_array(ptrs_out),
+                                                        dtype_out.value, _size_array(numels), group_size, _ptr_array(scales_ptrs),
+                                                        _ptr_array(zero_points_ptrs), n, int(seed) & 0xFFFFFFFFFFFFFFFF, round_mode.value)
+
     def reduce_quantize_grouped_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, ptr_residual: int, ptrs_in, scales_in, zero_points_in, ptr_out: int,
                                        dtype_out: DataType, numel: int, group_size: int, scales_ptr: int, zero_points_ptr: int, round_mode: RoundMode,
                                        _device_ptrs: bool = False, residual_dtype: Optional[DataType] = None) -> None:

@@ -569,14 +569,21 @@ class _DeviceOps:
                                                      group_size, sc, zp, seed, _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     def encode_batch_grouped_rotated(self, xs, bufs, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
-        """encode_grouped_rotated(xs[i], bufs[i]) for all i, one launch EACH: there is no batched rotated quantize yet."""
-        for x, b in zip(xs, bufs):
-            self.encode_grouped_rotated(x, b, qdtype, round_mode, group_size, seed)
+        """encode_grouped_rotated(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_grouped_rotated_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r[2] for r in recs],
+                                                               torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
+                                                               [r[1] for r in recs], seed, self._mode(round_mode), _device_ptrs=True)
 
     def decode_batch_grouped_rotated(self, bufs, outs, qdtype: torch.dtype, reduce_op: str, group_size: int, seed: int) -> None:
-        """decode_grouped_rotated(bufs[i], outs[i]) for all i, one launch EACH: there is no batched rotated dequantize yet."""
-        for b, o in zip(bufs, outs):
-            self.decode_grouped_rotated(b, o, qdtype, reduce_op, group_size, seed)
+        """decode_grouped_rotated(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
+        if bufs:
+            recs = [self._record(b, o.numel(), qdtype, group_size) for b, o in zip(bufs, outs)]
+            self._cx(outs[0]).dequantize_grouped_rotated_batch_ptr([r[2] for r in recs], torch_to_piquant_dtype(qdtype), [o.data_ptr() for o in outs],
+                                                                   torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], group_size,
+                                                                   [r[0] for r in recs], [r[1] for r in recs], seed, _REDUCE_OPS[reduce_op],
+                                                                   _device_ptrs=True)
 
     def reduce_encode_grouped_rotated(self, bufs, acc: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int,
                                       seed: int) -> None:
@@ -598,9 +605,13 @@ class _DeviceOps:
                                                     x.numel(), group_size, sc, zp, seed, self._mode(round_mode), _device_ptrs=True)
 
     def encode_batch_grouped_rotated_ef(self, xs, residuals, bufs, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
-        """encode_grouped_rotated_ef(xs[i], residuals[i], bufs[i]) for all i, one launch EACH, as encode_batch_grouped_rotated."""
-        for x, r, b in zip(xs, residuals, bufs):
-            self.encode_grouped_rotated_ef(x, r, b, qdtype, round_mode, group_size, seed)
+        """encode_grouped_rotated_ef(xs[i], residuals[i], bufs[i]) for all i with one kernel launch per 16 chunks (float32 residuals)."""
+        if xs:
+            recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_grouped_rotated_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype),
+                                                                  [r.data_ptr() for r in residuals], [r[2] for r in recs], torch_to_piquant_dtype(qdtype),
+                                                                  [x.numel() for x in xs], group_size, [r[0] for r in recs], [r[1] for r in recs], seed,
+                                                                  self._mode(round_mode), _device_ptrs=True)
 
     def reduce_encode_grouped_rotated_ef(self, bufs, acc: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str,
                                          group_size: int, seed: int) -> None:
@@ -988,8 +999,12 @@ def quantized_all_reduce(
     all-reduce (the one-launch reduce would not: it keeps the sum in the rotated domain); every decode ``dequantize_grouped_rotated`` 'set' of
     the same gathered bytes on every rank, the owner included: all ranks end bit-identical.  The wire format is unchanged; ``ring_chunks`` keeps
     every interior boundary on a multiple of 4096 elements, so every chunk rotates exactly as the whole tensor does.  ALL RANKS MUST PASS THE SAME
-    SEED: the library does not check it, and ranks that disagree sum values of different domains.  There is no batched rotated launch yet: the
-    mesh encodes its world - 1 chunks, and decodes its world chunks, with one launch each.  uint2 records gain nothing from the rotation in the
+    SEED: the library does not check it, and ranks that disagree sum values of different domains.  The mesh encodes its world - 1 chunks with ONE
+    ``quantize_grouped_rotated_batch`` launch and decodes its world chunks with ONE ``dequantize_grouped_rotated_batch`` launch (one per 16
+    chunks), as the un-rotated grouped mesh does with its batches: with the owner's two launches, four launches per all-reduce.  One consequence,
+    the un-rotated grouped mesh's rule: with ``round_mode='stochastic'`` and no pinned threshold a rotated mesh draws ONE threshold per batch,
+    where it drew one per chunk while every chunk was a launch of its own; the bytes under nearest rounding, under a pinned threshold
+    (``Context.set_stochastic_threshold``) and in per-element mode are what they were.  uint2 records gain nothing from the rotation in the
     all-reduce without error feedback.  ValueError before anything moves: without ``group_size``, with ``transport='p2p'``, with
     ``error_feedback`` (that residual lives in the original domain; ``rotated_error_feedback`` is the one that goes with a rotation), and in the
     direct schedule with more than 17 ranks (the owner's one launch sums at most 16 records).
@@ -998,7 +1013,8 @@ def quantized_all_reduce(
     without it): error feedback with the residual kept in the ROTATED domain -- a contiguous FLOAT32 tensor (float32 also for a bfloat16 tensor)
     of the tensor's device and numel that the caller keeps between steps (zeros before the first).  It is a keyword of its own because it is a
     different object from ``error_feedback``'s residual: a record of rotated values.  Every encode of this rank's own contribution becomes
-    ``quantize_grouped_rotated_ef`` on the matching slice (the ring's first encode, the mesh's peer chunks, one launch each); with
+    ``quantize_grouped_rotated_ef`` on the matching slice (the ring's first encode; the mesh's peer chunks, ONE
+    ``quantize_grouped_rotated_ef_batch`` launch per 16 of them); with
     ``error_feedback_requantize`` every hop of the ring becomes ONE ``reduce_quantize_grouped_rotated_ef`` launch on the hop's chunk, and the
     mesh owner's ``quantize_grouped_rotated`` becomes ``quantize_grouped_rotated_ef`` on the rank's own chunk: each chunk of the residual is then
     touched exactly once per call.  The residual belongs to one (world size, rank, algorithm, ``error_feedback_requantize``, SEED, GROUP SIZE):
@@ -1287,13 +1303,14 @@ def quantized_reduce_scatter(
     ``quantized_all_reduce(algorithm='direct', group_size=group_size)``: that schedule's ``reduce_quantize_grouped`` is defined as these ADDs
     followed by ``quantize_grouped``.
 
-    ``rotation_seed`` (the same int on all ranks; not checked): the peers' chunks are encoded by ``quantize_grouped_rotated`` (one launch each),
+    ``rotation_seed`` (the same int on all ranks; not checked): the peers' chunks are encoded by ONE ``quantize_grouped_rotated_batch``
+    launch per 16 chunks,
     and step 3 is ONE ``dequantize_sum_grouped_rotated(..., 'add')`` launch: the received records are summed in float32 in the rotated domain
     and the sum is rotated back once and added into the own chunk.  Followed by ``quantized_all_gather`` with the same seed it leaves exactly the bytes
     of ``quantized_all_reduce(algorithm='direct', rotation_seed=...)``, whose owner's step is these two.  At most 17 ranks; not with ``error_feedback``.
 
     ``rotated_error_feedback`` (``rotation_seed`` only): the float32 rotated-domain residual of ``quantized_all_reduce``; the peers' chunks are
-    encoded by ``quantize_grouped_rotated_ef`` on their chunks of it, the rank's own chunk of it is neither read nor written.  Followed by
+    encoded by ONE ``quantize_grouped_rotated_ef_batch`` launch per 16 on their chunks of it, the rank's own chunk of it is neither read nor written.  Followed by
     ``quantized_all_gather`` with the same residual it leaves exactly the tensor bytes and residual bytes of ``quantized_all_reduce(algorithm='direct',
     error_feedback_requantize=True)``.  The residual belongs to one (world size, rank, seed, group size).
 
@@ -1348,8 +1365,8 @@ def quantized_all_gather(
     ``quantized_reduce_scatter`` (which uses the peers' chunks) and this call unless that is the intent -- together the two touch every chunk
     exactly once, as ``quantized_all_reduce`` with ``error_feedback_requantize`` does.
 
-    ``rotation_seed`` (the same int on all ranks; not checked): step 1 is ``quantize_grouped_rotated``, step 3 one
-    ``dequantize_grouped_rotated(..., 'set')`` launch per chunk.  Not with ``error_feedback``.
+    ``rotation_seed`` (the same int on all ranks; not checked): step 1 is ``quantize_grouped_rotated``, step 3 ONE
+    ``dequantize_grouped_rotated_batch(..., 'set')`` launch per 16 chunks.  Not with ``error_feedback``.
 
     ``rotated_error_feedback`` (``rotation_seed`` only): the float32 rotated-domain residual of ``quantized_all_reduce``; step 1 becomes
     ``quantize_grouped_rotated_ef`` on the rank's own chunk of it, no other chunk is touched.  It belongs to one (world size, rank, seed, group

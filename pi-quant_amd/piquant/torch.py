@@ -696,9 +696,10 @@ def quantize_grouped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128
     return _quantize_grouped_batch(tensors, _NA, dtype, group_size, round_mode, ctx, outs, scales, zero_points, _GIVEN_PAIR, 'scales and zero_points')
 
 
-def _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, ctx, outs, scales, zero_points, pair_rule: str, what: str):
+def _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, ctx, outs, scales, zero_points, pair_rule: str, what: str, seed=None):
     """``quantize_grouped_batch`` (``residuals`` is ``_NA``; ``scales`` / ``zero_points`` are given parameters) and ``quantize_grouped_ef_batch`` (they are
-    its ``out_scales`` / ``out_zero_points``): the second checks the residuals and makes the ``_ef`` call."""
+    its ``out_scales`` / ``out_zero_points``): the second checks the residuals and makes the ``_ef`` call.  With a ``seed``: their rotated forms,
+    whose parameters are always computed (``scales`` / ``zero_points`` are outputs) and whose residuals are float32."""
     _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
     _require((scales is None) == (zero_points is None), pair_rule)
     tensors = list(tensors)
@@ -717,6 +718,9 @@ def _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, c
     if residuals is not _NA:
         for i, (t, r) in enumerate(zip(tensors, residuals)):
             _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, f'tensors[{i}] must be a float32 or bfloat16 tensor')
+            if seed is not None:
+                _check_rotated_residual(r, t, f'residuals[{i}]')
+                continue
             _check_residual(r, t, f'residuals[{i}]')
             _require(r.dtype == residuals[0].dtype, f'the residuals of a batch must share one dtype, got {residuals[0].dtype} and {r.dtype}')
     for i, t in enumerate(tensors):
@@ -729,7 +733,13 @@ def _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, c
     outs = _packed_outs(outs, dtype, tensors, device)
     ctx = _ctx_for(tensors[0], ctx)
     fdt, qdt, mode = torch_to_piquant_dtype(tensors[0].dtype), torch_to_piquant_dtype(dtype), _ROUND_MODES[round_mode]
-    if residuals is _NA:
+    if seed is not None and residuals is _NA:
+        ctx.quantize_grouped_rotated_batch_ptr(_ptrs(tensors), fdt, _ptrs(outs), qdt, numels, group_size, _ptrs(scales), _ptrs(zero_points), seed, mode,
+                                               _device_ptrs=True)
+    elif seed is not None:
+        ctx.quantize_grouped_rotated_ef_batch_ptr(_ptrs(tensors), fdt, _ptrs(residuals), _ptrs(outs), qdt, numels, group_size, _ptrs(scales),
+                                                  _ptrs(zero_points), seed, mode, _device_ptrs=True)
+    elif residuals is _NA:
         ctx.quantize_grouped_batch_ptr(_ptrs(tensors), fdt, _ptrs(outs), qdt, numels, group_size, _ptrs(scales), _ptrs(zero_points), given, mode, _device_ptrs=True)
     else:
         ctx.quantize_grouped_ef_batch_ptr(_ptrs(tensors), fdt, _ptrs(residuals), _ptrs(outs), qdt, numels, group_size, _ptrs(scales), _ptrs(zero_points), mode,
@@ -950,10 +960,47 @@ def quantize_grouped_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_s
                                    'out_scales and out_zero_points')
 
 
+def quantize_grouped_rotated_batch(tensors, *, dtype: torch.dtype, group_size: int = 128, seed=_NA, round_mode: str = 'nearest',
+                                   ctx: Optional[Context] = None, outs=None, out_scales=None, out_zero_points=None):
+    """``quantize_grouped_rotated`` of several independent tensors (one dtype pair, group size, ``seed`` and round mode) with one kernel launch per
+    16 tensors.  Returns (outs, scales, zero_points) as lists; tensor i's entries equal ``quantize_grouped_rotated(tensors[i], seed=seed)`` (a
+    stochastic batch draws one threshold).  A batch is its members, not their concatenation: the ragged last group of each tensor is not rotated
+    (``include/piquant_hip.h``, piquant_hip_quantize_grouped_rotated_batch)."""
+    seed = _check_seed(seed)
+    return _quantize_grouped_batch(tensors, _NA, dtype, group_size, round_mode, ctx, outs, out_scales, out_zero_points, _OUT_PAIR,
+                                   'out_scales and out_zero_points', seed)
+
+
+def quantize_grouped_rotated_ef_batch(tensors, residuals, *, dtype: torch.dtype, group_size: int = 128, seed=_NA, round_mode: str = 'nearest',
+                                      ctx: Optional[Context] = None, outs=None, out_scales=None, out_zero_points=None):
+    """``quantize_grouped_rotated_ef`` of several independent (tensor, residual) pairs (one dtype pair, group size, ``seed`` and round mode) with
+    one kernel launch per 16 pairs.  Returns (outs, scales, zero_points) as lists; pair i's entries and its updated residual equal
+    ``quantize_grouped_rotated_ef(tensors[i], residuals[i], seed=seed)`` (a stochastic batch draws one threshold).  Every residual is float32, also
+    for bfloat16 tensors (``include/piquant_hip.h``, piquant_hip_quantize_grouped_rotated_ef_batch)."""
+    seed = _check_seed(seed)
+    return _quantize_grouped_batch(tensors, residuals, dtype, group_size, round_mode, ctx, outs, out_scales, out_zero_points, _OUT_PAIR,
+                                   'out_scales and out_zero_points', seed)
+
+
 def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, reduce_op: str = 'set', ctx: Optional[Context] = None,
                              outs=None, quant_dtype: Optional[torch.dtype] = None, shapes=None):
     """``dequantize_grouped`` of several independent tensors with one kernel launch per 16 tensors; returns the list of outputs.  Raw uint8
     buffers of packed bytes need ``quant_dtype=`` and ``shapes=`` (one shape per tensor); ``reduce_op='add'`` accumulates into ``outs``."""
+    return _dequantize_grouped_batch(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, outs, quant_dtype, shapes)
+
+
+def dequantize_grouped_rotated_batch(tensors, scales, zero_points, *, dtype: torch.dtype, group_size: int, seed=_NA, reduce_op: str = 'set',
+                                     ctx: Optional[Context] = None, outs=None, quant_dtype: Optional[torch.dtype] = None, shapes=None):
+    """``dequantize_grouped_rotated`` of several independent tensors (records made with the same ``seed``) with one kernel launch per 16 tensors;
+    returns the list of outputs, output i equal to ``dequantize_grouped_rotated(tensors[i], scales[i], zero_points[i], seed=seed)``.  Raw uint8
+    buffers of packed bytes need ``quant_dtype=`` and ``shapes=`` (one shape per tensor); ``reduce_op='add'`` accumulates into ``outs``
+    (``include/piquant_hip.h``, piquant_hip_dequantize_grouped_rotated_batch)."""
+    seed = _check_seed(seed)
+    return _dequantize_grouped_batch(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, outs, quant_dtype, shapes, seed)
+
+
+def _dequantize_grouped_batch(tensors, scales, zero_points, dtype, group_size, reduce_op, ctx, outs, quant_dtype, shapes, seed=None):
+    """``dequantize_grouped_batch`` and, with a ``seed``, ``dequantize_grouped_rotated_batch``."""
     _check_modes(float_dtype=dtype, reduce_op=reduce_op, group_size=group_size)
     tensors, scales, zero_points = list(tensors), list(scales), list(zero_points)
     outs = None if outs is None else list(outs)
@@ -972,6 +1019,10 @@ def dequantize_grouped_batch(tensors, scales, zero_points, *, dtype: torch.dtype
     _check_grouped_terms(tensors, scales, zero_points, metas[0][0], numels, group_size, device)
     outs = _float_outs(outs, reduce_op, dtype, [shape for _, shape in metas], numels, device)
     ctx = _ctx_for(tensors[0], ctx)
+    if seed is not None:
+        ctx.dequantize_grouped_rotated_batch_ptr(_ptrs(tensors), metas[0][0], _ptrs(outs), torch_to_piquant_dtype(dtype), numels, group_size, _ptrs(scales),
+                                                 _ptrs(zero_points), seed, _REDUCE_OPS[reduce_op], _device_ptrs=True)
+        return outs
     ctx.dequantize_grouped_batch_ptr(_ptrs(tensors), metas[0][0], _ptrs(outs), torch_to_piquant_dtype(dtype), numels, group_size, _ptrs(scales),
                                      _ptrs(zero_points), _REDUCE_OPS[reduce_op], _device_ptrs=True)
     return outs

@@ -58,7 +58,16 @@ against the rotation, k float32 grouped dequantize ADD launches and quantize_gro
 fused / composition against the byte ratio is reported as met or missed.  Writes profiles/grouped_rot_ef_bench.json; --rows all appends these
 rows to its table.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce|rot_ef] [--windows 7] [--rotate-gb 3.3] [--out FILE]
+--rows rot_batch: the batched rotated launches (G = 128; fp32 -> uint8 and bf16 -> uint4): quantize_grouped_rotated_batch and
+quantize_grouped_rotated_ef_batch of the 7 peer chunks of an 8-way mesh (numel / 8 each) and dequantize_grouped_rotated_batch SET of its 8 chunks,
+each next to the loop of as many single calls in the same run; and one rank's replayed 8-way rotated mesh (fp32 -> uint4: encode batch,
+dequantize_sum_grouped_rotated ADD + quantize_grouped_rotated, decode batch) through piquant.distributed._DeviceOps as it is, next to a local copy
+of its former three loops.  Each row: stream time from HIP events around windows of whole sequences, met or missed against the loop's time plus the
+loop's own spread (max - min over its windows); --kernel-stats FILE (the kernel statistics of tools/grouped_rot_batch_workload.py under
+rocprofv3 --kernel-trace --stats) adds the sums of the kernel times, judged with the same spread.  Writes profiles/grouped_rot_batch_bench.json;
+--rows all appends these rows to its table.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce|rot_ef|rot_batch] [--windows 7] [--rotate-gb 3.3] [--out FILE] [--kernel-stats FILE]
 """
 import argparse
 import json
@@ -898,20 +907,227 @@ def rot_ef_rows(ctx, dev, stream, args, G=128, seed=0x9E3779B97F4A7C15):
     return rows
 
 
+ROT_SEED = 0x9E3779B97F4A7C15
+ROT_BATCH_PAIRS = (("f32", "uint8"), ("bf16", "uint4"))
+ROT_BATCH_MESH_PAIR = ("f32", "uint4")   # another instance than the rows', so that a kernel trace of the whole run keeps the two apart
+
+
+def rot_batch_cases(ctx, dev, rotate_gb, G=128, world=8, seed=ROT_SEED):
+    """The three batched rotated calls on the chunks of an 8-way mesh (world - 1 members for the two quantizing calls, world for the dequantize, each
+    of NUMEL / world elements), next to the loop of single calls -- what the parent of the batched launches made of the same chunks.  Yields
+    (kind, pair, members, nbuf, bytes, batch(i), loop(i)) with `nbuf` cold sets of buffers; tools/grouped_rot_batch_workload.py runs the same
+    cases under a profiler."""
+    per = NUMEL // world
+    gs = pt.num_groups(per, G)
+    g = torch.Generator(device=dev)
+    g.manual_seed(12)
+    nearest, op_set = piquant.RoundMode.NEAREST, piquant.ReduceOp.SET
+    for fname, qname in ROT_BATCH_PAIRS:
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        nq = qdt.packed_nbytes(per)
+        for kind, m in (("quantize_grouped_rotated", world - 1), ("quantize_grouped_rotated_ef", world - 1), ("dequantize_grouped_rotated", world)):
+            ef, deq = kind.endswith("_ef"), kind.startswith("dequantize")
+            member = per * esize + nq + 5 * gs + (8 * per if ef else 0)
+            nbuf = max(3, int(rotate_gb * 1e9 / (m * member)) + 1)
+            xs = [[torch.empty(per, device=dev).normal_(generator=g).to(tdt) for _ in range(m)] for _ in range(nbuf)]
+            rs = [[torch.empty(per, device=dev).normal_(generator=g).mul_(0.01) for _ in range(m)] for _ in range(nbuf)] if ef else None
+            if deq:
+                qs = [[torch.randint(0, 256, (nq,), dtype=torch.uint8, device=dev, generator=g) for _ in range(m)] for _ in range(nbuf)]
+                sc = [[torch.empty(gs, device=dev).uniform_(1e-3, 2e-3, generator=g) for _ in range(m)] for _ in range(nbuf)]
+                zs = [[torch.randint(0, 1 << bits, (gs,), dtype=torch.uint8, device=dev, generator=g) for _ in range(m)] for _ in range(nbuf)]
+            else:
+                qs = [[torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(m)] for _ in range(nbuf)]
+                sc = [[torch.empty(gs, dtype=torch.float32, device=dev) for _ in range(m)] for _ in range(nbuf)]
+                zs = [[torch.empty(gs, dtype=torch.uint8, device=dev) for _ in range(m)] for _ in range(nbuf)]
+            ptrs = lambda ts: [t.data_ptr() for t in ts]   # noqa: E731
+
+            def batch(i, ef=ef, deq=deq, xs=xs, rs=rs, qs=qs, sc=sc, zs=zs, m=m, fdt=fdt, qdt=qdt):
+                if deq:
+                    ctx.dequantize_grouped_rotated_batch_ptr(ptrs(qs[i]), qdt, ptrs(xs[i]), fdt, [per] * m, G, ptrs(sc[i]), ptrs(zs[i]), seed, op_set,
+                                                             _device_ptrs=True)
+                elif ef:
+                    ctx.quantize_grouped_rotated_ef_batch_ptr(ptrs(xs[i]), fdt, ptrs(rs[i]), ptrs(qs[i]), qdt, [per] * m, G, ptrs(sc[i]), ptrs(zs[i]), seed,
+                                                              nearest, _device_ptrs=True)
+                else:
+                    ctx.quantize_grouped_rotated_batch_ptr(ptrs(xs[i]), fdt, ptrs(qs[i]), qdt, [per] * m, G, ptrs(sc[i]), ptrs(zs[i]), seed, nearest,
+                                                           _device_ptrs=True)
+
+            def loop(i, ef=ef, deq=deq, xs=xs, rs=rs, qs=qs, sc=sc, zs=zs, m=m, fdt=fdt, qdt=qdt):
+                for j in range(m):
+                    if deq:
+                        ctx.dequantize_grouped_rotated_ptr(qs[i][j].data_ptr(), qdt, xs[i][j].data_ptr(), fdt, per, G, sc[i][j].data_ptr(),
+                                                           zs[i][j].data_ptr(), seed, op_set, _device_ptrs=True)
+                    elif ef:
+                        ctx.quantize_grouped_rotated_ef_ptr(xs[i][j].data_ptr(), fdt, rs[i][j].data_ptr(), qs[i][j].data_ptr(), qdt, per, G,
+                                                            sc[i][j].data_ptr(), zs[i][j].data_ptr(), seed, nearest, _device_ptrs=True)
+                    else:
+                        ctx.quantize_grouped_rotated_ptr(xs[i][j].data_ptr(), fdt, qs[i][j].data_ptr(), qdt, per, G, sc[i][j].data_ptr(),
+                                                         zs[i][j].data_ptr(), seed, nearest, _device_ptrs=True)
+
+            yield kind, (f"{qname}->{fname}" if deq else f"{fname}->{qname}"), m, nbuf, m * member, batch, loop
+            del xs, rs, qs, sc, zs, batch, loop
+            torch.cuda.empty_cache()
+
+
+def rot_batch_mesh(ctx, dev, G=128, world=8, seed=ROT_SEED):
+    """One rank's kernels of an 8-way rotated grouped mesh all-reduce (no wire: stand-in receive buffers), built as the replayed-mesh rows of
+    --rows ef are: the encode batch of the world - 1 peer chunks, the owner's dequantize_sum_grouped_rotated ADD + quantize_grouped_rotated, the
+    decode batch of the world chunks.  -> {"batched": mesh(), "loop": mesh()}: piquant.distributed._DeviceOps as it is, and the same with a local
+    copy of the three loops of single launches it had before the batched rotated launches."""
+    import piquant.distributed as D
+
+    class LoopOps(D._DeviceOps):
+        def encode_batch_grouped_rotated(self, xs, bufs, qdtype, round_mode, group_size, seed):
+            for x, b in zip(xs, bufs):
+                self.encode_grouped_rotated(x, b, qdtype, round_mode, group_size, seed)
+
+        def decode_batch_grouped_rotated(self, bufs, outs, qdtype, reduce_op, group_size, seed):
+            for b, o in zip(bufs, outs):
+                self.decode_grouped_rotated(b, o, qdtype, reduce_op, group_size, seed)
+
+        def encode_batch_grouped_rotated_ef(self, xs, residuals, bufs, qdtype, round_mode, group_size, seed):
+            for x, r, b in zip(xs, residuals, bufs):
+                self.encode_grouped_rotated_ef(x, r, b, qdtype, round_mode, group_size, seed)
+
+    fname, qname = ROT_BATCH_MESH_PAIR
+    bits = QUANT[qname][1]
+    qdt = {8: torch.uint8, 4: torch.quint4x2, 2: torch.quint2x4}[bits]
+    g = torch.Generator(device=dev)
+    g.manual_seed(13)
+    x = torch.empty(NUMEL, device=dev).normal_(generator=g).to(FLOAT[fname][1])
+    chunks = D.ring_chunks(NUMEL, world, bits)
+    gbytes = [D.grouped_wire_layout(e - b, G, bits).nbytes for b, e in chunks]
+    slot = -(-max(gbytes) // 16) * 16
+    bufs = torch.zeros(world * slot, dtype=torch.uint8, device=dev)
+    mine = torch.zeros(slot, dtype=torch.uint8, device=dev)
+    peers = list(range(1, world))
+    D._DeviceOps(ctx).encode_batch_grouped_rotated([x[b:e] for b, e in chunks], [bufs[j * slot: j * slot + gbytes[j]] for j in range(world)], qdt, "nearest",
+                                                   G, seed)
+
+    def mesh_of(ops):
+        def mesh():
+            ops.encode_batch_grouped_rotated([x[chunks[j][0]:chunks[j][1]] for j in peers], [bufs[j * slot: j * slot + gbytes[j]] for j in peers], qdt,
+                                             "nearest", G, seed)
+            own = x[chunks[0][0]:chunks[0][1]]
+            ops.decode_sum_grouped_rotated([bufs[i * slot: i * slot + gbytes[0]] for i in peers], own, qdt, "add", G, seed)
+            ops.encode_grouped_rotated(own, mine[: gbytes[0]], qdt, "nearest", G, seed)
+            ops.decode_batch_grouped_rotated([bufs[j * slot: j * slot + gbytes[j]] for j in range(world)], [x[chunks[j][0]:chunks[j][1]] for j in range(world)],
+                                             qdt, "set", G, seed)
+        return mesh
+
+    return {"batched": mesh_of(D._DeviceOps(ctx)), "loop": mesh_of(LoopOps(ctx))}
+
+
+def rot_batch_kernel_sums(path, world=8):
+    """{(kind, pair): (batch kernel us, loop kernel us)} from the kernel statistics (rocprofv3 --kernel-trace --stats, CSV) of a run of
+    tools/grouped_rot_batch_workload.py: a batch is ONE dispatch of its batch kernel, the loop `members` dispatches of the single-tensor kernel."""
+    import csv
+    import re
+
+    avg = {}
+    with open(path, newline="") as f:
+        for r in csv.DictReader(f):
+            m = re.search(r"pq::(\w+)<(\d+), (\d+), \d+, 128>", r["Name"])
+            if m:
+                avg[(m.group(1), int(m.group(2)), int(m.group(3)))] = float(r["AverageNs"]) / 1000.0
+    dt = {"f32": int(piquant.DataType.F32.value), "bf16": int(piquant.DataType.BF16.value)}
+    sums = {}
+    for fname, qname in ROT_BATCH_PAIRS:
+        key = (dt[fname], QUANT[qname][1])
+        for kind, m, pair in (("quantize_grouped_rotated", world - 1, f"{fname}->{qname}"), ("quantize_grouped_rotated_ef", world - 1, f"{fname}->{qname}"),
+                              ("dequantize_grouped_rotated", world, f"{qname}->{fname}")):
+            sums[(kind, pair)] = (avg[(kind + "_batch_kernel",) + key], m * avg[(kind + "_kernel",) + key])
+    fname, qname = ROT_BATCH_MESH_PAIR
+    key = (dt[fname], QUANT[qname][1])
+    owner = avg[("dequantize_sum_grouped_rotated_kernel",) + key] + avg[("quantize_grouped_rotated_kernel",) + key]
+    sums[("rotated_mesh_kernels_per_rank", f"{fname}->{qname}")] = (
+        avg[("quantize_grouped_rotated_batch_kernel",) + key] + owner + avg[("dequantize_grouped_rotated_batch_kernel",) + key],
+        (world - 1) * avg[("quantize_grouped_rotated_kernel",) + key] + owner + world * avg[("dequantize_grouped_rotated_kernel",) + key])
+    return sums
+
+
+def rot_batch_rows(ctx, dev, stream, args, G=128, world=8):
+    """the batched rotated launches against the loop of single launches, in the same run: stream time (HIP events around each window of whole
+    sequences) and, with --kernel-stats, the sum of the kernel times.  Targets: the batch's stream time <= the loop's + the loop's own spread
+    (max - min over its windows); the batch's kernel time <= the loop's kernel-time sum + that same spread."""
+    rows = []
+    sums = rot_batch_kernel_sums(args.kernel_stats, world) if args.kernel_stats else {}
+
+    def judge(br, lr, key):
+        spread = max(lr["windows_us"]) - min(lr["windows_us"])
+        br["loop_us"], br["loop_spread_us"], br["over_loop"] = lr["us"], round(spread, 3), round(br["us"] / lr["us"], 3)
+        br["stream_time_target"] = "met" if br["us"] <= lr["us"] + spread else "missed"
+        line = f"    batch / loop = {br['over_loop']:.3f} (loop spread {spread:.2f} us): stream time {br['stream_time_target']}"
+        if key in sums:
+            br["kernel_us"], br["loop_kernel_us"] = round(sums[key][0], 3), round(sums[key][1], 3)
+            br["kernel_time_target"] = "met" if sums[key][0] <= sums[key][1] + spread else "missed"
+            line += f"; kernel time {br['kernel_us']:.2f} against {br['loop_kernel_us']:.2f} us: {br['kernel_time_target']}"
+        print(line, flush=True)
+
+    for kind, pair, m, nbuf, nbytes, batch, loop in rot_batch_cases(ctx, dev, args.rotate_gb, G, world):
+        per_window = max(2 * nbuf, 32)
+        us_l, s_l = timed(loop, nbuf, args.windows, per_window, stream)
+        lr = row(f"{kind} x{m} single", pair, G, us_l, nbytes, s_l)
+        us_b, s_b = timed(batch, nbuf, args.windows, per_window, stream)
+        br = row(f"{kind}_batch {m}", pair, G, us_b, nbytes, s_b)
+        judge(br, lr, (kind, pair))
+        rows += [lr, br]
+    # one rank's replayed mesh: windows of 20 replays of the captured sequence
+    meshes = rot_batch_mesh(ctx, dev, G, world)
+    res = {}
+    for name in ("loop", "batched"):
+        mesh = meshes[name]
+        for _ in range(3):
+            mesh()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            mesh()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph, stream=side):
+                mesh()
+            graph.replay()
+            torch.cuda.synchronize()
+            samples = []
+            for _ in range(args.windows):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(20):
+                    graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                samples.append(e0.elapsed_time(e1) * 1e3 / 20)
+        res[name] = samples
+    ctx.set_stream(stream.cuda_stream)
+    pair = "->".join(ROT_BATCH_MESH_PAIR)
+    launches = {"loop": (world - 1) + 2 + world, "batched": 4}
+    out = {}
+    for name in ("loop", "batched"):
+        out[name] = {"kind": f"rotated_mesh_kernels_per_rank ({name})", "pair": pair, "group_size": G, "world": world,
+                     "launches_per_all_reduce": launches[name], "us": round(statistics.median(res[name]), 3), "windows_us": [round(s, 3) for s in res[name]]}
+        print(f"rotated mesh {pair} ({name}, {launches[name]} launches): {out[name]['us']:.1f} us per replay", flush=True)
+    judge(out["batched"], out["loop"], ("rotated_mesh_kernels_per_rank", pair))
+    return rows + [out["loop"], out["batched"]]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce", "rot_ef"),
-                    default="all")
+    ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce", "rot_ef",
+                                       "rot_batch"), default="all")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernel-stats", default=None, help="rot_batch rows: kernel statistics CSV of tools/grouped_rot_batch_workload.py under rocprofv3")
     args = ap.parse_args()
     if args.out is None:
         args.out = str(ROOT / "profiles" / {"all": "grouped_bench.json", "reduce": "grouped_reduce_bench.json", "ef": "grouped_ef_bench.json",
                                                    "reduce_ef": "grouped_reduce_ef_bench.json", "ef_f32r": "grouped_ef_f32r_bench.json",
                                                    "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
                                                    "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json",
-                                                   "rot_reduce": "grouped_rot_reduce_bench.json", "rot_ef": "grouped_rot_ef_bench.json"}[args.rows])
+                                                   "rot_reduce": "grouped_rot_reduce_bench.json", "rot_ef": "grouped_rot_ef_bench.json",
+                                                   "rot_batch": "grouped_rot_batch_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -941,6 +1157,8 @@ def main():
         rows = rot_reduce_rows(ctx, dev, stream, args)
     if args.rows == "rot_ef":
         rows = rot_ef_rows(ctx, dev, stream, args)
+    if args.rows == "rot_batch":
+        rows = rot_batch_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
@@ -987,6 +1205,7 @@ def main():
         rows += requant_rows(ctx, dev, stream, args)
         rows += dequant_sum_rows(ctx, dev, stream, args)
         rows += rot_ef_rows(ctx, dev, stream, args)
+        rows += rot_batch_rows(ctx, dev, stream, args)
     out = Path(args.out)
     out.parent.mkdir(parents=True, exist_ok=True)
     out.write_text(json.dumps({"numel": NUMEL, "device": torch.cuda.get_device_name(0), "hbm_peak_gbs": HBM_PEAK_GBS, "rotate_gb": args.rotate_gb,
