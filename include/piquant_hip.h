@@ -488,6 +488,41 @@ PIQUANT_EXPORT void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_contex
                                                                   uint8_t* const* zero_points, size_t count, uint64_t seed,
                                                                   piquant_round_mode_t mode);
 
+/* PER-GROUP CLIP SEARCH.  piquant_hip_quantize_grouped takes a group's step from its min and max, which on a narrow wire spends most codes on the
+ * tails.  piquant_hip_quantize_grouped_clipped tries, for every group on its own, `steps` (1 .. 12) ranges shrunk towards zero and keeps the one
+ * whose round trip loses the least squared error -- in ONE launch that reads `in` once.  A searched group is an ordinary group with other
+ * parameters: the wire format and every dequantizing call are untouched.  The parameters are always computed.
+ * THE DEFINITION, every step float32 unless it says otherwise.  xf is `in` widened to float32.  For every FULL group g, with lo, hi the min and
+ * max piquant_hip_quantize_grouped finds (NaNs ignored):
+ *   1. candidate k, 0 <= k < steps: lo_k = lo * r_k, hi_k = hi * r_k, one multiplication each, r_k = 1 - k / 16 (exact); (scale_k, zp_k) is
+ *      piquant_hip_quant_params_from_minmax(lo_k, hi_k), the zero point clamped to [0, qmax] as everywhere.  Candidate 0 is exactly the pair of
+ *      piquant_hip_quantize_grouped.  A candidate with not hi_k > lo_k is skipped;
+ *   2. its error, ALWAYS with nearest rounding whatever `mode` is: q = the position-independent quantize of the group with (scale_k, zp_k);
+ *      d = what piquant_hip_dequantize_grouped(q, ..., float32, PIQUANT_REDUCE_OP_SET) stores -- float32 also for a bfloat16 `in`;
+ *      e_i = xf_i - d_i and s_i = e_i * e_i, two roundings, never an fma; s_i = +0 where xf_i is a NaN; E_k = the sum of s_0 .. s_{G-1} by the
+ *      adjacent-pair tree (replace s by s[2j] + s[2j+1] until one value is left), nothing fused;
+ *   3. best = 0; for k = 1 .. steps - 1 in order: if E_k < E_best then best = k.  Strict: a NaN E_k never wins, a tie keeps the smaller k, and
+ *      an E_0 that is NaN or +inf is never beaten;
+ *   4. NOT searched (best = 0): a degenerate group (not hi > lo: constant, all NaN), the ragged last group, every group when steps == 1;
+ *   5. the bytes of `out` are those of piquant_hip_quantize_grouped(in, ..., scales, zero_points, params_given = 1, mode) with the chosen pairs,
+ *      in every rounding mode (ONE threshold per call; the per-element mode indexes the global element); scales[g] / zero_points[g] hold the
+ *      chosen pair and choices[g] -- uint8[ngroups], device, may be NULL -- receives best.
+ * steps == 1 is piquant_hip_quantize_grouped with computed parameters, bit for bit.  steps outside [1, 12] aborts.
+ * Buffers that are not 16-byte aligned take a guarded one-wave-per-group launch that writes the same bytes; `in` not aligned to its element aborts.
+ * piquant_hip_quantize_grouped_clipped_batch: tensor i has its own input, output, scales, zero_points, numels[i] and choices[i] (the list, or any
+ * entry of it, may be NULL), with the rules of piquant_hip_quantize_grouped_batch: member i gets the bytes, parameters and choices of the single
+ * call on it, one threshold per batch, up to 16 tensors per launch and one launch per 16 beyond, empty tensors skipped, a misaligned member runs
+ * alone in its place in the sequence.
+ * Device (or pinned) buffers only; stream-ordered on the context's stream as piquant_hip_quantize_grouped with computed parameters is; no scan, no
+ * atomics, no grid barrier, no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op that draws no threshold. */
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_clipped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out,
+                                                         piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales,
+                                                         uint8_t* zero_points, uint8_t* choices, int steps, piquant_round_mode_t mode);
+PIQUANT_EXPORT void piquant_hip_quantize_grouped_clipped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
+                                                               void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels,
+                                                               size_t group_size, float* const* scales, uint8_t* const* zero_points,
+                                                               uint8_t* const* choices, size_t count, int steps, piquant_round_mode_t mode);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

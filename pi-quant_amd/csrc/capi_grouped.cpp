@@ -1,5 +1,5 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, the two error-feedback calls of the rotated domain, and the batches of the rotated quantize, dequantize and error-feedback quantize.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
+// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, the two error-feedback calls of the rotated domain, the batches of the rotated quantize, dequantize and error-feedback quantize, and the quantize with a per-group clip search and its batch.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
 // draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
 // owns them.
 #include "context.hpp"
@@ -627,6 +627,60 @@ void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_context_t* ctx, const
         [&](const GroupedTensor& t) { launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
         [&] { launch_quantize_grouped_rotated_ef_batch(b, seed, ctx->stream); });
     if (ctx->blocking) wait_stream(ctx);
+}
+
+// The clip search (grouped_clip_kernels.hpp): piquant_hip_quantize_grouped_batch's rules with computed parameters, the candidates' count and the
+// members' choices.  A member whose in or out is not 16-byte aligned runs alone through the guarded launch: the same bytes.  steps == 1 searches
+// nothing: it IS quantize_grouped with computed parameters, so its launches are made and the members' choices are zeroed on the stream.
+void piquant_hip_quantize_grouped_clipped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                                                piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
+                                                uint8_t* const* zero_points, uint8_t* const* choices, size_t count, int steps,
+                                                piquant_round_mode_t mode) {
+    const char* entry = "piquant_hip_quantize_grouped_clipped_batch";
+    if (!ctx) panic("%s: context is NULL", entry);
+    check_dynamic_types(dtype_in, dtype_out, mode);
+    check_group_size(group_size, entry);
+    if (steps < 1 || steps > 12) panic("%s: steps %d is not in [1, 12]", entry, steps);
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
+    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
+    const size_t esize = dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2;
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, false);
+    run_batch(
+        b, numels, count,
+        [&](size_t i) {
+            const Where w {entry, static_cast<long>(i)};
+            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+            GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0) bad(w, "in is not aligned to its element size");
+            if (choices && choices[i]) t.choices = static_cast<uint8_t*>(device_ptr(w, resolve(choices[i])));
+            if (steps == 1 && t.choices) PQ_HIP(hipMemsetAsync(t.choices, 0, (numels[i] + group_size - 1) / group_size, ctx->stream));
+            return t;
+        },
+        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
+        [&](const GroupedTensor& t) {
+            if (steps == 1) launch_quantize_grouped(GroupedQuantLaunch {t, b}, ctx->stream, ctx->num_cu);
+            else launch_quantize_grouped_clipped_guarded(GroupedQuantLaunch {t, b}, steps, ctx->stream, ctx->num_cu);
+        },
+        [&] {
+            if (steps == 1 && b.count == 1) launch_quantize_grouped(GroupedQuantLaunch {b.t[0], b}, ctx->stream, ctx->num_cu);   // the single kernel
+            else if (steps == 1) launch_quantize_grouped_batch(b, ctx->stream);
+            else launch_quantize_grouped_clipped_batch(b, steps, ctx->stream);
+        });
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The single call is a batch of one, which launches the single-tensor kernel; an empty tensor returns behind the argument checks and draws nothing.
+void piquant_hip_quantize_grouped_clipped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
+                                          size_t numel, size_t group_size, float* scales, uint8_t* zero_points, uint8_t* choices, int steps,
+                                          piquant_round_mode_t mode) {
+    if (!ctx) panic("piquant_hip_quantize_grouped_clipped: context is NULL");
+    piquant_hip_quantize_grouped_clipped_batch(ctx, &in, dtype_in, &out, dtype_out, &numel, group_size, &scales, &zero_points, &choices, numel == 0 ? 0 : 1,
+                                               steps, mode);
 }
 
 void piquant_hip_reduce_quantize_grouped(piquant_context_t* ctx, void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,

@@ -1,5 +1,5 @@
 // Host code shared by the translation units that instantiate the grouped kernels (kernels_grouped.hip, kernels_grouped_ef.hip,
-// kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip, kernels_grouped_reduce_ef_f32r.hip, kernels_grouped_requant*.hip, kernels_grouped_dequant_sum.hip, kernels_grouped_rot*.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
+// kernels_grouped_ef_f32r.hip, kernels_grouped_reduce_ef.hip, kernels_grouped_reduce_ef_f32r.hip, kernels_grouped_requant*.hip, kernels_grouped_dequant_sum.hip, kernels_grouped_rot*.hip, kernels_grouped_clip.hip): runtime group size / types / rounding mode -> std::integral_constant, the per-call
 // QuantParams, the chunk table and grids, and the launch bodies of the error-feedback kernel families and of the fused reduce kernels.
 #pragma once
 

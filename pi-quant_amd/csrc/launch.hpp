@@ -110,6 +110,7 @@ struct GroupedTensor {
     float* scales;         // float32[ngroups], device (dequantize only reads the parameters)
     uint8_t* zero_points;  // uint8[ngroups], device
     int64_t numel;
+    uint8_t* choices = nullptr;   // clip search only: uint8[ngroups], device, written; may stay NULL
 };
 struct GroupedQuantCall {
     int64_t group_size;
@@ -235,6 +236,12 @@ void launch_reduce_quantize_grouped_rotated_ef(const GroupedReduceLaunch& r, uin
 void launch_quantize_grouped_rotated_batch(const GroupedQuantBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
 void launch_dequantize_grouped_rotated_batch(const GroupedDequantBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
 void launch_quantize_grouped_rotated_ef_batch(const GroupedEfBatchLaunch& b, uint64_t rot_seed, hipStream_t stream);
+// quantize_grouped with a per-group clip search (grouped_clip_kernels.hpp; kernels_grouped_clip.hip): every full, non-degenerate group tries `steps`
+// (1 .. 12) shrunk ranges and is quantized with the one whose nearest round trip loses least; parameters always computed (params_given is not
+// used), t.choices -- where not NULL -- receives the winners' indices.  The batch takes members whose in and out are 16-byte aligned, ONE launch (a
+// batch of one launches the single-tensor kernel); the guarded launch runs one tensor of any element alignment, the same bytes.
+void launch_quantize_grouped_clipped_batch(const GroupedQuantBatchLaunch& b, int steps, hipStream_t stream);
+void launch_quantize_grouped_clipped_guarded(const GroupedQuantLaunch& q, int steps, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -460,6 +460,33 @@ class Context:
         C.piquant_hip_quantize_grouped_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value, _size_array(numels),
                                              group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs), n, 1 if params_given else 0, round_mode.value)
 
+    def quantize_grouped_clipped_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, group_size: int,
+                                     scales_ptr: int, zero_points_ptr: int, choices_ptr: int, steps: int, round_mode: RoundMode,
+                                     _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_ptr`` with a per-group clip search (``piquant_hip_quantize_grouped_clipped``): every full group tries ``steps`` (1 to 12)
+        ranges shrunk towards zero and is quantized with the one whose nearest round trip loses least.  The parameters are written; ``choices_ptr``
+        (a uint8[ngroups] device array, or 0) receives the chosen candidates."""
+        assert dtype_in.is_dequantized and dtype_out.is_quantized
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_clipped(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
+                                               choices_ptr or None, steps, round_mode.value)
+
+    def quantize_grouped_clipped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
+                                           zero_points_ptrs, choices_ptrs, steps: int, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
+        """``quantize_grouped_clipped_ptr`` for several independent tensors, up to 16 per kernel launch
+        (``piquant_hip_quantize_grouped_clipped_batch``); one stochastic threshold for the batch.  ``choices_ptrs`` may be None, or hold 0 for a member
+        whose choices are not wanted."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and dtype_out.is_quantized and n == len(ptrs_out) == len(numels) == len(scales_ptrs) == len(zero_points_ptrs)
+        assert choices_ptrs is None or len(choices_ptrs) == n
+        if n == 0:
+            return
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_grouped_clipped_batch(self._ctx, _ptr_array(ptrs_in), dtype_in.value, _ptr_array(ptrs_out), dtype_out.value,
+                                                     _size_array(numels), group_size, _ptr_array(scales_ptrs), _ptr_array(zero_points_ptrs),
+                                                     None if choices_ptrs is None else _ptr_array([p or None for p in choices_ptrs]), n, steps,
+                                                     round_mode.value)
+
     def dequantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
                                      zero_points_ptrs, reduce_op: ReduceOp, _device_ptrs: bool = False) -> None:
         """``dequantize_grouped_ptr`` for several independent tensors, up to 16 per kernel launch (``piquant_hip_dequantize_grouped_batch``)."""

@@ -81,6 +81,9 @@ _DECLS = [
                                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, C.c_uint64, _int]),
     ('piquant_hip_quantize_grouped_rotated_ef_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _int,
                                                              C.POINTER(_sz), _sz, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, C.c_uint64, _int]),
+    ('piquant_hip_quantize_grouped_clipped', None, [_vp, _vp, _int, _vp, _int, _sz, _sz, _vp, _vp, _vp, _int, _int]),
+    ('piquant_hip_quantize_grouped_clipped_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int, C.POINTER(_sz), _sz,
+                                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _int, _int]),
     ('piquant_hip_reduce_quantize_grouped_ef', None, [_vp, _vp, _int, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _int,
                                                       _sz, _sz, _vp, _vp, _int]),
     ('piquant_hip_quantize_grouped_ef', None, [_vp, _vp, _int, _vp, _vp, _int, _sz, _sz, _vp, _vp, _int]),

@@ -503,6 +503,20 @@ class _DeviceOps:
                                                        torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
                                                        [r[1] for r in recs], False, self._mode(round_mode), _device_ptrs=True)
 
+    def encode_grouped_clipped(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int, steps: int) -> None:
+        """encode_grouped with the per-group clip search (``clip_steps``): the same record, other parameters."""
+        sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
+        self._cx(x).quantize_grouped_clipped_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), data, torch_to_piquant_dtype(qdtype), x.numel(), group_size,
+                                                 sc, zp, 0, steps, self._mode(round_mode), _device_ptrs=True)
+
+    def encode_batch_grouped_clipped(self, xs, bufs, qdtype: torch.dtype, round_mode: str, group_size: int, steps: int) -> None:
+        """encode_grouped_clipped(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record(b, x.numel(), qdtype, group_size) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_grouped_clipped_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r[2] for r in recs],
+                                                               torch_to_piquant_dtype(qdtype), [x.numel() for x in xs], group_size, [r[0] for r in recs],
+                                                               [r[1] for r in recs], None, steps, self._mode(round_mode), _device_ptrs=True)
+
     def encode_grouped_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int) -> None:
         """encode_grouped(x + residual) with residual <- (x + residual) - what the record decodes to, one launch.  The residual's dtype goes down
         with it: float32 for a bfloat16 ``x`` is the float32 pipeline on the widened ``x``."""
@@ -769,9 +783,10 @@ class _Wire:
     takes part, the step works on that slice of it."""
 
     def __init__(self, ops, quant_dtype: torch.dtype, round_mode: str, group_size: Optional[int] = None, residual: Optional[torch.Tensor] = None,
-                 requantize: bool = False, rotation_seed: Optional[int] = None):
+                 requantize: bool = False, rotation_seed: Optional[int] = None, clip_steps: Optional[int] = None):
         self.ops, self.round_mode, self.group_size = ops, round_mode, group_size
         self.seed = rotation_seed
+        self.clip_steps = clip_steps             # the encodes search each group's clipping range (never with a seed or a residual: _check_clip_steps)
         self.quant_dtype, self.qdt = quant_dtype, torch_to_piquant_dtype(quant_dtype)     # the torch dtype the ops take, its DataType for the lengths
         self.residual = None if residual is None else residual.view(-1)
         self.requantize = requantize
@@ -786,6 +801,8 @@ class _Wire:
         """``ef`` False: the rotated owner's encode without ``requantize``, which leaves the residual alone."""
         if self.group_size is None:
             self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
+        elif self.clip_steps is not None:
+            self.ops.encode_grouped_clipped(x, buf, self.quant_dtype, self.round_mode, self.group_size, self.clip_steps)
         elif self.seed is not None and (self.residual is None or not ef):
             self.ops.encode_grouped_rotated(x, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif self.seed is not None:
@@ -798,6 +815,8 @@ class _Wire:
     def encode_batch(self, xs, bufs, chunks) -> None:
         if self.group_size is None:
             self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
+        elif self.clip_steps is not None:
+            self.ops.encode_batch_grouped_clipped(xs, bufs, self.quant_dtype, self.round_mode, self.group_size, self.clip_steps)
         elif self.seed is not None and self.residual is None:
             self.ops.encode_batch_grouped_rotated(xs, bufs, self.quant_dtype, self.round_mode, self.group_size, self.seed)
         elif self.seed is not None:
@@ -951,6 +970,7 @@ def quantized_all_reduce(
     error_feedback_requantize: bool = False,
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
+    clip_steps: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1048,9 +1068,13 @@ def quantized_all_reduce(
     stores ``dequantize(..., 'set')`` of the same bytes, so all ranks end bit-identical.  Wire traffic per element is
     1 byte (uint8) / 0.5 (uint4) instead of 4, over the same 2(G-1)/G ring schedule; each xGMI link carries one
     point-to-point stream, which is what the per-link (not NVSwitch-style) bandwidth of MI355X wants.
+
+    ``clip_steps`` must stay None: the per-group clip search serves ``quantized_reduce_scatter`` and ``quantized_all_gather``, where no partial sum
+    is re-quantized; here it raises ValueError before anything moves.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
+    _check_clip_steps(clip_steps, group_size, all_reduce=True)
     if algorithm not in ('ring', 'direct'):
         raise ValueError(f"algorithm must be 'ring' or 'direct', got {algorithm!r}")
     if transport not in ('collective', 'p2p'):
@@ -1091,6 +1115,7 @@ def quantized_all_reduce_direct(
     error_feedback_requantize: bool = False,
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
+    clip_steps: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1139,6 +1164,7 @@ def quantized_all_reduce_direct(
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
+    _check_clip_steps(clip_steps, group_size, all_reduce=True)
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
     _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
@@ -1256,6 +1282,27 @@ def _check_rotated_terms(seed, world: int, what: str) -> None:
                          f'got {world}')
 
 
+def _check_clip_steps(clip_steps, group_size, rotation_seed=None, error_feedback=None, rotated_error_feedback=None, transport: str = 'collective',
+                      all_reduce: bool = False) -> None:
+    """ValueError before anything moves: ``clip_steps`` is None or an int in [1, 12], on the grouped wire, where no partial sum is re-quantized
+    and nothing else changes what is encoded."""
+    if clip_steps is None:
+        return
+    if all_reduce:
+        raise ValueError('clip_steps= is not supported by quantized_all_reduce: its ring hops and its owner step re-quantize partial sums, which needs '
+                         'a clipped fused reduce; use quantized_reduce_scatter / quantized_all_gather')
+    if not (isinstance(clip_steps, int) and not isinstance(clip_steps, bool) and 1 <= clip_steps <= 12):
+        raise ValueError(f'clip_steps must be None or an int in [1, 12], got {clip_steps!r}')
+    if group_size is None:
+        raise ValueError('clip_steps= needs the grouped wire: pass group_size= (the search is per group)')
+    if rotation_seed is not None:
+        raise ValueError('clip_steps= is not supported with rotation_seed=')
+    if error_feedback is not None or rotated_error_feedback is not None:
+        raise ValueError('clip_steps= is not supported with error_feedback= or rotated_error_feedback= (the clipped mass would have to be carried forward)')
+    if transport == 'p2p':
+        raise ValueError("clip_steps= is not supported with transport='p2p'; use transport='collective'")
+
+
 def _check_sharded_collective(name: str, tensor: torch.Tensor, group_size, error_feedback) -> None:
     """ValueError before anything moves, for ``quantized_reduce_scatter`` and ``quantized_all_gather``: the tensor, a group size that is no group
     size (``None`` included: they have the grouped wire only) and a residual that does not match the tensor."""
@@ -1278,6 +1325,7 @@ def quantized_reduce_scatter(
     error_feedback: Optional[torch.Tensor] = None,
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
+    clip_steps: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1314,12 +1362,17 @@ def quantized_reduce_scatter(
     ``quantized_all_gather`` with the same residual it leaves exactly the tensor bytes and residual bytes of ``quantized_all_reduce(algorithm='direct',
     error_feedback_requantize=True)``.  The residual belongs to one (world size, rank, seed, group size).
 
+    ``clip_steps`` (None, or an int in [1, 12]; the same value on all ranks, not checked): step 1 becomes ONE ``quantize_grouped_clipped_batch``
+    launch per 16 chunks -- every group of every record is quantized with the best of ``clip_steps`` shrunk ranges (``piquant.torch.quantize_grouped_clipped``);
+    the records, the all-to-all and step 3 are unchanged.  Not with ``rotation_seed``, ``error_feedback`` or ``rotated_error_feedback``.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
     of this module's multi-GPU paths.)"""
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
+    _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     _check_rotated_terms(seed, world, 'quantized_reduce_scatter')
@@ -1328,7 +1381,7 @@ def quantized_reduce_scatter(
         b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
         return flat[b_own:e_own]
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 rotation_seed=seed)
+                 rotation_seed=seed, clip_steps=clip_steps)
     ch = _Chunks.of(wire, flat, world)
     x_own = ch.views[rank]
     terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
@@ -1348,6 +1401,7 @@ def quantized_all_gather(
     error_feedback: Optional[torch.Tensor] = None,
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
+    clip_steps: Optional[int] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1372,17 +1426,21 @@ def quantized_all_gather(
     ``quantize_grouped_rotated_ef`` on the rank's own chunk of it, no other chunk is touched.  It belongs to one (world size, rank, seed, group
     size).
 
+    ``clip_steps`` (as in ``quantized_reduce_scatter``): step 1 becomes ``quantize_grouped_clipped`` on the rank's own chunk; steps 2 and 3 are
+    unchanged.  Not with ``rotation_seed``, ``error_feedback`` or ``rotated_error_feedback``.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
     _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
+    _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 rotation_seed=seed)
+                 rotation_seed=seed, clip_steps=clip_steps)
     ch = _Chunks.of(wire, tensor.view(-1), world)
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
     if ch.views[rank].numel():

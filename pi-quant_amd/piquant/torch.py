@@ -523,6 +523,93 @@ def quantize_grouped(tensor: torch.Tensor, *, dtype: torch.dtype, group_size: in
     return out, scales, zero_points
 
 
+CLIP_STEPS_MAX = 12   # candidate ranges of the clip search: r_k = 1 - k / 16, k < steps
+
+
+def _check_clip_steps(steps) -> None:
+    _require(isinstance(steps, int) and not isinstance(steps, bool) and 1 <= steps <= CLIP_STEPS_MAX,
+             f'steps must be an int in [1, {CLIP_STEPS_MAX}], got {steps!r}')
+
+
+def _check_choices(choices, ngroups: int, device: torch.device, what: str) -> None:
+    _require(isinstance(choices, torch.Tensor) and choices.dtype == torch.uint8 and choices.dim() == 1 and choices.numel() == ngroups and
+             choices.is_contiguous(), f'{what} must be a contiguous 1-D uint8 tensor of {ngroups} elements')
+    _require(choices.device == device, f'{what} must live on {device}')
+
+
+def quantize_grouped_clipped(tensor: torch.Tensor, *, dtype: torch.dtype, group_size: int = 128, steps: int = 9, round_mode: str = 'nearest',
+                             ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None, out_scales: Optional[torch.Tensor] = None,
+                             out_zero_points: Optional[torch.Tensor] = None, out_choices: Optional[torch.Tensor] = None,
+                             return_choices: bool = False):
+    """``quantize_grouped`` (computed parameters) with a per-group search for the clipping range, in one launch: every full group tries ``steps``
+    ranges -- its min and max both shrunk towards zero by ``1 - k / 16``, ``k < steps`` -- and is quantized with the one whose nearest round trip
+    has the smallest squared error (ties keep the smaller ``k``; ``k = 0`` is ``quantize_grouped``'s range).  On a narrow wire this is worth a
+    large part of the error (uint2, Gaussian, group_size 128: about half); a searched group is an ordinary group, so ``dequantize_grouped`` and
+    every other consumer take the result as it is.  Constant and all-NaN groups and a ragged last group are not searched; ``steps=1`` is
+    ``quantize_grouped`` bit for bit.  Returns (quantized, scales, zero_points), and with ``return_choices=True`` also the uint8[ngroups] tensor
+    of the chosen ``k`` (``include/piquant_hip.h``, piquant_hip_quantize_grouped_clipped, has the definition)."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    _check_clip_steps(steps)
+    _require((out_scales is None) == (out_zero_points is None), _OUT_PAIR)
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    ngroups = num_groups(tensor.numel(), group_size)
+    if out_scales is not None:
+        _check_group_params(out_scales, out_zero_points, ngroups)
+    _check_float_input(tensor)
+    scales, zero_points = _group_params_of(out_scales, out_zero_points, tensor.numel(), group_size, tensor.device, 'out_scales and out_zero_points',
+                                           shapes_checked=True)
+    if out_choices is not None:
+        _check_choices(out_choices, ngroups, tensor.device, 'out_choices')
+    elif return_choices:
+        out_choices = torch.empty(ngroups, dtype=torch.uint8, device=tensor.device)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    out = _packed_out(out, dtype, tensor, tensor.device)
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_grouped_clipped_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), out.data_ptr(), torch_to_piquant_dtype(dtype),
+                                     tensor.numel(), group_size, scales.data_ptr(), zero_points.data_ptr(),
+                                     0 if out_choices is None else out_choices.data_ptr(), steps, _ROUND_MODES[round_mode], _device_ptrs=True)
+    return (out, scales, zero_points, out_choices) if return_choices else (out, scales, zero_points)
+
+
+def quantize_grouped_clipped_batch(tensors, *, dtype: torch.dtype, group_size: int = 128, steps: int = 9, round_mode: str = 'nearest',
+                                   ctx: Optional[Context] = None, outs=None, scales=None, zero_points=None, choices=None,
+                                   return_choices: bool = False):
+    """``quantize_grouped_clipped`` of several independent tensors (one dtype pair, group size, ``steps`` and round mode) with one kernel launch per
+    16 tensors.  Returns (outs, scales, zero_points) as lists -- ``scales`` / ``zero_points`` are outputs, given or allocated -- and with
+    ``return_choices=True`` also the list of choices; tensor i's entries equal ``quantize_grouped_clipped(tensors[i])`` (a stochastic batch draws
+    one threshold) (``include/piquant_hip.h``, piquant_hip_quantize_grouped_clipped_batch)."""
+    _check_modes(quant_dtype=dtype, round_mode=round_mode, group_size=group_size)
+    _check_clip_steps(steps)
+    _require((scales is None) == (zero_points is None), 'pass both scales and zero_points or neither')
+    tensors = list(tensors)
+    lists = [tensors]
+    for given in (outs, scales, zero_points, choices):
+        if given is not None:
+            lists.append(list(given))
+    _check_batch_lists(*lists)
+    for i, t in enumerate(tensors):
+        _check_float_input(t, f'tensors[{i}]')
+        _require(t.device == tensors[0].device and t.dtype == tensors[0].dtype, 'the tensors of a batch must share one device and one dtype')
+    device = tensors[0].device
+    tensors = _contiguous(tensors)
+    numels = [t.numel() for t in tensors]
+    scales, zero_points = _group_params(None if scales is None else list(scales), None if zero_points is None else list(zero_points), numels, group_size,
+                                        device, 'scales and zero_points')
+    if choices is not None:
+        choices = list(choices)
+        for i, (c, n) in enumerate(zip(choices, numels)):
+            _check_choices(c, num_groups(n, group_size), device, f'choices[{i}]')
+    elif return_choices:
+        choices = [torch.empty(num_groups(n, group_size), dtype=torch.uint8, device=device) for n in numels]
+    outs = _packed_outs(None if outs is None else list(outs), dtype, tensors, device)
+    ctx = _ctx_for(tensors[0], ctx)
+    ctx.quantize_grouped_clipped_batch_ptr(_ptrs(tensors), torch_to_piquant_dtype(tensors[0].dtype), _ptrs(outs), torch_to_piquant_dtype(dtype), numels,
+                                           group_size, _ptrs(scales), _ptrs(zero_points), None if choices is None else _ptrs(choices), steps,
+                                           _ROUND_MODES[round_mode], _device_ptrs=True)
+    return (outs, scales, zero_points, choices) if return_choices else (outs, scales, zero_points)
+
+
 def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: torch.Tensor, *, dtype: torch.dtype, group_size: int,
                        reduce_op: str = 'set', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
                        quant_dtype: Optional[torch.dtype] = None, shape=None) -> torch.Tensor:

@@ -67,7 +67,12 @@ loop's own spread (max - min over its windows); --kernel-stats FILE (the kernel 
 rocprofv3 --kernel-trace --stats) adds the sums of the kernel times, judged with the same spread.  Writes profiles/grouped_rot_batch_bench.json;
 --rows all appends these rows to its table.
 
-    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce|rot_ef|rot_batch] [--windows 7] [--rotate-gb 3.3] [--out FILE] [--kernel-stats FILE]
+--rows clip: the per-group clip search (quantize_grouped_clipped: fp32 -> uint8 / uint4 / uint2 and bf16 -> uint4 / uint2 at 1, 5 and 9 candidates,
+G = 128; fp32 -> uint4 at G = 32 and 1024 with 9), each next to quantize_grouped of the same pair and group size in the same run -- the call that
+moves the same bytes.  Reports fused us, quantize_grouped us, their ratio and the marginal us per candidate.  Writes
+profiles/grouped_clip_bench.json.
+
+    python tools/grouped_bench.py [--rows all|reduce|ef|reduce_ef|ef_f32r|reduce_ef_f32r|requant|dequant_sum|rot|rot_reduce|rot_ef|rot_batch|clip] [--windows 7] [--rotate-gb 3.3] [--out FILE] [--kernel-stats FILE]
 """
 import argparse
 import json
@@ -1112,12 +1117,57 @@ def rot_batch_rows(ctx, dev, stream, args, G=128, world=8):
     return rows + [out["loop"], out["batched"]]
 
 
+def clip_rows(ctx, dev, stream, args):
+    """quantize_grouped_clipped at 1, 5 and 9 candidates against quantize_grouped: the same bytes, so the difference is arithmetic"""
+    rows = []
+    g = torch.Generator(device=dev)
+    g.manual_seed(11)
+    cases = [(f, q, 128, (1, 5, 9)) for f, q in (("f32", "uint8"), ("f32", "uint4"), ("f32", "uint2"), ("bf16", "uint4"), ("bf16", "uint2"))]
+    cases += [("f32", "uint4", 32, (9,)), ("f32", "uint4", 1024, (9,))]
+    for fname, qname, G, steps_list in cases:
+        fdt, tdt, esize = FLOAT[fname]
+        qdt, bits = QUANT[qname]
+        ng = pt.num_groups(NUMEL, G)
+        nq = qdt.packed_nbytes(NUMEL)
+        nbytes = NUMEL * esize + nq + 5 * ng                                    # x in; packed bytes and parameters out: the same for both calls
+        nbuf = max(3, int(args.rotate_gb * 1e9 / nbytes) + 1)
+        xs = [torch.empty(NUMEL, dtype=tdt, device=dev).normal_(generator=g) for _ in range(nbuf)]
+        outs = [torch.empty(nq, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        sc = [torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        zs = [torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        per_window = max(2 * nbuf, 32)
+        pair = f"{fname}->{qname}"
+
+        def plain(i):
+            ctx.quantize_grouped_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), False,
+                                     piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+        us_p, s_p = timed(plain, nbuf, args.windows, per_window, stream)
+        rows.append(row("quantize_grouped", pair, G, us_p, nbytes, s_p))
+        for steps in steps_list:
+            def clipped(i, steps=steps):
+                ctx.quantize_grouped_clipped_ptr(xs[i].data_ptr(), fdt, outs[i].data_ptr(), qdt, NUMEL, G, sc[i].data_ptr(), zs[i].data_ptr(), 0, steps,
+                                                 piquant.RoundMode.NEAREST, _device_ptrs=True)
+
+            us_c, s_c = timed(clipped, nbuf, args.windows, per_window, stream)
+            r = row(f"quantize_grouped_clipped steps={steps}", pair, G, us_c, nbytes, s_c)
+            r["steps"] = steps
+            r["quantize_grouped_us"] = round(us_p, 3)
+            r["over_quantize_grouped"] = round(us_c / us_p, 3)
+            r["marginal_us_per_candidate"] = round((us_c - us_p) / steps, 3) if steps > 1 else None
+            print(f"    clipped / quantize_grouped = {r['over_quantize_grouped']:.3f}, {r['marginal_us_per_candidate']} us per candidate", flush=True)
+            rows.append(r)
+        del xs, outs, sc, zs
+        torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
     ap.add_argument("--rows", choices=("all", "reduce", "ef", "reduce_ef", "ef_f32r", "reduce_ef_f32r", "requant", "dequant_sum", "rot", "rot_reduce", "rot_ef",
-                                       "rot_batch"), default="all")
+                                       "rot_batch", "clip"), default="all")
     ap.add_argument("--out", default=None)
     ap.add_argument("--kernel-stats", default=None, help="rot_batch rows: kernel statistics CSV of tools/grouped_rot_batch_workload.py under rocprofv3")
     args = ap.parse_args()
@@ -1127,7 +1177,7 @@ def main():
                                                    "reduce_ef_f32r": "grouped_reduce_ef_f32r_bench.json", "requant": "grouped_requant_bench.json",
                                                    "dequant_sum": "grouped_dequant_sum_bench.json", "rot": "grouped_rot_bench.json",
                                                    "rot_reduce": "grouped_rot_reduce_bench.json", "rot_ef": "grouped_rot_ef_bench.json",
-                                                   "rot_batch": "grouped_rot_batch_bench.json"}[args.rows])
+                                                   "rot_batch": "grouped_rot_batch_bench.json", "clip": "grouped_clip_bench.json"}[args.rows])
     assert torch.cuda.is_available(), "grouped_bench measures on the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
@@ -1159,6 +1209,8 @@ def main():
         rows = rot_ef_rows(ctx, dev, stream, args)
     if args.rows == "rot_batch":
         rows = rot_batch_rows(ctx, dev, stream, args)
+    if args.rows == "clip":
+        rows = clip_rows(ctx, dev, stream, args)
     for fname, (fdt, tdt, esize) in (FLOAT.items() if args.rows == "all" else ()):
         nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
         g = torch.Generator(device=dev)
