@@ -523,6 +523,54 @@ PIQUANT_EXPORT void piquant_hip_quantize_grouped_clipped_batch(piquant_context_t
                                                                size_t group_size, float* const* scales, uint8_t* const* zero_points,
                                                                uint8_t* const* choices, size_t count, int steps, piquant_round_mode_t mode);
 
+/* HISTOGRAM CLIP SEARCH for per-tensor parameters.  piquant_hip_compute_quant_params_device takes the step from the tensor's min and max; on a
+ * tensor of 10^6 .. 10^8 elements the extremes lie 5 sigma and more out, and a narrow wire spends most codes on empty range.
+ * piquant_hip_compute_quant_params_clipped_device judges `steps` (1 .. PIQUANT_HIP_CLIP_MAX_STEPS) ranges shrunk towards zero on a histogram of the
+ * tensor -- one more streaming pass, whatever the number of candidates -- and writes the record of the one with the smallest estimated squared error.
+ * The record is an ordinary record: piquant_hip_quantize_dp, piquant_hip_dequantize_dp and every wire take it as it is.
+ * The counts are integers: exact in any order, in any grid and across ranks (a sharded caller adds ONE SUM all-reduce of the counts to the scan's
+ * MIN all-reduce of the keys), so the whole search is reproducible bit for bit.
+ * THE DEFINITION.  x is float32, or bfloat16 widened exactly; qmax = 2^bits - 1 of the target type; B = PIQUANT_HIP_CLIP_BINS.
+ *   1. RANGE.  (lo, hi) is the scan's float32 minimum and maximum, NaNs ignored: the pair behind piquant_hip_compute_quant_params_device and
+ *      piquant_hip_minmax_keys.  If nothing was scanned, or not hi > lo, the counts stay zero, no candidate is evaluated, and the result is that
+ *      call's record with choice 0 -- decided on the device, the call stays stream-ordered.  steps == 1 searches nothing either: that call's record,
+ *      choice 0, no error evaluated (piquant_hip_compute_quant_params_clipped_device decides this on the host and forwards to that call).
+ *   2. COUNTS.  Only non-NaN elements are counted.  In float32, each operation rounded on its own: wf = hi - lo (may be +inf); inv = B / wf (may be
+ *      0 or +inf); t = (x - lo) * inv; bin = int(min(max(t, 0), B - 1)) with a NaN t giving 0 (the fmaxf(NaN, 0) = 0 rule: +-inf inputs and an
+ *      overflowing range are defined).  c[j], uint64, is the number of elements in bin j.
+ *   3. CANDIDATES.  r_k = 1 - k / 64 (exact), lo_k = fl32(lo * r_k), hi_k = fl32(hi * r_k), 0 <= k < steps.  Candidate k is evaluated iff k == 0 or
+ *      hi_k > lo_k; (s_k, z_k) is the ordinary epilogue on (lo_k, hi_k), 0 <= z_k <= qmax; candidate 0 is piquant_hip_compute_quant_params_device's
+ *      pair.  Its error, in binary64, every operation rounded once, nothing fused:  W = (double(hi) - double(lo)) / B;  m_j = double(lo) + (j + 0.5) * W;
+ *      u = floor(m_j / double(s_k) + 0.5) + z_k, clamped to [0, qmax], a NaN giving 0;  d = (u - z_k) * double(s_k);  e = m_j - d;
+ *      term_j = double(c_j) * (e * e), and exactly +0 where c_j == 0;  E_k = the sum of the B terms by the adjacent-pair tree (replace t by
+ *      t[2j] + t[2j+1] until one value is left).  An E_k that is NaN is stored as the one pattern 0x7ff8000000000000.
+ *   4. CHOICE.  best = 0; for k = 1 .. steps - 1 in order: if E_k < E_best then best = k.  Strict: a tie or a NaN keeps the smaller k.
+ * RESULT: the record {s_best, fl32(1 / s_best), z_best} and the choice.
+ * The search ESTIMATES the error: bin centres stand for the elements, and the rounding mode of the quantizing call plays no part.  The definition is
+ * the histogram's, not the round trip's.  r_k >= 1/32: an outlier beyond 32 x the bulk is out of reach, the bulk then shares a few bins.
+ *
+ * piquant_hip_clip_histogram: device_hist (uint64[PIQUANT_HIP_CLIP_BINS]) receives the counts of x against the range in device_keys (int32[2], as
+ *   piquant_hip_minmax_keys leaves them -- or as a MIN all-reduce over ranks does); init != 0 zeroes the counts first, several calls with init == 0
+ *   accumulate (shards, parts).  n == 0 with init == 0 does nothing.
+ * piquant_hip_quant_params_from_histogram: steps 3 and 4 on given keys and counts.  device_choice (int32) and device_errors (double[63]; entry k is
+ *   E_k, NaN where candidate k was not evaluated or k >= steps) may be NULL.
+ * piquant_hip_compute_quant_params_clipped_device: keys (init), histogram (init), search, on scratch of the context.
+ * x not aligned to 16 bytes is counted like the scan scans it (a few leading elements one by one; not even element-aligned: element by element);
+ * nothing outside the tensor is read.  Device (or pinned) buffers only.  Stream-ordered on the context's stream, no host synchronisation, no float
+ * atomics, no grid barrier.  The scratch is allocated by the context's first such call; from the second on a call allocates nothing and can be
+ * captured into a hipGraph.  A wrong dtype or steps outside [1, PIQUANT_HIP_CLIP_MAX_STEPS] aborts. */
+#define PIQUANT_HIP_CLIP_BINS 8192
+#define PIQUANT_HIP_CLIP_MAX_STEPS 63
+PIQUANT_EXPORT void piquant_hip_clip_histogram(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n, const int32_t* device_keys,
+                                               uint64_t* device_hist, int init);
+PIQUANT_EXPORT void piquant_hip_quant_params_from_histogram(piquant_context_t* ctx, const int32_t* device_keys, const uint64_t* device_hist,
+                                                            piquant_dtype_t target_quant_dtype, int steps, piquant_hip_params_t* device_params,
+                                                            int32_t* device_choice, double* device_errors);
+PIQUANT_EXPORT void piquant_hip_compute_quant_params_clipped_device(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n,
+                                                                    piquant_dtype_t target_quant_dtype, int steps,
+                                                                    piquant_hip_params_t* device_params, int32_t* device_choice,
+                                                                    double* device_errors);
+
 /* INDEPENDENT CALLS (opt-in, off by default).  Calls on a stream run one after the other: the dispatch packet of every kernel carries a barrier
  * bit, the next kernel starts when the previous one has drained, and the ~2 us in which a launch ramps up and drains move no bytes (9 % of a
  * 23 us quantize at numel 27 264 000, a third of a 5 us shard).  A caller that quantizes or dequantizes tensor after tensor -- the gradients of a

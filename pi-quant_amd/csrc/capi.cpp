@@ -11,18 +11,22 @@ using namespace pq;
 
 namespace pq {
 
-void scan(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n, const MinmaxAction& action) {
-    // scans of one context share one state buffer: they must not overlap, which stream order guarantees on one stream
+void order_scan_state(piquant_context_t* ctx) {
+    // launches on per-context state share its buffers: they must not overlap, which stream order guarantees on one stream
     // (a handle that went stale despite the rule "replace a stream before destroying it" gives an error here, not an abort: its work is over)
     if (ctx->scan_stream && ctx->scan_stream != ctx->stream && !stream_is_capturing(ctx->stream) && !stream_is_capturing(ctx->scan_stream) &&
         hipStreamSynchronize(ctx->scan_stream) != hipSuccess)
         (void)hipGetLastError();
-    if (ctx->scan_left_pending && !stream_is_capturing(ctx->stream)) {   // a scan on a stream the context has left since (context.cpp, leave_stream)
+    if (ctx->scan_left_pending && !stream_is_capturing(ctx->stream)) {   // such a launch on a stream the context has left since (context.cpp, leave_stream)
         if (hipStreamWaitEvent(ctx->stream, ctx->scan_left, 0) != hipSuccess) (void)hipGetLastError();
         ctx->scan_left_pending = false;
     }
     ctx->scan_stream = ctx->stream;
-    order_context_state(ctx);   // captured scans of one context on parallel branches of a graph become successors of each other
+    order_context_state(ctx);   // captured launches of one context on parallel branches of a graph become successors of each other
+}
+
+void scan(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n, const MinmaxAction& action) {
+    order_scan_state(ctx);
     if (n == 0) {
         launch_minmax_epilogue(ctx->d_state, action, false, ctx->stream);
         return;

@@ -296,6 +296,130 @@ void piquant_hip_reduce_quantize_dynamic(piquant_context_t* ctx, void* acc, piqu
     if (ctx->blocking) wait_stream(ctx);
 }
 
+}  // extern "C"
+
+// Scratch of the histogram clip search, one allocation made by the context's first such call: {keys int32[2], pad} | errors double[64] |
+// counts uint64[8192] | one uint32[8192] row per block of the histogram pass.  Like the scan state it belongs to the context, so a warmed-up
+// call allocates nothing and can be captured into a hipGraph; the first call cannot.
+namespace {
+
+struct ClipScratch {
+    int32_t* keys;
+    double* errors;
+    uint64_t* hist;
+    uint32_t* partials;
+};
+
+ClipScratch clip_scratch(piquant_context_t* ctx) {
+    constexpr size_t kKeys = 16, kErrors = 64 * sizeof(double), kHist = PIQUANT_HIP_CLIP_BINS * sizeof(uint64_t);
+    if (!ctx->d_clip) {
+        if (stream_is_capturing(ctx->stream))
+            panic("the context's first histogram clip search allocates its scratch and cannot be captured into a hipGraph: run the call once before capturing it");
+        PQ_HIP(hipMalloc(&ctx->d_clip, kKeys + kErrors + kHist + clip_partial_bytes(ctx->num_cu)));
+    }
+    char* base = static_cast<char*>(ctx->d_clip);
+    return {reinterpret_cast<int32_t*>(base), reinterpret_cast<double*>(base + kKeys), reinterpret_cast<uint64_t*>(base + kKeys + kErrors),
+            reinterpret_cast<uint32_t*>(base + kKeys + kErrors + kHist)};
+}
+
+void check_clip_input(const char* who, piquant_dtype_t dtype) {
+    if (dtype != PIQUANT_DTYPE_F32 && dtype != PIQUANT_DTYPE_BF16) panic("%s needs f32 or bf16 input, got %s", who, dtype_of(dtype).name);
+}
+
+void check_clip_target(piquant_dtype_t target_quant_dtype) {
+    if (!dtype_of(target_quant_dtype).quant) panic("type %s is not a quantization type", dtype_of(target_quant_dtype).name);
+}
+
+void check_clip_steps(const char* who, int steps) {
+    if (steps < 1 || steps > PIQUANT_HIP_CLIP_MAX_STEPS) panic("%s: %d steps, 1 to %d are possible", who, steps, PIQUANT_HIP_CLIP_MAX_STEPS);
+}
+
+// a caller's device (or pinned) buffer, classified as the context classifies the tensors (not at all once the caller has vouched for device pointers)
+void* clip_device_ptr(piquant_context_t* ctx, const char* who, const char* what, const void* p) {
+    if (!p) panic("%s: NULL %s", who, what);
+    const Resolved r = ctx->resolve_ptr(p);
+    if (r.pageable) panic("%s: the %s must live in device (or pinned) memory", who, what);
+    return r.dev;
+}
+
+void* clip_optional_ptr(piquant_context_t* ctx, const char* who, const char* what, const void* p) { return p ? clip_device_ptr(ctx, who, what, p) : nullptr; }
+
+}  // namespace
+
+extern "C" {
+
+void piquant_hip_clip_histogram(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n, const int32_t* device_keys, uint64_t* device_hist, int init) {
+    const char* who = "piquant_hip_clip_histogram";
+    if (!ctx) panic("%s: context is NULL", who);
+    check_clip_input(who, dtype);
+    if (n != 0 && !x) panic("%s: NULL input", who);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const int32_t* keys = static_cast<const int32_t*>(clip_device_ptr(ctx, who, "key buffer", device_keys));
+    uint64_t* hist = static_cast<uint64_t*>(clip_device_ptr(ctx, who, "histogram", device_hist));
+    const void* x_dev = n != 0 ? clip_device_ptr(ctx, who, "input", x) : nullptr;
+    const ClipScratch s = clip_scratch(ctx);
+    order_scan_state(ctx);   // the rows are the context's, as the scan state is
+    launch_clip_histogram(x_dev, dtype, static_cast<int64_t>(n), keys, s.partials, clip_partial_rows(ctx->num_cu), hist, init != 0, ctx->stream);
+}
+
+void piquant_hip_quant_params_from_histogram(piquant_context_t* ctx, const int32_t* device_keys, const uint64_t* device_hist, piquant_dtype_t target_quant_dtype,
+                                             int steps, piquant_hip_params_t* device_params, int32_t* device_choice, double* device_errors) {
+    const char* who = "piquant_hip_quant_params_from_histogram";
+    if (!ctx) panic("%s: context is NULL", who);
+    check_clip_target(target_quant_dtype);
+    check_clip_steps(who, steps);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const int32_t* keys = static_cast<const int32_t*>(clip_device_ptr(ctx, who, "key buffer", device_keys));
+    const uint64_t* hist = static_cast<const uint64_t*>(clip_device_ptr(ctx, who, "histogram", device_hist));
+    void* params = clip_device_ptr(ctx, who, "parameter record", device_params);
+    int32_t* choice = static_cast<int32_t*>(clip_optional_ptr(ctx, who, "choice", device_choice));
+    double* errors = static_cast<double*>(clip_optional_ptr(ctx, who, "error buffer", device_errors));
+    const ClipScratch s = clip_scratch(ctx);
+    order_scan_state(ctx);   // the candidates' errors pass through the context's scratch
+    launch_clip_search(keys, hist, dtype_of(target_quant_dtype).bits, steps, s.errors, params, choice, errors, ctx->stream);
+}
+
+void piquant_hip_compute_quant_params_clipped_device(piquant_context_t* ctx, const void* x, piquant_dtype_t dtype, size_t n, piquant_dtype_t target_quant_dtype,
+                                                     int steps, piquant_hip_params_t* device_params, int32_t* device_choice, double* device_errors) {
+    const char* who = "piquant_hip_compute_quant_params_clipped_device";
+    if (!ctx) panic("%s: context is NULL", who);
+    check_clip_input(who, dtype);
+    check_clip_target(target_quant_dtype);
+    check_clip_steps(who, steps);
+    if (n != 0 && !x) panic("%s: NULL input", who);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    void* params = clip_device_ptr(ctx, who, "parameter record", device_params);
+    int32_t* choice = static_cast<int32_t*>(clip_optional_ptr(ctx, who, "choice", device_choice));
+    double* errors = static_cast<double*>(clip_optional_ptr(ctx, who, "error buffer", device_errors));
+    const void* x_dev = n != 0 ? clip_device_ptr(ctx, who, "input", x) : nullptr;
+    const int bits = dtype_of(target_quant_dtype).bits;
+    // the scan on the pointer resolved above; n == 0: the fold of the armed state, the identities (max < min)
+    auto scan_resolved = [&](const MinmaxAction& a) {
+        if (n == 0) launch_minmax_epilogue(ctx->d_state, a, false, ctx->stream);
+        else launch_minmax(x_dev, dtype, static_cast<int64_t>(n), ctx->d_state, a, ctx->stream, ctx->num_cu);
+    };
+    MinmaxAction a;
+    if (steps == 1) {   // nothing to search: the plain call's launch, then choice 0 and no error for whoever asked
+        order_scan_state(ctx);
+        a.action = MM_PARAMS;
+        a.bits = bits;
+        a.dst = params;
+        scan_resolved(a);
+        launch_clip_unsearched(choice, errors, ctx->stream);
+        return;
+    }
+    const ClipScratch s = clip_scratch(ctx);
+    order_scan_state(ctx);   // once for the three steps: they follow each other on the stream
+    a.action = MM_KEYS_SET;
+    a.dst = s.keys;
+    scan_resolved(a);   // an empty tensor leaves max < min: the histogram stays zero and the search writes the degenerate record
+    launch_clip_histogram(x_dev, dtype, static_cast<int64_t>(n), s.keys, s.partials, clip_partial_rows(ctx->num_cu), s.hist, true, ctx->stream);
+    launch_clip_search(s.keys, s.hist, bits, steps, s.errors, params, choice, errors, ctx->stream);
+}
+
 void piquant_hip_signal_flags(piquant_context_t* ctx, uint32_t* const* flags, size_t count, uint32_t value) {
     if (!ctx) panic("piquant_hip_signal_flags: context is NULL");
     if (count == 0) return;

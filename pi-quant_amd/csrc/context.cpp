@@ -424,6 +424,7 @@ void piquant_context_destroy(piquant_context_t* ctx) {
             if (p) (void)hipFree(p);
         if (ctx->d_state) (void)hipFree(ctx->d_state);
         if (ctx->d_fused) (void)hipFree(ctx->d_fused);
+        if (ctx->d_clip) (void)hipFree(ctx->d_clip);
         if (ctx->h_keys) (void)hipHostFree(ctx->h_keys);
         if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
         if (ctx->done) (void)hipHostFree(ctx->done);

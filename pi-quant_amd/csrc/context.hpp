@@ -82,6 +82,7 @@ struct piquant_context_t {
     hipStream_t capture_stream = nullptr;  // capturing stream that last used the scan / barrier state (order_context_state)
     hipEvent_t capture_edge = nullptr;     // event that turns "used by another capturing stream" into a graph edge
     void* d_fused = nullptr;               // FusedState of the one-launch params + quantize kernel (fused_kernels.hpp)
+    void* d_clip = nullptr;                // scratch of the histogram clip search (keys, errors, counts, per-block rows), allocated by its first call
     bool fusion = true;                    // piquant_hip_set_fusion
     uint32_t barrier_timeout_us = 0;       // piquant_hip_set_barrier_timeout_us (0 = the kernel's default, 1 ms)
     int wait_mode = 0;                     // how a blocking call waits (WAIT_*, piquant_hip_set_blocking_wait)
@@ -237,6 +238,11 @@ void fill_round_mode(piquant_context_t* ctx, QuantLaunch& q, piquant_round_mode_
 // argument checks shared by the additive entry points: the quantize side (types and round mode) and the dequantize side (types and reduce op)
 void check_dynamic_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_round_mode_t mode);
 void check_dequant_types(piquant_dtype_t dtype_in, piquant_dtype_t dtype_out, piquant_reduce_op_t op);
+
+// In front of every launch that uses the context's scan state or the scratch of the histogram clip search (both one buffer per context): waits for
+// such launches still in flight on a stream the context has left or is leaving (an event recorded by leave_stream, or a synchronise), remembers the
+// stream, and orders captured launches (order_context_state).  scan() calls it itself.  Caller holds ctx->mu and the device guard.
+void order_scan_state(piquant_context_t* ctx);
 
 // Min/max scan of x with `action` as its epilogue (launch.hpp): one launch for device input; staged chunks plus a fold launch
 // for pageable host input; for an empty input the fold of the armed state (the identities, reference

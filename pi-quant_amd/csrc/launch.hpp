@@ -242,6 +242,19 @@ void launch_quantize_grouped_rotated_ef_batch(const GroupedEfBatchLaunch& b, uin
 // batch of one launches the single-tensor kernel); the guarded launch runs one tensor of any element alignment, the same bytes.
 void launch_quantize_grouped_clipped_batch(const GroupedQuantBatchLaunch& b, int steps, hipStream_t stream);
 void launch_quantize_grouped_clipped_guarded(const GroupedQuantLaunch& q, int steps, hipStream_t stream, int num_cu);
+// Histogram clip search for per-tensor parameters (clip_params_kernels.hpp; kernels_clip_params.hip).  `keys` is the scan's device {key(min), key(-max)}.
+// launch_clip_histogram: hist (uint64[8192], device) = or += the counts of `in` against the keys' range -- one streaming launch that leaves one
+// uint32[8192] row per block in `partials` (clip_partial_bytes(num_cu) of device scratch, clip_partial_rows(num_cu) rows) and a fold launch; numel == 0
+// zeroes (init) or does nothing.  launch_clip_search: steps blocks judge the candidates from `hist` into errors_scratch (double[63], device), one wave
+// chooses and writes the 16-byte record and, where not NULL, the choice and the 63 errors (NaN: not evaluated).  steps == 1 launches the wave alone.
+// launch_clip_unsearched: choice 0 and 63 NaNs, what a call that forwards to the plain scan still owes its caller.
+size_t clip_partial_rows(int num_cu);
+size_t clip_partial_bytes(int num_cu);
+void launch_clip_histogram(const void* in, int dt_in, int64_t numel, const int32_t* keys, uint32_t* partials, size_t partial_rows, uint64_t* hist, bool init,
+                           hipStream_t stream);
+void launch_clip_search(const int32_t* keys, const uint64_t* hist, int bits, int steps, double* errors_scratch, void* device_param_record, int32_t* device_choice,
+                        double* device_errors, hipStream_t stream);
+void launch_clip_unsearched(int32_t* device_choice, double* device_errors, hipStream_t stream);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

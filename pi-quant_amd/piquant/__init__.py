@@ -271,6 +271,30 @@ class Context:
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_compute_quant_params_device(self._ctx, ptr, dtype.value, numel, target_quant_dtype.value, params_ptr)
 
+    # histogram clip search for per-tensor parameters (include/piquant_hip.h, "HISTOGRAM CLIP SEARCH"); device (or pinned) pointers only
+    def clip_histogram_ptr(self, ptr: int, dtype: DataType, numel: int, keys_ptr: int, hist_ptr: int, init: bool = True, _device_ptrs: bool = False) -> None:
+        """uint64[8192] counts at ``hist_ptr`` (zeroed first with ``init``, accumulated otherwise) of the tensor against the range in the int32[2]
+        keys at ``keys_ptr`` (``minmax_keys_ptr``, possibly MIN-reduced over ranks)."""
+        assert dtype.is_dequantized and keys_ptr != 0 and hist_ptr != 0
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_clip_histogram(self._ctx, ptr or None, dtype.value, numel, keys_ptr, hist_ptr, 1 if init else 0)
+
+    def quant_params_from_histogram_ptr(self, keys_ptr: int, hist_ptr: int, target_quant_dtype: DataType, steps: int, params_ptr: int, choice_ptr: int = 0,
+                                        errors_ptr: int = 0) -> None:
+        """The search on given keys and counts: the 16-byte record at ``params_ptr``, the int32 choice and the double[63] errors where wanted."""
+        assert target_quant_dtype.is_quantized and keys_ptr != 0 and hist_ptr != 0 and params_ptr != 0
+        C.piquant_hip_quant_params_from_histogram(self._ctx, keys_ptr, hist_ptr, target_quant_dtype.value, steps, params_ptr, choice_ptr or None,
+                                                  errors_ptr or None)
+
+    def compute_quant_params_clipped_device_ptr(self, ptr: int, dtype: DataType, numel: int, target_quant_dtype: DataType, steps: int, params_ptr: int,
+                                                choice_ptr: int = 0, errors_ptr: int = 0, _device_ptrs: bool = False) -> None:
+        """``compute_quant_params_device_ptr`` with the histogram clip search over ``steps`` (1 to 63) candidate ranges: keys, histogram and
+        search on the context's scratch, stream-ordered."""
+        assert dtype.is_dequantized and target_quant_dtype.is_quantized and params_ptr != 0
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_compute_quant_params_clipped_device(self._ctx, ptr or None, dtype.value, numel, target_quant_dtype.value, steps, params_ptr,
+                                                          choice_ptr or None, errors_ptr or None)
+
     def quantize_dp_ptr(self, ptr_in: int, dtype_in: DataType, ptr_out: int, dtype_out: DataType, numel: int, params_ptr: int,
                         round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         assert dtype_in.is_dequantized and dtype_out.is_quantized and params_ptr != 0

@@ -40,6 +40,9 @@ _DECLS = [
     ('piquant_hip_dequantize_uniform', None, [_vp, _vp, _int, _vp, _int, _sz, _f32, _i64, _int]),
     ('piquant_hip_quantize_dequantize', None, [_vp, _vp, _int, _vp, _int, _sz, _f32, _i64, _int, _int]),
     ('piquant_hip_compute_quant_params_device', None, [_vp, _vp, _int, _sz, _int, _vp]),
+    ('piquant_hip_clip_histogram', None, [_vp, _vp, _int, _sz, _vp, _vp, _int]),
+    ('piquant_hip_quant_params_from_histogram', None, [_vp, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    ('piquant_hip_compute_quant_params_clipped_device', None, [_vp, _vp, _int, _sz, _int, _int, _vp, _vp, _vp]),
     ('piquant_hip_quantize_dp', None, [_vp, _vp, _int, _vp, _int, _sz, _vp, _int]),
     ('piquant_hip_quantize_dynamic', None, [_vp, _vp, _int, _vp, _int, _sz, _vp, _int]),
     ('piquant_hip_set_fusion', None, [_vp, _int]),

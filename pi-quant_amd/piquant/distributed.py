@@ -259,6 +259,33 @@ def compute_quant_params(
     return quant_params_from_minmax(r_min, r_max, torch_to_piquant_dtype(dtype))
 
 
+def compute_quant_params_clipped(
+    local_shard: torch.Tensor,
+    *,
+    dtype: torch.dtype,
+    steps: int = 63,
+    group: Optional[dist.ProcessGroup] = None,
+    ctx: Optional[Context] = None,
+) -> Tuple[float, int]:
+    """``piquant.torch.compute_quant_params_clipped`` of the tensor whose shards are spread over ``group``: the local keys, the 8-byte
+    ``all_reduce(MIN)``, the local histogram against the GLOBAL keys, one ``all_reduce(SUM)`` of the int64[8192] counts, the search.  Counts are
+    integers, so the result is identical on every rank and identical to the single-GPU call on the whole tensor.  Collective transport only."""
+    from .torch import _check_clip_params_steps, _check_float_input, clip_histogram, params_to_host, quant_params_from_histogram
+
+    if dtype not in _QUANT_TYPES:
+        raise ValueError(f'{dtype} is not a quantized dtype')
+    _check_clip_params_steps(steps)
+    _check_float_input(local_shard, 'local_shard (the tensor)')   # before the first launch and the first collective: a bad rank enters neither
+    keys = local_minmax_keys(local_shard, ctx)
+    world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    if world > 1:
+        dist.all_reduce(keys, op=dist.ReduceOp.MIN, group=group)
+    hist = clip_histogram(local_shard, keys, ctx=ctx)
+    if world > 1:
+        dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=group)
+    return params_to_host(quant_params_from_histogram(keys, hist, dtype=dtype, steps=steps, ctx=ctx))
+
+
 def _device_identity(index: int) -> str:
     props = torch.cuda.get_device_properties(index)
     uuid = getattr(props, 'uuid', None)

@@ -433,6 +433,93 @@ def compute_quant_params_device(tensor: torch.Tensor, *, dtype: torch.dtype, ctx
     return out
 
 
+# ---- histogram clip search for per-tensor parameters (include/piquant_hip.h, "HISTOGRAM CLIP SEARCH") ----------------------------------------
+CLIP_BINS = 8192            # PIQUANT_HIP_CLIP_BINS
+CLIP_PARAMS_STEPS_MAX = 63  # candidate ranges of the per-tensor search: r_k = 1 - k / 64, k < steps
+
+
+def _check_clip_params_steps(steps) -> None:
+    _require(isinstance(steps, int) and not isinstance(steps, bool) and 1 <= steps <= CLIP_PARAMS_STEPS_MAX,
+             f'steps must be an int in [1, {CLIP_PARAMS_STEPS_MAX}], got {steps!r}')
+
+
+def _check_clip_keys(keys, device=None) -> None:
+    _require(isinstance(keys, torch.Tensor) and keys.is_cuda and keys.dtype == torch.int32 and keys.dim() == 1 and keys.numel() == 2 and keys.is_contiguous(),
+             'keys must be a contiguous int32[2] ROCm device tensor ({key(min), key(-max)}, local_minmax_keys)')
+    _require(device is None or keys.device == device, f'keys must live on {device}')
+
+
+def _check_clip_hist(hist, device: torch.device, what: str) -> None:
+    _require(isinstance(hist, torch.Tensor) and hist.dtype == torch.int64 and hist.dim() == 1 and hist.numel() == CLIP_BINS and hist.is_contiguous(),
+             f'{what} must be a contiguous 1-D int64 tensor of {CLIP_BINS} elements')
+    _require(hist.device == device, f'{what} must live on {device}')
+
+
+def clip_histogram(tensor: torch.Tensor, keys: torch.Tensor, *, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                   ctx: Optional[Context] = None) -> torch.Tensor:
+    """int64[8192] counts of ``tensor`` against the range in ``keys`` (int32[2], ``piquant.distributed.local_minmax_keys`` -- of this tensor, or
+    MIN-reduced over the shards of a larger one).  ``accumulate=True`` adds to ``out`` instead of overwriting it.  One streaming launch plus a
+    fold, asynchronous on the current stream."""
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    _check_float_input(tensor)
+    _check_clip_keys(keys, tensor.device)
+    _require(out is not None or not accumulate, 'accumulate=True needs out= (the counts to add to)')
+    if out is None:
+        out = torch.empty(CLIP_BINS, dtype=torch.int64, device=tensor.device)
+    _check_clip_hist(out, tensor.device, 'out')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    ctx = _ctx_for(tensor, ctx)
+    ctx.clip_histogram_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), tensor.numel(), keys.data_ptr(), out.data_ptr(), init=not accumulate,
+                           _device_ptrs=True)
+    return out
+
+
+def quant_params_from_histogram(keys: torch.Tensor, hist: torch.Tensor, *, dtype: torch.dtype, steps: int = 63, ctx: Optional[Context] = None,
+                                return_choice: bool = False, return_errors: bool = False):
+    """The search on given keys and counts: the 16-byte parameter record, then -- where asked for -- the int32[1] choice and the float64[63] errors
+    (NaN: candidate not evaluated), all on the device of ``keys``."""
+    _check_modes(quant_dtype=dtype)
+    _check_clip_params_steps(steps)
+    _check_clip_keys(keys)
+    _check_clip_hist(hist, keys.device, 'hist')
+    params = torch.empty(PARAMS_NBYTES, dtype=torch.uint8, device=keys.device)
+    choice = torch.empty(1, dtype=torch.int32, device=keys.device) if return_choice else None
+    errors = torch.empty(CLIP_PARAMS_STEPS_MAX, dtype=torch.float64, device=keys.device) if return_errors else None
+    ctx = _ctx_for(keys, ctx)
+    ctx.quant_params_from_histogram_ptr(keys.data_ptr(), hist.data_ptr(), torch_to_piquant_dtype(dtype), steps, params.data_ptr(),
+                                        0 if choice is None else choice.data_ptr(), 0 if errors is None else errors.data_ptr())
+    extra = tuple(t for t in (choice, errors) if t is not None)
+    return (params,) + extra if extra else params
+
+
+def compute_quant_params_clipped_device(tensor: torch.Tensor, *, dtype: torch.dtype, steps: int = 63, ctx: Optional[Context] = None,
+                                        out: Optional[torch.Tensor] = None, return_choice: bool = False):
+    """``compute_quant_params_device`` with a search for the clipping range: ``steps`` ranges -- min and max both shrunk towards zero by
+    ``1 - k / 64``, ``k < steps`` -- are judged on an 8192-bin histogram of the tensor, and the record of the one with the smallest estimated squared
+    error is returned (the 16-byte uint8 device tensor ``quantize_dp`` / ``dequantize_dynamic`` take); with ``return_choice=True`` also the int32[1]
+    device tensor of the chosen ``k``.  ``steps=1``, a constant, an empty and an all-NaN tensor give ``compute_quant_params_device``'s record.
+    Asynchronous on the current stream: scan, histogram pass, search."""
+    _check_modes(quant_dtype=dtype)
+    _check_clip_params_steps(steps)
+    _check_float_input(tensor)
+    if out is None:
+        out = torch.empty(PARAMS_NBYTES, dtype=torch.uint8, device=tensor.device)
+    _check_params(out, tensor.device, 'out')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    choice = torch.empty(1, dtype=torch.int32, device=tensor.device) if return_choice else None
+    ctx = _ctx_for(tensor, ctx)
+    ctx.compute_quant_params_clipped_device_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), tensor.numel(), torch_to_piquant_dtype(dtype), steps,
+                                                out.data_ptr(), 0 if choice is None else choice.data_ptr(), _device_ptrs=True)
+    return (out, choice) if return_choice else out
+
+
+def compute_quant_params_clipped(tensor: torch.Tensor, *, dtype: torch.dtype, steps: int = 63, ctx: Optional[Context] = None) -> Tuple[float, int]:
+    """(scale, zero_point) of ``compute_quant_params_clipped_device`` on the host (synchronises)."""
+    return params_to_host(compute_quant_params_clipped_device(tensor, dtype=dtype, steps=steps, ctx=ctx))
+
+
 def quantize_dynamic(tensor: torch.Tensor, *, dtype: torch.dtype, round_mode: str = 'nearest', ctx: Optional[Context] = None,
                      out: Optional[torch.Tensor] = None, params: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``compute_quant_params`` + ``quantize`` in one asynchronous call, parameters computed and kept on the device.  Returns
