@@ -699,6 +699,39 @@ PIQUANT_EXPORT void piquant_hip_exchange_minmax_keys(piquant_context_t* ctx, con
  * the peer mesh of that kind as poisoned: its next use is refused until piquant.distributed.release_peer_meshes() has let it be rebuilt. */
 PIQUANT_EXPORT int piquant_hip_peer_timeout(piquant_context_t* ctx, uint32_t* out_rank, uint32_t* out_expected, uint32_t* out_seen);
 
+/* OCP microscaling (MX) block formats: 32 elements of FP4 E2M1 or FP8 E4M3 share one power-of-two scale byte (E8M0).  The formats gfx950
+ * converts in hardware and its scaled MFMA instructions consume; the bytes view as torch.float4_e2m1fn_x2 / float8_e4m3fn / float8_e8m0fnu.
+ * Blocks and storage: the block size is 32, fixed; nblocks = ceil(numel / 32), the last block possibly ragged.  Three flat arrays, caller-owned,
+ * not aliased:
+ *   codes, FP4:  byte i = code[2i] | code[2i + 1] << 4, ceil(numel / 2) bytes (the nibble order of UINT4 here); missing high-nibble bits of a
+ *                ragged end are 0.  codes, FP8: one byte per element.
+ *   scales:      uint8[nblocks], linear.  Byte s means 2^(s - 127); 0xFF means NaN.
+ *   E2M1: values +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, emax = 2, no NaN, no infinity.  E4M3 (the "fn" variant): emax = 8, largest finite value 448,
+ *   subnormals down to 2^-9, 0x7F and 0xFF are NaN, no infinity.
+ * piquant_hip_quantize_mx (nearest only), block b with elements x_i widened exactly to float32:
+ *   1. amax = the largest |x_i| over the elements that are not NaN (infinities take part); 0 when there is none.
+ *   2. E = max(exponent field of amax, 1): a zero or denormal amax counts as exponent -126, an infinite one gives E = 255.
+ *   3. s = max(E - emax, 0), never 0xFF; scales[b] = s.
+ *   4. v_i = x_i * 2^(127 - s) as a real number (a power-of-two scaling: exact).
+ *   5. code_i = the element-format value nearest to v_i, ties to the even code, saturating to the largest finite magnitude (+-6, +-448), which
+ *      an infinite x_i gives too.
+ *   6. The sign bit is x_i's: -0 and a negative value that rounds to zero give the negative-zero code.
+ *   7. A NaN x_i gives a NaN code in E4M3 (either NaN byte: payload and sign of a NaN are outside the contract) and code 0x0 in E2M1.
+ *   By 2 and 3 amax lands in [2^emax, 2^(emax + 1)) of the scaled domain, whose upper part -- (6, 8), (448, 512) -- saturates: the OCP rule, kept;
+ *   the scale is not rounded up.
+ * piquant_hip_dequantize_mx: d_i = value(code_i) * 2^(s - 127) rounded to float32 (exact whenever representable; +-inf past the top); s = 0xFF or
+ *   a NaN code gives NaN.  SET stores d_i (float32) or RNE_bf16(d_i); ADD stores fl32(fl32(out_i) + d_i), for bfloat16 then rounded once to
+ *   bfloat16 -- the rule of the grouped dequantize ADD.
+ * The hardware conversions are the hot path, not the definition: the kernels add what makes them agree with it (mx_kernels.hpp).  ONE launch each;
+ * quantize reads its input once (no scan, no atomics, no barrier).  Buffers 16-byte aligned take the streaming kernels, anything else (the float
+ * side aligned to its element) guarded kernels that write the same bytes.  Device (or pinned) buffers only; stream-ordered on the context's stream,
+ * no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op. */
+typedef enum { PIQUANT_HIP_MX_FP4_E2M1 = 0, PIQUANT_HIP_MX_FP8_E4M3 = 1 } piquant_hip_mx_format_t;
+PIQUANT_EXPORT void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
+                                            piquant_hip_mx_format_t fmt);
+PIQUANT_EXPORT void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out,
+                                              size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op);
+
 /* Host helpers: key <-> float, and the (min,max) -> (scale, zero_point) epilogue in double precision
  * (reference src/piquant.cpp:213-220, 245-258).  keys[0] encodes min, keys[1] encodes -max. */
 PIQUANT_EXPORT void piquant_hip_decode_minmax_keys(const int32_t keys[2], float* out_min, float* out_max);

@@ -305,6 +305,53 @@ void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piqu
     if (ctx->blocking) wait_stream(ctx);
 }
 
+// The MX block formats (mx_kernels.hpp): fixed blocks of 32 under one E8M0 scale byte instead of groups with (scale, zero point); the same checks,
+// scopes and buffer rules as the two entries above.
+static_assert(PIQUANT_HIP_MX_FP4_E2M1 == MX_FP4_E2M1 && PIQUANT_HIP_MX_FP8_E4M3 == MX_FP8_E4M3, "piquant_hip_mx_format_t and the kernels' format codes");
+
+void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
+                             piquant_hip_mx_format_t fmt) {
+    const Where w {"piquant_hip_quantize_mx"};
+    if (!ctx) bad(w, "context is NULL");
+    if (dtype_in != PIQUANT_DTYPE_F32 && dtype_in != PIQUANT_DTYPE_BF16) bad(w, "the input must be float32 or bfloat16");
+    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
+    if (numel == 0) return;
+    if (!in || !codes || !scales) bad(w, "NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const MxQuantLaunch q {device_ptr(w, ctx->resolve_ptr(in)), device_ptr(w, ctx->resolve_ptr(codes)), static_cast<uint8_t*>(device_ptr(w, resolve(scales))),
+                           static_cast<int64_t>(numel), dtype_in, fmt};
+    if (reinterpret_cast<uintptr_t>(q.in) % (dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "in is not aligned to its element size");
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx);
+        launch_quantize_mx(q, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out, size_t numel,
+                               piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
+    const Where w {"piquant_hip_dequantize_mx"};
+    if (!ctx) bad(w, "context is NULL");
+    if (dtype_out != PIQUANT_DTYPE_F32 && dtype_out != PIQUANT_DTYPE_BF16) bad(w, "the output must be float32 or bfloat16");
+    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) bad(w, "the reduce op must be SET or ADD");
+    if (numel == 0) return;
+    if (!codes || !scales || !out) bad(w, "NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    const MxDequantLaunch d {device_ptr(w, ctx->resolve_ptr(codes)), static_cast<const uint8_t*>(device_ptr(w, resolve(scales))),
+                             device_ptr(w, ctx->resolve_ptr(out)), static_cast<int64_t>(numel), dtype_out, fmt, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET};
+    if (reinterpret_cast<uintptr_t>(d.out) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the scale bytes are written by whatever was enqueued just before
+        launch_dequantize_mx(d, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
 // The three rotated calls (grouped_rot_kernels.hpp): the two entries above with the rotation's seed, and the stand-alone transform.  In and out
 // 16-byte aligned: the streaming kernels; anything else element-aligned: the guarded ones, the same bytes.
 void piquant_hip_hadamard_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype, void* out, size_t numel, size_t group_size,

@@ -255,6 +255,29 @@ void launch_clip_histogram(const void* in, int dt_in, int64_t numel, const int32
 void launch_clip_search(const int32_t* keys, const uint64_t* hist, int bits, int steps, double* errors_scratch, void* device_param_record, int32_t* device_choice,
                         double* device_errors, hipStream_t stream);
 void launch_clip_unsearched(int32_t* device_choice, double* device_errors, hipStream_t stream);
+// The MX block formats (mx_kernels.hpp; kernels_mx.hip): 32 elements of FP4 E2M1 / FP8 E4M3 (fmt: MX_FP4_E2M1 = 0, MX_FP8_E4M3 = 1, the values of
+// piquant_hip_mx_format_t) under one E8M0 scale byte.  ONE launch each.  Every buffer 16-byte aligned: the streaming kernels; anything else (the
+// float side aligned to its element): the guarded ones, the same bytes.
+enum : int { MX_FP4_E2M1 = 0, MX_FP8_E4M3 = 1 };
+struct MxQuantLaunch {
+    const void* in;        // numel elements of dt_in
+    void* codes;           // ceil(numel * bits / 8) bytes
+    uint8_t* scales;       // uint8[ceil(numel / 32)]
+    int64_t numel;
+    int dt_in;             // DT_F32 / DT_BF16
+    int fmt;
+};
+struct MxDequantLaunch {
+    const void* codes;
+    const uint8_t* scales;
+    void* out;             // numel elements of dt_out
+    int64_t numel;
+    int dt_out;            // DT_F32 / DT_BF16
+    int fmt;
+    int op;                // OP_SET / OP_ADD
+};
+void launch_quantize_mx(const MxQuantLaunch& q, hipStream_t stream, int num_cu);
+void launch_dequantize_mx(const MxDequantLaunch& d, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -472,6 +472,20 @@ class Context:
         C.piquant_hip_dequantize_grouped(self._ctx, ptr_in, dtype_in.value, ptr_out, dtype_out.value, numel, group_size, scales_ptr, zero_points_ptr,
                                          reduce_op.value)
 
+    def quantize_mx_ptr(self, ptr_in: int, dtype_in: DataType, codes_ptr: int, scales_ptr: int, numel: int, fmt: int, _device_ptrs: bool = False) -> None:
+        """MX block quantize (``piquant_hip_quantize_mx``): ``fmt`` 0 = FP4 E2M1 (``ceil(numel / 2)`` code bytes), 1 = FP8 E4M3 (``numel``), one
+        E8M0 scale byte per 32 elements in ``scales_ptr``."""
+        assert dtype_in.is_dequantized and fmt in (0, 1)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx(self._ctx, ptr_in, dtype_in.value, codes_ptr, scales_ptr, numel, fmt)
+
+    def dequantize_mx_ptr(self, codes_ptr: int, scales_ptr: int, ptr_out: int, dtype_out: DataType, numel: int, fmt: int, reduce_op: ReduceOp,
+                          _device_ptrs: bool = False) -> None:
+        """MX block dequantize (``piquant_hip_dequantize_mx``), the buffers of ``quantize_mx_ptr``."""
+        assert dtype_out.is_dequantized and fmt in (0, 1)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_mx(self._ctx, codes_ptr, scales_ptr, ptr_out, dtype_out.value, numel, fmt, reduce_op.value)
+
     def quantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
                                    zero_points_ptrs, params_given: bool, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         """``quantize_grouped_ptr`` for several independent tensors (own parameter arrays each), up to 16 per kernel launch

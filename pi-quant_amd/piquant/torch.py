@@ -719,6 +719,76 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
     return out
 
 
+# ---- MX block formats: 32 elements of FP4 E2M1 / FP8 E4M3 under one power-of-two scale byte ------------------------------------------------
+MX_BLOCK = 32
+MX_FORMATS: dict[str, int] = {'fp4_e2m1': 0, 'fp8_e4m3': 1}   # piquant_hip_mx_format_t
+
+
+def mx_nbytes(numel: int, format: str) -> Tuple[int, int]:
+    """(code bytes, scale bytes) of ``numel`` elements in an MX format."""
+    return ((int(numel) + 1) // 2 if MX_FORMATS[format] == 0 else int(numel)), (int(numel) + MX_BLOCK - 1) // MX_BLOCK
+
+
+def _check_mx_format(format) -> None:
+    _require(isinstance(format, str) and format in MX_FORMATS, f'format must be one of {sorted(MX_FORMATS)}, got {format!r}')
+
+
+def _check_mx_bytes(t, nbytes: int, what: str) -> None:
+    _require(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 1 and t.numel() == nbytes and t.is_contiguous(),
+             f'{what} must be a contiguous 1-D uint8 tensor of {nbytes} bytes')
+
+
+def quantize_mx(tensor: torch.Tensor, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
+                out_scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """OCP microscaling quantization (``include/piquant_hip.h``, piquant_hip_quantize_mx): the flattened tensor is cut into blocks of 32 elements
+    (the last may be ragged), each stored as FP4 E2M1 (``'fp4_e2m1'``) or FP8 E4M3 (``'fp8_e4m3'``) codes under one power-of-two scale byte.
+    Nearest rounding, ties to even, saturating.  Returns (codes, scales), flat uint8 tensors on the tensor's device: ``ceil(numel / 2)`` (FP4, even
+    index in the low nibble) or ``numel`` (FP8) code bytes and ``ceil(numel / 32)`` scale bytes.  They ``.view()`` as
+    ``torch.float4_e2m1fn_x2`` / ``torch.float8_e4m3fn`` and ``torch.float8_e8m0fnu``.  One asynchronous launch on the current stream."""
+    _check_mx_format(format)
+    _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
+    ncodes, nscales = mx_nbytes(tensor.numel(), format)
+    if out is not None:
+        _check_mx_bytes(out, ncodes, 'out')
+    if out_scales is not None:
+        _check_mx_bytes(out_scales, nscales, 'out_scales')
+    _check_float_input(tensor)
+    for name, t in (('out', out), ('out_scales', out_scales)):
+        _require(t is None or t.device == tensor.device, f'{name} must live on {tensor.device}')
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    codes = torch.empty(ncodes, dtype=torch.uint8, device=tensor.device) if out is None else out
+    scales = torch.empty(nscales, dtype=torch.uint8, device=tensor.device) if out_scales is None else out_scales
+    ctx = _ctx_for(tensor, ctx)
+    ctx.quantize_mx_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), codes.data_ptr(), scales.data_ptr(), tensor.numel(), MX_FORMATS[format],
+                        _device_ptrs=True)
+    return codes, scales
+
+
+def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor, *, format: str, dtype: torch.dtype, shape=None, reduce_op: str = 'set',
+                  ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Inverse of ``quantize_mx``: element i of the result (``reduce_op='set'``) or of ``out`` (``'add'``) is ``value(code_i) * 2^(scales[i // 32] -
+    127)``; scale byte 0xFF and the FP8 NaN codes give NaN.  ``shape`` is the logical shape (``out``'s, or flat over every code, by default); its
+    element count decides how many codes are read -- an FP4 buffer alone cannot tell an odd count from the next even one."""
+    _check_mx_format(format)
+    _check_modes(float_dtype=dtype, reduce_op=reduce_op)
+    _require(isinstance(codes, torch.Tensor) and codes.dtype == torch.uint8 and codes.dim() == 1 and codes.is_contiguous(),
+             'codes must be a contiguous 1-D uint8 tensor')
+    if shape is None:
+        shape = out.shape if isinstance(out, torch.Tensor) else (codes.numel() * (2 if MX_FORMATS[format] == 0 else 1),)
+    numel = _numel_of(shape)
+    ncodes, nscales = mx_nbytes(numel, format)
+    _require(codes.numel() == ncodes, f'codes holds {codes.numel()} bytes, {numel} {format} elements are {ncodes}')
+    _check_mx_bytes(scales, nscales, 'scales')
+    _require(codes.is_cuda, 'dequantize_mx needs a ROCm device tensor')
+    _require(scales.device == codes.device, f'scales must live on {codes.device}')
+    out = _float_out(out, reduce_op, dtype, shape, numel, codes.device)
+    ctx = _ctx_for(codes, ctx)
+    ctx.dequantize_mx_ptr(codes.data_ptr(), scales.data_ptr(), out.data_ptr(), torch_to_piquant_dtype(out.dtype), numel, MX_FORMATS[format],
+                          _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return out
+
+
 def _check_seed(seed) -> int:
     """The rotation's seed: any Python int, taken modulo 2^64 (``_NA``: the call was made without one)."""
     _require(seed is not _NA, 'seed= is required: the rotation is defined by it, and the inverse needs the same one')
