@@ -732,6 +732,33 @@ PIQUANT_EXPORT void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* 
 PIQUANT_EXPORT void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out,
                                               size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op);
 
+/* The MX wire: the four calls that make a quantized collective over MX records a handful of launches.  Each is DEFINED as a composition of the two
+ * calls above (nearest only, like them); `fmt` is one format for the terms and the result; term i is (codes[i], scales[i]) of `numel` elements.
+ * piquant_hip_dequantize_sum_mx: out (op)= sum_i dequantize_mx(term_i) -- exactly the bytes of piquant_hip_dequantize_mx(term_0, op) followed by
+ *   piquant_hip_dequantize_mx(term_i, ADD) for i = 1 .. count - 1, in order: the running sum is rounded to dtype_out after EVERY term (float32: one
+ *   addition per term; bfloat16: each float32 sum rounded to bfloat16 before the next term is added).  SET never reads out.  count >= 1.  Buffers
+ *   16-byte aligned: ONE launch per 16 terms that keeps the sum in registers (the first with `op`, the following ADD: the same bytes); anything else:
+ *   the composition itself.
+ * piquant_hip_reduce_quantize_mx: (out_codes, out_scales) = quantize_mx(acc + sum_i dequantize_mx(term_i)) -- bit for bit dequantize_mx(term_i, ADD)
+ *   into a copy of acc for i = 0 .. count - 1, in order, the sum rounded to dtype_acc after each term, then quantize_mx of that copy.  acc is NOT
+ *   written; no scratch tensor, no allocation.  count == 0 is quantize_mx(acc); count > 16 aborts like a NULL argument.  ONE launch: streaming for
+ *   16-byte aligned buffers, a guarded kernel (the same bytes) otherwise.
+ * piquant_hip_quantize_mx_batch / piquant_hip_dequantize_mx_batch: member i (its own pointers and numels[i]; dtype, fmt and op shared) gets the bytes
+ *   of the single call.  ONE launch per 16 members; empty members are skipped, a member with a buffer that is not 16-byte aligned goes through the
+ *   single call in its place.
+ * All four: device (or pinned) buffers only, stream-ordered on the context's stream, no host synchronisation, no device allocation
+ * (hipGraph-capturable); numel == 0 is a no-op; a NaN keeps neither payload nor sign. */
+PIQUANT_EXPORT void piquant_hip_dequantize_sum_mx(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, size_t count, void* out,
+                                                  piquant_dtype_t dtype_out, size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op);
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_mx(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* codes,
+                                                   const uint8_t* const* scales, size_t count, void* out_codes, uint8_t* out_scales, size_t numel,
+                                                   piquant_hip_mx_format_t fmt);
+PIQUANT_EXPORT void piquant_hip_quantize_mx_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes,
+                                                  uint8_t* const* scales, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt);
+PIQUANT_EXPORT void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, void* const* outputs,
+                                                    piquant_dtype_t dtype_out, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt,
+                                                    piquant_reduce_op_t op);
+
 /* Host helpers: key <-> float, and the (min,max) -> (scale, zero_point) epilogue in double precision
  * (reference src/piquant.cpp:213-220, 245-258).  keys[0] encodes min, keys[1] encodes -max. */
 PIQUANT_EXPORT void piquant_hip_decode_minmax_keys(const int32_t keys[2], float* out_min, float* out_max);

@@ -352,6 +352,165 @@ void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const 
     if (ctx->blocking) wait_stream(ctx);
 }
 
+// The MX wire (mx_reduce_kernels.hpp): the fused reduce, the dequantize-sum and the two batches.  What the four share: the checks of the two entries
+// above, the terms resolved once (no allocation: at most kMxMaxInputs a launch, on the stack), everything always behind what was enqueued before.
+namespace {
+
+void check_mx_call(const Where& w, const piquant_context_t* ctx, piquant_dtype_t dtype, piquant_hip_mx_format_t fmt) {
+    if (!ctx) bad(w, "context is NULL");
+    if (dtype != PIQUANT_DTYPE_F32 && dtype != PIQUANT_DTYPE_BF16) bad(w, "the float type must be float32 or bfloat16");
+    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
+}
+
+void* mx_float_ptr(const piquant_context_t* ctx, const Where& w, const void* p, piquant_dtype_t dtype) {
+    void* dev = device_ptr(w, ctx->resolve_ptr(p));
+    if (reinterpret_cast<uintptr_t>(dev) % (dtype == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "the float tensor is not aligned to its element size");
+    return dev;
+}
+
+// terms [from, from + n) into `term`; false when one of their buffers is not 16-byte aligned
+bool resolve_mx_terms(const piquant_context_t* ctx, const char* entry, const void* const* codes, const uint8_t* const* scales, size_t from, size_t n,
+                      MxTerm* term) {
+    bool aligned = true;
+    for (size_t i = 0; i < n; ++i) {
+        const Where w {entry, static_cast<long>(from + i)};
+        if (!codes[from + i] || !scales[from + i]) bad(w, "NULL buffer");
+        term[i] = MxTerm {device_ptr(w, ctx->resolve_ptr(codes[from + i])), static_cast<const uint8_t*>(device_ptr(w, resolve(scales[from + i])))};
+        aligned = aligned && aligned16(term[i].codes) && aligned16(term[i].scales);
+    }
+    return aligned;
+}
+
+}  // namespace
+
+void piquant_hip_reduce_quantize_mx(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* codes, const uint8_t* const* scales,
+                                    size_t count, void* out_codes, uint8_t* out_scales, size_t numel, piquant_hip_mx_format_t fmt) {
+    const char* entry = "piquant_hip_reduce_quantize_mx";
+    const Where w {entry};
+    check_mx_call(w, ctx, dtype_acc, fmt);
+    if (count > static_cast<size_t>(kMxMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kMxMaxInputs);
+    if (numel == 0) return;
+    if (!acc || !out_codes || !out_scales) bad(w, "NULL buffer");
+    if (count != 0 && (!codes || !scales)) bad(w, "NULL term list");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    MxReduceLaunch r {mx_float_ptr(ctx, w, acc, dtype_acc), device_ptr(w, ctx->resolve_ptr(out_codes)), static_cast<uint8_t*>(device_ptr(w, resolve(out_scales))),
+                      static_cast<int64_t>(numel), dtype_acc, fmt, {}, static_cast<int>(count)};
+    const bool aligned = resolve_mx_terms(ctx, entry, codes, scales, 0, count, r.term) && aligned16(r.acc) && aligned16(r.codes) && aligned16(r.scales);
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // acc and the terms are written by what was enqueued before: always behind it
+        launch_reduce_quantize_mx(r, !aligned, ctx->stream, ctx->num_cu);
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// Everything 16-byte aligned: one launch per kMxMaxInputs terms, the first with the call's op and the others ADD -- the composition rounds to
+// dtype_out at every term, so where the launches are cut changes no byte.  Anything misaligned: the composition itself, one dequantize_mx per term.
+void piquant_hip_dequantize_sum_mx(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, size_t count, void* out,
+                                   piquant_dtype_t dtype_out, size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_sum_mx";
+    const Where w {entry};
+    check_mx_call(w, ctx, dtype_out, fmt);
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) bad(w, "the reduce op must be SET or ADD");
+    if (count == 0) bad(w, "no terms (count must be at least 1)");
+    if (!codes || !scales) bad(w, "NULL term list");
+    if (numel == 0) return;
+    if (!out) bad(w, "NULL buffer");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    void* out_dev = mx_float_ptr(ctx, w, out, dtype_out);
+    bool aligned = aligned16(out_dev);
+    for (size_t from = 0; from < count; from += kMxMaxInputs) {   // every term is checked before anything is launched
+        MxTerm term[kMxMaxInputs];
+        aligned = resolve_mx_terms(ctx, entry, codes, scales, from, std::min(count - from, static_cast<size_t>(kMxMaxInputs)), term) && aligned;
+    }
+    {   // both scopes end before the wait
+        StopEventScope completion(ctx);
+        IndependentCallScope independent(ctx, true);   // the terms and an ADD's out are written by what was enqueued before: always behind it
+        for (size_t from = 0; from < count; from += kMxMaxInputs) {
+            const size_t n = std::min(count - from, static_cast<size_t>(kMxMaxInputs));
+            MxDequantSumLaunch d {out_dev, static_cast<int64_t>(numel), dtype_out, fmt, from == 0 && op == PIQUANT_REDUCE_OP_SET ? OP_SET : OP_ADD, {},
+                                  static_cast<int>(n)};
+            resolve_mx_terms(ctx, entry, codes, scales, from, n, d.term);
+            if (aligned) {
+                launch_dequantize_sum_mx(d, ctx->stream);
+                continue;
+            }
+            for (size_t i = 0; i < n; ++i)
+                launch_dequantize_mx(MxDequantLaunch {d.term[i].codes, d.term[i].scales, out_dev, d.numel, dtype_out, fmt, i == 0 ? d.op : OP_ADD}, ctx->stream,
+                                     ctx->num_cu);
+        }
+    }
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+// The batches: piquant_hip_quantize_grouped_batch's rule.  Empty members are skipped, a member with a buffer that is not 16-byte aligned runs alone
+// through the single launch (the guarded kernel, the same bytes), the others collect and leave every kMxMaxInputs members and at the end.
+void piquant_hip_quantize_mx_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes, uint8_t* const* scales,
+                                   const size_t* numels, size_t count, piquant_hip_mx_format_t fmt) {
+    const char* entry = "piquant_hip_quantize_mx_batch";
+    check_mx_call(Where {entry}, ctx, dtype_in, fmt);
+    if (count == 0) return;
+    if (!inputs || !codes || !scales || !numels) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    MxQuantBatchLaunch b {};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx);
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        const Where w {entry, static_cast<long>(i)};
+        if (!inputs[i] || !codes[i] || !scales[i]) bad(w, "NULL buffer");
+        const MxQuantLaunch q {mx_float_ptr(ctx, w, inputs[i], dtype_in), device_ptr(w, ctx->resolve_ptr(codes[i])),
+                               static_cast<uint8_t*>(device_ptr(w, resolve(scales[i]))), static_cast<int64_t>(numels[i]), dtype_in, fmt};
+        if (!(aligned16(q.in) && aligned16(q.codes) && aligned16(q.scales))) {
+            launch_quantize_mx(q, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        b.t[b.count] = q;
+        if (++b.count == kMxMaxInputs) {
+            launch_quantize_mx_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_quantize_mx_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
+void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, void* const* outputs,
+                                     piquant_dtype_t dtype_out, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
+    const char* entry = "piquant_hip_dequantize_mx_batch";
+    check_mx_call(Where {entry}, ctx, dtype_out, fmt);
+    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("%s: the reduce op must be SET or ADD", entry);
+    if (count == 0) return;
+    if (!codes || !scales || !outputs || !numels) panic("%s: NULL argument", entry);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    MxDequantBatchLaunch b {};
+    StopEventScope completion(ctx);
+    IndependentCallScope independent(ctx, true);   // the scale bytes are written by whatever was enqueued just before
+    for (size_t i = 0; i < count; ++i) {
+        if (numels[i] == 0) continue;
+        const Where w {entry, static_cast<long>(i)};
+        if (!codes[i] || !scales[i] || !outputs[i]) bad(w, "NULL buffer");
+        const MxDequantLaunch d {device_ptr(w, ctx->resolve_ptr(codes[i])), static_cast<const uint8_t*>(device_ptr(w, resolve(scales[i]))),
+                                 mx_float_ptr(ctx, w, outputs[i], dtype_out), static_cast<int64_t>(numels[i]), dtype_out, fmt,
+                                 op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET};
+        if (!(aligned16(d.codes) && aligned16(d.scales) && aligned16(d.out))) {
+            launch_dequantize_mx(d, ctx->stream, ctx->num_cu);
+            continue;
+        }
+        b.t[b.count] = d;
+        if (++b.count == kMxMaxInputs) {
+            launch_dequantize_mx_batch(b, ctx->stream);
+            b.count = 0;
+        }
+    }
+    launch_dequantize_mx_batch(b, ctx->stream);
+    if (ctx->blocking) wait_stream(ctx);
+}
+
 // The three rotated calls (grouped_rot_kernels.hpp): the two entries above with the rotation's seed, and the stand-alone transform.  In and out
 // 16-byte aligned: the streaming kernels; anything else element-aligned: the guarded ones, the same bytes.
 void piquant_hip_hadamard_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype, void* out, size_t numel, size_t group_size,

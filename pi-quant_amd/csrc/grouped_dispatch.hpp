@@ -47,6 +47,22 @@ inline void with_quant_bits(int dt, F&& f) {
     }
 }
 
+// the MX units' (kernels_mx.hip, kernels_mx_reduce.hip, kernels_mx_batch.hip)
+template <class F>
+inline void with_mx_format(int fmt, F&& f) {
+    switch (fmt) {
+        case MX_FP4_E2M1: f(std::integral_constant<int, MX_FP4_E2M1> {}); return;
+        case MX_FP8_E4M3: f(std::integral_constant<int, MX_FP8_E4M3> {}); return;
+        default: panic("invalid MX format %d", fmt);
+    }
+}
+
+// grid of the MX guarded kernels: a thread per item, grid-stride beyond 16 blocks per CU (256 CUs when num_cu is not known)
+inline unsigned mx_guarded_blocks(int64_t items, int num_cu) {
+    const int64_t want = (items + kGroupedBlock - 1) / kGroupedBlock, cap = static_cast<int64_t>(16) * (num_cu > 0 ? num_cu : 256);
+    return static_cast<unsigned>(want < cap ? want : cap);
+}
+
 // the rounding modes of quantize_grouped_mode: the nearest step of quantize_uniform for the pair
 template <int DT_IN, int BITS, class F>
 inline void with_round_mode(int round_mode, F&& f) {

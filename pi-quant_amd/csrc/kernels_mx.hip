@@ -10,22 +10,7 @@ namespace pq {
 
 namespace {
 
-template <class F>
-void with_mx_format(int fmt, F&& f) {
-    switch (fmt) {
-        case MX_FP4_E2M1: f(std::integral_constant<int, MX_FP4_E2M1> {}); return;
-        case MX_FP8_E4M3: f(std::integral_constant<int, MX_FP8_E4M3> {}); return;
-        default: panic("invalid MX format %d", fmt);
-    }
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// grid of the guarded kernels: a thread per item, grid-stride beyond 16 blocks per CU (256 CUs when num_cu is not known)
-unsigned mx_guarded_blocks(int64_t items, int num_cu) {
-    const int64_t want = (items + kGroupedBlock - 1) / kGroupedBlock, cap = static_cast<int64_t>(16) * (num_cu > 0 ? num_cu : 256);
-    return static_cast<unsigned>(want < cap ? want : cap);
-}
 
 }  // namespace
 

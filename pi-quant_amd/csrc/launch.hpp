@@ -278,6 +278,50 @@ struct MxDequantLaunch {
 };
 void launch_quantize_mx(const MxQuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize_mx(const MxDequantLaunch& d, hipStream_t stream, int num_cu);
+// The MX wire (mx_reduce_kernels.hpp; kernels_mx_reduce.hip, kernels_mx_batch.hip): at most kMxMaxInputs terms, or batch members, per launch.
+//   reduce       (codes, scales) = quantize_mx(acc + sum_i dequantize_mx(term[i])), the terms added in order and the sum rounded to dt_acc after each;
+//                acc is only read.  ONE launch for 0 .. kMxMaxInputs terms: the streaming kernel when every buffer is 16-byte aligned, `guarded`
+//                (acc aligned to its element) otherwise -- the same bytes.
+//   dequant-sum  out (op)= sum_i dequantize_mx(term[i]), the same order and rounding.  ONE launch for 1 .. kMxMaxInputs terms, every buffer 16-byte
+//                aligned: the caller sends anything else through launch_dequantize_mx, term by term (the same bytes).
+//   batches      member i gets the bytes of the single launch on t[i]; every member non-empty and 16-byte aligned (the caller sends anything else
+//                through the single launches); dt and fmt are t[0]'s, op is t[0]'s.  A batch of one launches the single kernel.
+constexpr int kMxMaxInputs = 16;
+struct MxTerm {
+    const void* codes;
+    const uint8_t* scales;
+};
+struct MxReduceLaunch {
+    const void* acc;       // numel elements of dt_acc
+    void* codes;
+    uint8_t* scales;
+    int64_t numel;
+    int dt_acc;            // DT_F32 / DT_BF16
+    int fmt;               // of the terms and of the result
+    MxTerm term[kMxMaxInputs];
+    int count;
+};
+struct MxDequantSumLaunch {
+    void* out;             // numel elements of dt_out
+    int64_t numel;
+    int dt_out;
+    int fmt;
+    int op;                // OP_SET / OP_ADD
+    MxTerm term[kMxMaxInputs];
+    int count;
+};
+struct MxQuantBatchLaunch {
+    MxQuantLaunch t[kMxMaxInputs];
+    int count;
+};
+struct MxDequantBatchLaunch {
+    MxDequantLaunch t[kMxMaxInputs];
+    int count;
+};
+void launch_reduce_quantize_mx(const MxReduceLaunch& r, bool guarded, hipStream_t stream, int num_cu);
+void launch_dequantize_sum_mx(const MxDequantSumLaunch& d, hipStream_t stream);
+void launch_quantize_mx_batch(const MxQuantBatchLaunch& b, hipStream_t stream);
+void launch_dequantize_mx_batch(const MxDequantBatchLaunch& b, hipStream_t stream);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

@@ -151,25 +151,13 @@ __device__ __forceinline__ void mx_unpack_bits(const u32x4& raw, uint32_t (&x)[I
     }
 }
 
+// The tile's NV rows in `raw` (grouped_load: elements at or past numel are quiet NaNs) -> its codes and scale bytes, staged through the wave's LDS
+// slices and stored.  Shared by the single kernel, the batch (kernels_mx_batch.hip) and the fused reduce (mx_reduce_kernels.hpp).
 template <int DT_IN, int FMT>
-__global__ void __launch_bounds__(kGroupedBlock)
-quantize_mx_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks) {
+__device__ __forceinline__ void mx_quantize_rows(const u32x4 (&raw)[MxQuantTile<DT_IN, FMT>::NV], uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
+                                                 int64_t numel, int64_t nblocks, int64_t tile, bool full, int lane, uint8_t* stage, uint8_t* stage_scales) {
     using T = MxQuantTile<DT_IN, FMT>;
-    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, LPB = T::LPB, BPR = T::BPR, NB = T::NB, WAVES = kGroupedBlock / 64;
-    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::OUT_BYTES];
-    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][NB];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
-    const int64_t e0 = tile * T::TILE_ELEMS;
-    if (e0 >= numel) return;
-    const bool full = e0 + T::TILE_ELEMS <= numel;                  // wave-uniform
-    uint8_t* stage = s_codes[wave];
-    uint8_t* stage_scales = s_scales[wave];
-
-    u32x4 raw[NV];
-    grouped_load<DT_IN, NV>(in, numel, e0 / EPV, lane, full, raw);
+    constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, LPB = T::LPB, BPR = T::BPR, NB = T::NB;
 #pragma unroll
     for (int r = 0; r < NV; ++r) {
         uint32_t x[EPV];
@@ -203,6 +191,33 @@ quantize_mx_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uin
         const int64_t blocks_left = nblocks - tile * NB;
         for (int b = lane; b < NB && b < blocks_left; b += 64) osc[b] = stage_scales[b];
     }
+}
+
+// one wave's tile of one tensor (tile * TILE_ELEMS < numel): load, then mx_quantize_rows
+template <int DT_IN, int FMT>
+__device__ __forceinline__ void mx_quantize_tile(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel,
+                                                 int64_t nblocks, int64_t tile, int lane, uint8_t* stage, uint8_t* stage_scales) {
+    using T = MxQuantTile<DT_IN, FMT>;
+    const int64_t e0 = tile * T::TILE_ELEMS;
+    const bool full = e0 + T::TILE_ELEMS <= numel;                  // wave-uniform
+    u32x4 raw[T::NV];
+    grouped_load<DT_IN, T::NV>(in, numel, e0 / T::EPV, lane, full, raw);
+    mx_quantize_rows<DT_IN, FMT>(raw, codes, scales, numel, nblocks, tile, full, lane, stage, stage_scales);
+}
+
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks) {
+    using T = MxQuantTile<DT_IN, FMT>;
+    constexpr int WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::OUT_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][T::NB];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (tile * T::TILE_ELEMS >= numel) return;
+    mx_quantize_tile<DT_IN, FMT>(in, codes, scales, numel, nblocks, tile, lane, s_codes[wave], s_scales[wave]);
 }
 
 // element i of a float32 / bfloat16 tensor as float32 bits
@@ -269,22 +284,14 @@ __device__ __forceinline__ void mx_store_one(void* out, int64_t i, float d) {
     }
 }
 
+// one wave's tile of one tensor (tile * TILE_ELEMS < numel).  Shared by the single kernel and the batch (kernels_mx_batch.hip).
 template <int FMT, int DT_OUT, int OP>
-__global__ void __launch_bounds__(kGroupedBlock)
-dequantize_mx_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales, void* __restrict__ out, int64_t numel, int64_t nblocks) {
+__device__ __forceinline__ void mx_dequantize_tile(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales, void* __restrict__ out, int64_t numel,
+                                                   int64_t nblocks, int64_t tile, int lane, uint8_t* stage, uint8_t* stage_scales) {
     using T = MxDequantTile<FMT, DT_OUT>;
-    constexpr int EPV = T::EPV, IB = T::IB, NB = T::NB, WORDS = IB > 4 ? 2 : 1, WAVES = kGroupedBlock / 64;
-    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::TILE_BYTES];
-    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][NB];
-
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    constexpr int EPV = T::EPV, IB = T::IB, NB = T::NB, WORDS = IB > 4 ? 2 : 1;
     const int64_t e0 = tile * T::TILE_ELEMS;
-    if (e0 >= numel) return;
     const bool full = e0 + T::TILE_ELEMS <= numel;                  // wave-uniform
-    uint8_t* stage = s_codes[wave];
-    uint8_t* stage_scales = s_scales[wave];
     const int64_t b0 = tile * T::TILE_BYTES, nbytes = (numel * T::BITS + 7) / 8;
 
     u32x4 raw[T::NIN];
@@ -358,6 +365,21 @@ dequantize_mx_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restric
             }
         }
     }
+}
+
+template <int FMT, int DT_OUT, int OP>
+__global__ void __launch_bounds__(kGroupedBlock)
+dequantize_mx_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales, void* __restrict__ out, int64_t numel, int64_t nblocks) {
+    using T = MxDequantTile<FMT, DT_OUT>;
+    constexpr int WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::TILE_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][T::NB];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (tile * T::TILE_ELEMS >= numel) return;
+    mx_dequantize_tile<FMT, DT_OUT, OP>(codes, scales, out, numel, nblocks, tile, lane, s_codes[wave], s_scales[wave]);
 }
 
 // Guarded form for buffers that are not 16-byte aligned: element by element, the same bytes.

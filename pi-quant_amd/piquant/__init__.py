@@ -486,6 +486,45 @@ class Context:
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_dequantize_mx(self._ctx, codes_ptr, scales_ptr, ptr_out, dtype_out.value, numel, fmt, reduce_op.value)
 
+    def dequantize_sum_mx_ptr(self, codes_ptrs, scales_ptrs, ptr_out: int, dtype_out: DataType, numel: int, fmt: int, reduce_op: ReduceOp,
+                              _device_ptrs: bool = False) -> None:
+        """``out (op)= sum_i dequantize_mx(term_i)``, the terms added in order and the sum rounded to ``dtype_out`` after each
+        (``piquant_hip_dequantize_sum_mx``): one launch per 16 terms."""
+        n = len(codes_ptrs)
+        assert dtype_out.is_dequantized and fmt in (0, 1) and n == len(scales_ptrs) and n >= 1
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_sum_mx(self._ctx, (_C.c_void_p * n)(*codes_ptrs), (_C.c_void_p * n)(*scales_ptrs), n, ptr_out, dtype_out.value, numel, fmt,
+                                        reduce_op.value)
+
+    def reduce_quantize_mx_ptr(self, ptr_acc: int, dtype_acc: DataType, codes_ptrs, scales_ptrs, out_codes_ptr: int, out_scales_ptr: int, numel: int,
+                               fmt: int, _device_ptrs: bool = False) -> None:
+        """``quantize_mx(acc + sum_i dequantize_mx(term_i))`` in one launch (``piquant_hip_reduce_quantize_mx``); ``acc`` is only read.  At most 16
+        terms: more is a ValueError here (the C call aborts)."""
+        n = len(codes_ptrs)
+        if n > 16:
+            raise ValueError(f'reduce_quantize_mx takes at most 16 terms, got {n}')
+        assert dtype_acc.is_dequantized and fmt in (0, 1) and n == len(scales_ptrs)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_reduce_quantize_mx(self._ctx, ptr_acc, dtype_acc.value, (_C.c_void_p * n)(*codes_ptrs), (_C.c_void_p * n)(*scales_ptrs), n,
+                                         out_codes_ptr, out_scales_ptr, numel, fmt)
+
+    def quantize_mx_batch_ptr(self, ptrs_in, dtype_in: DataType, codes_ptrs, scales_ptrs, numels, fmt: int, _device_ptrs: bool = False) -> None:
+        """``quantize_mx_ptr`` for several independent tensors, up to 16 per kernel launch (``piquant_hip_quantize_mx_batch``)."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and fmt in (0, 1) and n == len(codes_ptrs) == len(scales_ptrs) == len(numels)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*codes_ptrs),
+                                        (_C.c_void_p * n)(*scales_ptrs), (_C.c_size_t * n)(*numels), n, fmt)
+
+    def dequantize_mx_batch_ptr(self, codes_ptrs, scales_ptrs, ptrs_out, dtype_out: DataType, numels, fmt: int, reduce_op: ReduceOp,
+                                _device_ptrs: bool = False) -> None:
+        """``dequantize_mx_ptr`` for several independent tensors, up to 16 per kernel launch (``piquant_hip_dequantize_mx_batch``)."""
+        n = len(codes_ptrs)
+        assert dtype_out.is_dequantized and fmt in (0, 1) and n == len(scales_ptrs) == len(ptrs_out) == len(numels)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_dequantize_mx_batch(self._ctx, (_C.c_void_p * n)(*codes_ptrs), (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*ptrs_out),
+                                          dtype_out.value, (_C.c_size_t * n)(*numels), n, fmt, reduce_op.value)
+
     def quantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
                                    zero_points_ptrs, params_given: bool, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         """``quantize_grouped_ptr`` for several independent tensors (own parameter arrays each), up to 16 per kernel launch

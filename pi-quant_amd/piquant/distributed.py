@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import Context, DataType, decode_minmax_keys, quant_params_from_minmax
+from .torch import MX_FORMATS as _MX_FORMATS
 from .torch import _QUANT_TYPES, _REDUCE_OPS, _ROUND_MODES, _ctx_for, _residual_dtype, torch_to_piquant_dtype
 
 
@@ -443,6 +444,24 @@ def grouped_wire_layout(numel: int, group_size: int, packed_bits: int) -> Groupe
     return GroupedWireLayout(ngroups, zp, data, data + -(-int(numel) * int(packed_bits) // 8))
 
 
+class MxWireLayout(NamedTuple):
+    """One chunk's record on the MX wire: ``uint8 scales[nblocks] | pad to 16 | codes``."""
+    scales_offset: int       # 0
+    codes_offset: int        # nblocks rounded up to 16: the codes start on a vector boundary of the kernels
+    nbytes: int              # the whole record (scale bytes, padding, code bytes)
+
+
+def mx_wire_layout(numel: int, format: str) -> MxWireLayout:
+    """Layout of the MX wire record of a chunk of ``numel`` elements (``quantized_all_reduce(mx_format=...)``): nblocks = ceil(numel / 32) E8M0
+    scale bytes, zero padding up to a multiple of 16 bytes, then the FP4 E2M1 (``ceil(numel / 2)`` bytes) or FP8 E4M3 (``numel`` bytes) codes --
+    one parameter byte per 32 elements where the grouped wire carries 5 per group.  The record of an empty chunk is empty."""
+    from .torch import mx_nbytes
+
+    ncodes, nblocks = mx_nbytes(numel, format)
+    codes = -(-nblocks // 16) * 16
+    return MxWireLayout(0, codes, codes + ncodes)
+
+
 class _DeviceOps:
     """Wire encode / decode on ROCm device tensors (HIP kernels through libpiquant.so).  The parameters are derived on
     the device straight into the buffer's header and read back from it by the receiver's dequantize kernel: a hop
@@ -597,6 +616,54 @@ class _DeviceOps:
         self._cx(acc).reduce_quantize_grouped_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[2] for r in recs],
                                                      [r[0] for r in recs], [r[1] for r in recs], data, torch_to_piquant_dtype(qdtype), n, group_size, sc, zp,
                                                      self._mode(round_mode), _device_ptrs=True, residual_dtype=_residual_dtype(residual, acc))
+
+    # ---- the MX wire (mx_wire_layout): one E8M0 scale byte per block of 32 in front of the FP4 / FP8 codes; nearest rounding only ----
+    @staticmethod
+    def _record_mx(buf: torch.Tensor, numel: int, fmt: str):
+        """(codes, scales) addresses of the MX record in ``buf``"""
+        p = buf.data_ptr()
+        return p + mx_wire_layout(numel, fmt).codes_offset, p
+
+    def encode_mx(self, x: torch.Tensor, buf: torch.Tensor, fmt: str) -> None:
+        codes, sc = self._record_mx(buf, x.numel(), fmt)
+        self._cx(x).quantize_mx_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), codes, sc, x.numel(), _MX_FORMATS[fmt], _device_ptrs=True)
+
+    def encode_batch_mx(self, xs, bufs, fmt: str) -> None:
+        """encode_mx(xs[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record_mx(b, x.numel(), fmt) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_mx_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r[0] for r in recs], [r[1] for r in recs],
+                                                  [x.numel() for x in xs], _MX_FORMATS[fmt], _device_ptrs=True)
+
+    def decode_mx(self, buf: torch.Tensor, out: torch.Tensor, reduce_op: str, fmt: str) -> None:
+        codes, sc = self._record_mx(buf, out.numel(), fmt)
+        self._cx(out).dequantize_mx_ptr(codes, sc, out.data_ptr(), torch_to_piquant_dtype(out.dtype), out.numel(), _MX_FORMATS[fmt], _REDUCE_OPS[reduce_op],
+                                        _device_ptrs=True)
+
+    def decode_batch_mx(self, bufs, outs, reduce_op: str, fmt: str) -> None:
+        """decode_mx(bufs[i], outs[i]) for all i with one kernel launch per 16 chunks."""
+        if bufs:
+            recs = [self._record_mx(b, o.numel(), fmt) for b, o in zip(bufs, outs)]
+            self._cx(outs[0]).dequantize_mx_batch_ptr([r[0] for r in recs], [r[1] for r in recs], [o.data_ptr() for o in outs],
+                                                      torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], _MX_FORMATS[fmt],
+                                                      _REDUCE_OPS[reduce_op], _device_ptrs=True)
+
+    def reduce_encode_mx(self, bufs, acc: torch.Tensor, buf: torch.Tensor, fmt: str) -> None:
+        """encode_mx(acc + the wire buffers, added in order) into ``buf`` as ONE launch; ``acc`` is only read."""
+        n = acc.numel()
+        recs = [self._record_mx(b, n, fmt) for b in bufs]
+        codes, sc = self._record_mx(buf, n, fmt)
+        self._cx(acc).reduce_quantize_mx_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [r[0] for r in recs], [r[1] for r in recs], codes, sc, n,
+                                             _MX_FORMATS[fmt], _device_ptrs=True)
+
+    def decode_sum_mx(self, bufs, out: torch.Tensor, reduce_op: str, fmt: str) -> None:
+        """out (op)= the wire buffers, added in order, ONE launch per 16 and one pass over ``out`` (the bytes of decode_mx buffer by buffer, the first
+        with ``reduce_op`` and the others with 'add')."""
+        if bufs:
+            n = out.numel()
+            recs = [self._record_mx(b, n, fmt) for b in bufs]
+            self._cx(out).dequantize_sum_mx_ptr([r[0] for r in recs], [r[1] for r in recs], out.data_ptr(), torch_to_piquant_dtype(out.dtype), n,
+                                                _MX_FORMATS[fmt], _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
     # ---- the grouped wire in the rotated domain (``rotation_seed``): the same records, holding the rotated values ----
     def encode_grouped_rotated(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
@@ -810,8 +877,9 @@ class _Wire:
     takes part, the step works on that slice of it."""
 
     def __init__(self, ops, quant_dtype: torch.dtype, round_mode: str, group_size: Optional[int] = None, residual: Optional[torch.Tensor] = None,
-                 requantize: bool = False, rotation_seed: Optional[int] = None, clip_steps: Optional[int] = None):
+                 requantize: bool = False, rotation_seed: Optional[int] = None, clip_steps: Optional[int] = None, mx_format: Optional[str] = None):
         self.ops, self.round_mode, self.group_size = ops, round_mode, group_size
+        self.mx = mx_format                      # the MX wire (mx_wire_layout): never with a group size, a seed, a residual or a clip search (_check_mx_format)
         self.seed = rotation_seed
         self.clip_steps = clip_steps             # the encodes search each group's clipping range (never with a seed or a residual: _check_clip_steps)
         self.quant_dtype, self.qdt = quant_dtype, torch_to_piquant_dtype(quant_dtype)     # the torch dtype the ops take, its DataType for the lengths
@@ -820,13 +888,17 @@ class _Wire:
 
     def nbytes(self, numel: int) -> int:
         """Length of the record of ``numel`` elements."""
+        if self.mx is not None:
+            return mx_wire_layout(numel, self.mx).nbytes
         if self.group_size is None:
             return _HEADER_BYTES + self.qdt.packed_nbytes(numel)
         return grouped_wire_layout(numel, self.group_size, self.qdt.bit_size).nbytes
 
     def encode(self, x, buf, chunk, ef: bool = True) -> None:
         """``ef`` False: the rotated owner's encode without ``requantize``, which leaves the residual alone."""
-        if self.group_size is None:
+        if self.mx is not None:
+            self.ops.encode_mx(x, buf, self.mx)
+        elif self.group_size is None:
             self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
         elif self.clip_steps is not None:
             self.ops.encode_grouped_clipped(x, buf, self.quant_dtype, self.round_mode, self.group_size, self.clip_steps)
@@ -840,7 +912,9 @@ class _Wire:
             self.ops.encode_grouped_ef(x, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size)
 
     def encode_batch(self, xs, bufs, chunks) -> None:
-        if self.group_size is None:
+        if self.mx is not None:
+            self.ops.encode_batch_mx(xs, bufs, self.mx)
+        elif self.group_size is None:
             self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
         elif self.clip_steps is not None:
             self.ops.encode_batch_grouped_clipped(xs, bufs, self.quant_dtype, self.round_mode, self.group_size, self.clip_steps)
@@ -856,7 +930,9 @@ class _Wire:
 
     def reduce_encode(self, terms, acc, buf, chunk) -> None:
         """encode(acc + the records in ``terms``, added in order) into ``buf``, one launch; the residual takes part only with ``requantize``."""
-        if self.group_size is None:
+        if self.mx is not None:
+            self.ops.reduce_encode_mx(terms, acc, buf, self.mx)
+        elif self.group_size is None:
             self.ops.reduce_encode(terms, acc, buf, self.quant_dtype, self.round_mode)
         elif self.seed is not None and not self.requantize:
             self.ops.reduce_encode_grouped_rotated(terms, acc, buf, self.quant_dtype, self.round_mode, self.group_size, self.seed)
@@ -882,7 +958,9 @@ class _Wire:
             self.encode(acc, buf, chunk, ef=self.requantize)
 
     def decode(self, buf, out, op: str) -> None:
-        if self.group_size is None:
+        if self.mx is not None:
+            self.ops.decode_mx(buf, out, op, self.mx)
+        elif self.group_size is None:
             self.ops.decode(buf, out, self.quant_dtype, op)
         elif self.seed is not None:
             self.ops.decode_grouped_rotated(buf, out, self.quant_dtype, op, self.group_size, self.seed)
@@ -890,7 +968,9 @@ class _Wire:
             self.ops.decode_grouped(buf, out, self.quant_dtype, op, self.group_size)
 
     def decode_batch(self, bufs, outs, op: str) -> None:
-        if self.group_size is None:
+        if self.mx is not None:
+            self.ops.decode_batch_mx(bufs, outs, op, self.mx)
+        elif self.group_size is None:
             self.ops.decode_batch(bufs, outs, self.quant_dtype, op)
         elif self.seed is not None:
             self.ops.decode_batch_grouped_rotated(bufs, outs, self.quant_dtype, op, self.group_size, self.seed)
@@ -898,8 +978,10 @@ class _Wire:
             self.ops.decode_batch_grouped(bufs, outs, self.quant_dtype, op, self.group_size)
 
     def decode_sum(self, terms, out, op: str) -> None:
-        """The grouped wire's only: nothing sums per-chunk records under a ``reduce_op``."""
-        if self.seed is not None:
+        """The grouped and the MX wire's only: nothing sums per-chunk records under a ``reduce_op``."""
+        if self.mx is not None:
+            self.ops.decode_sum_mx(terms, out, op, self.mx)
+        elif self.seed is not None:
             self.ops.decode_sum_grouped_rotated(terms, out, self.quant_dtype, op, self.group_size, self.seed)
         else:
             self.ops.decode_sum_grouped(terms, out, self.quant_dtype, op, self.group_size)
@@ -998,6 +1080,7 @@ def quantized_all_reduce(
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
+    mx_format: Optional[str] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1098,9 +1181,23 @@ def quantized_all_reduce(
 
     ``clip_steps`` must stay None: the per-group clip search serves ``quantized_reduce_scatter`` and ``quantized_all_gather``, where no partial sum
     is re-quantized; here it raises ValueError before anything moves.
+
+    ``mx_format`` (None, ``'fp4_e2m1'`` or ``'fp8_e4m3'``; default None: every byte, every launch and every ``_ops`` call as without it): the wire
+    carries OCP microscaling records -- ``uint8 scales[nblocks] | pad to 16 | codes`` (``mx_wire_layout``), one power-of-two scale byte per block of
+    32 elements and no zero point, 0.53 (FP4) or 1.03 (FP8) bytes per element.  ``ring_chunks`` keeps every interior boundary on a multiple of 4096
+    elements, so the wire's blocks are the whole tensor's.  Every encode is ``quantize_mx`` (the mesh's peers: ONE ``quantize_mx_batch`` launch),
+    every ring hop and the mesh owner's step ONE ``reduce_quantize_mx`` launch, every decode ``dequantize_mx`` 'set' of the same bytes on every
+    rank (the mesh's: ONE ``dequantize_mx_batch`` launch): three launches per direct all-reduce, all ranks bit-identical, and
+    ``quantized_reduce_scatter`` + ``quantized_all_gather`` leave exactly the direct all-reduce's bytes.  Nearest rounding only.  ValueError before
+    anything moves: together with ``group_size``, ``error_feedback``, ``error_feedback_requantize``, ``rotation_seed``, ``rotated_error_feedback``,
+    ``clip_steps`` or ``transport='p2p'``, with a ``quant_dtype`` other than the default, with a ``round_mode`` other than 'nearest', and in the
+    direct schedule with more than 17 ranks.  (Unmeasured on more than one GPU.)
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
+    _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
+                     error_feedback_requantize=error_feedback_requantize, rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback,
+                     clip_steps=clip_steps, transport=transport)
     _check_clip_steps(clip_steps, group_size, all_reduce=True)
     if algorithm not in ('ring', 'direct'):
         raise ValueError(f"algorithm must be 'ring' or 'direct', got {algorithm!r}")
@@ -1115,7 +1212,8 @@ def quantized_all_reduce(
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
                                            group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize,
-                                           rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
+                                           rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, mx_format=mx_format, _ops=_ops,
+                                           _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
@@ -1123,7 +1221,7 @@ def quantized_all_reduce(
     if world == 1 and not _single_rank_collectives:
         return tensor
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 error_feedback_requantize, seed)
+                 error_feedback_requantize, seed, mx_format=mx_format)
     _ring(wire, _Chunks.of(wire, tensor.view(-1), world), group, world, rank, tensor.device)
     return tensor
 
@@ -1143,6 +1241,7 @@ def quantized_all_reduce_direct(
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
+    mx_format: Optional[str] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1188,9 +1287,16 @@ def quantized_all_reduce_direct(
     ``quantize_grouped_rotated_ef`` on the peers' chunks of it; with ``error_feedback_requantize`` the owner's ``quantize_grouped_rotated`` becomes
     ``quantize_grouped_rotated_ef`` on the rank's own chunk.  It belongs to one (world size, rank, algorithm, ``error_feedback_requantize``, seed,
     group size).
+
+    ``mx_format``: the MX wire of ``quantized_all_reduce`` -- step 1 is ONE ``quantize_mx_batch`` launch, steps 3-4 ONE ``reduce_quantize_mx`` launch
+    over the G-1 received records in increasing rank order, the decode ONE ``dequantize_mx_batch`` launch.  At most 17 ranks; collective transport,
+    nearest rounding and none of the grouped wire's keywords.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
+    _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
+                     error_feedback_requantize=error_feedback_requantize, rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback,
+                     clip_steps=clip_steps, transport=transport)
     _check_clip_steps(clip_steps, group_size, all_reduce=True)
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
@@ -1201,10 +1307,11 @@ def quantized_all_reduce_direct(
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     _check_rotated_terms(seed, world, 'the direct schedule')
+    _check_mx_terms(mx_format, world, 'the direct schedule')
     if world == 1 and not _single_rank_collectives:
         return tensor
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 error_feedback_requantize, seed)
+                 error_feedback_requantize, seed, mx_format=mx_format)
     flat = tensor.view(-1)
     ch = _Chunks.of(wire, flat, world)
     if transport == 'p2p':
@@ -1330,6 +1437,39 @@ def _check_clip_steps(clip_steps, group_size, rotation_seed=None, error_feedback
         raise ValueError("clip_steps= is not supported with transport='p2p'; use transport='collective'")
 
 
+_MX_MAX_TERMS = 16   # piquant_hip_reduce_quantize_mx: one launch, the sum never leaves the registers
+
+
+def _check_mx_format(mx_format, *, quant_dtype, round_mode, group_size, error_feedback=None, error_feedback_requantize=False, rotation_seed=None,
+                     rotated_error_feedback=None, clip_steps=None, transport: str = 'collective', default_group_size=None) -> None:
+    """ValueError before anything moves: the MX wire is a wire of its own -- its blocks of 32 are no groups, its scale bytes no (scale, zero point),
+    its rounding nearest -- so it goes with none of the grouped wire's keywords, no ``quant_dtype`` and no peer-to-peer transport.
+    ``default_group_size``: what ``group_size`` is when the caller did not pass it (128 for the two sharded collectives)."""
+    if mx_format is None:
+        return
+    if not (isinstance(mx_format, str) and mx_format in _MX_FORMATS):
+        raise ValueError(f'mx_format must be None or one of {sorted(_MX_FORMATS)}, got {mx_format!r}')
+    if group_size != default_group_size:
+        raise ValueError('mx_format= is not supported with group_size= (an MX block is 32 elements under one scale byte; leave group_size at its default)')
+    for name, given in (('error_feedback', error_feedback is not None), ('error_feedback_requantize', bool(error_feedback_requantize)),
+                        ('rotation_seed', rotation_seed is not None), ('rotated_error_feedback', rotated_error_feedback is not None),
+                        ('clip_steps', clip_steps is not None)):
+        if given:
+            raise ValueError(f'mx_format= is not supported with {name}=')
+    if transport == 'p2p':
+        raise ValueError("mx_format= is not supported with transport='p2p'; use transport='collective'")
+    if quant_dtype != torch.uint8:
+        raise ValueError(f'mx_format= names the wire format itself: quant_dtype must stay at its default, got {quant_dtype}')
+    if round_mode != 'nearest':
+        raise ValueError(f"mx_format= rounds to nearest only (quantize_mx has no stochastic mode), got round_mode={round_mode!r}")
+
+
+def _check_mx_terms(mx_format, world: int, what: str) -> None:
+    """ValueError before anything moves: the owner's step of an MX mesh schedule is one launch over world - 1 records, at most 16."""
+    if mx_format is not None and world - 1 > _MX_MAX_TERMS:
+        raise ValueError(f'mx_format= with {what} takes at most {_MX_MAX_TERMS + 1} ranks (the owner sums world - 1 records in one launch), got {world}')
+
+
 def _check_sharded_collective(name: str, tensor: torch.Tensor, group_size, error_feedback) -> None:
     """ValueError before anything moves, for ``quantized_reduce_scatter`` and ``quantized_all_gather``: the tensor, a group size that is no group
     size (``None`` included: they have the grouped wire only) and a residual that does not match the tensor."""
@@ -1353,6 +1493,7 @@ def quantized_reduce_scatter(
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
+    mx_format: Optional[str] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1393,22 +1534,30 @@ def quantized_reduce_scatter(
     launch per 16 chunks -- every group of every record is quantized with the best of ``clip_steps`` shrunk ranges (``piquant.torch.quantize_grouped_clipped``);
     the records, the all-to-all and step 3 are unchanged.  Not with ``rotation_seed``, ``error_feedback`` or ``rotated_error_feedback``.
 
+    ``mx_format`` (as in ``quantized_all_reduce``; ``group_size`` must be left at its default, which is then not used): step 1 is ONE
+    ``quantize_mx_batch`` launch per 16 chunks, step 3 ONE ``dequantize_sum_mx(..., 'add')`` launch into the own chunk.  Followed by
+    ``quantized_all_gather`` with the same format it leaves exactly the bytes of ``quantized_all_reduce(algorithm='direct', mx_format=...)``, whose
+    ``reduce_quantize_mx`` is defined as these ADDs followed by ``quantize_mx``.  At most 17 ranks.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
     of this module's multi-GPU paths.)"""
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
+    _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
+                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     _check_rotated_terms(seed, world, 'quantized_reduce_scatter')
+    _check_mx_terms(mx_format, world, 'quantized_reduce_scatter')
     flat = tensor.view(-1)
     if world == 1 and not _single_rank_collectives:
         b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
         return flat[b_own:e_own]
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 rotation_seed=seed, clip_steps=clip_steps)
+                 rotation_seed=seed, clip_steps=clip_steps, mx_format=mx_format)
     ch = _Chunks.of(wire, flat, world)
     x_own = ch.views[rank]
     terms = _mesh_scatter(wire, ch, group, world, rank, tensor.device)
@@ -1429,6 +1578,7 @@ def quantized_all_gather(
     rotation_seed: Optional[int] = None,
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
+    mx_format: Optional[str] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1456,9 +1606,14 @@ def quantized_all_gather(
     ``clip_steps`` (as in ``quantized_reduce_scatter``): step 1 becomes ``quantize_grouped_clipped`` on the rank's own chunk; steps 2 and 3 are
     unchanged.  Not with ``rotation_seed``, ``error_feedback`` or ``rotated_error_feedback``.
 
+    ``mx_format`` (as in ``quantized_reduce_scatter``): step 1 is ``quantize_mx`` of the own chunk, step 3 ONE ``dequantize_mx_batch(..., 'set')``
+    launch per 16 chunks.
+
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
     _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
+    _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
+                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
@@ -1467,7 +1622,7 @@ def quantized_all_gather(
     if world == 1 and not _single_rank_collectives:
         return tensor
     wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
-                 rotation_seed=seed, clip_steps=clip_steps)
+                 rotation_seed=seed, clip_steps=clip_steps, mx_format=mx_format)
     ch = _Chunks.of(wire, tensor.view(-1), world)
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)
     if ch.views[rank].numel():

@@ -789,6 +789,91 @@ def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor, *, format: str, dty
     return out
 
 
+def _check_mx_terms(terms, numel: int, format: str, device) -> None:
+    """``terms``: a list of (codes, scales) of ``numel`` elements each, as ``dequantize_mx`` takes them."""
+    _require(isinstance(terms, (list, tuple)), 'terms must be a list of (codes, scales)')
+    ncodes, nscales = mx_nbytes(numel, format)
+    for i, term in enumerate(terms):
+        _require(isinstance(term, (list, tuple)) and len(term) == 2, f'terms[{i}] must be (codes, scales)')
+        _check_mx_bytes(term[0], ncodes, f'terms[{i}] codes')
+        _check_mx_bytes(term[1], nscales, f'terms[{i}] scales')
+        _require(term[0].device == device and term[1].device == device, f'terms[{i}] must live on {device}')
+
+
+def quantize_mx_batch(tensors, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None):
+    """``quantize_mx`` of every tensor of a list (one float dtype, one device) with ONE launch per 16 tensors
+    (piquant_hip_quantize_mx_batch); returns the list of (codes, scales), each the bytes of the single call.  Empty tensors take no part."""
+    _check_mx_format(format)
+    _require(isinstance(tensors, (list, tuple)), 'tensors must be a list of tensors')
+    for t in tensors:
+        _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, 'every tensor must be a float32 or bfloat16 tensor')
+        _require(t.dtype == tensors[0].dtype and t.device == tensors[0].device, 'the tensors of a batch share one dtype and one device')
+        _check_float_input(t)
+    if not tensors:
+        return []
+    xs = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    outs = [tuple(torch.empty(n, dtype=torch.uint8, device=x.device) for n in mx_nbytes(x.numel(), format)) for x in xs]
+    _ctx_for(xs[0], ctx).quantize_mx_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [o[0].data_ptr() for o in outs],
+                                               [o[1].data_ptr() for o in outs], [x.numel() for x in xs], MX_FORMATS[format], _device_ptrs=True)
+    return outs
+
+
+def dequantize_mx_batch(terms, outs, *, format: str, reduce_op: str = 'set', ctx: Optional[Context] = None):
+    """``dequantize_mx(terms[i], out=outs[i], reduce_op=...)`` for every i with ONE launch per 16 members (piquant_hip_dequantize_mx_batch):
+    ``terms`` is a list of (codes, scales), ``outs`` the contiguous float32 / bfloat16 tensors (one dtype, one device) that are stored into or
+    added to; their element counts decide how many codes are read.  Returns ``outs``."""
+    _check_mx_format(format)
+    _require(isinstance(terms, (list, tuple)) and isinstance(outs, (list, tuple)) and len(terms) == len(outs), 'terms and outs must be lists of one length')
+    if not outs:
+        return outs
+    _check_modes(float_dtype=outs[0].dtype, reduce_op=reduce_op)
+    for term, out in zip(terms, outs):
+        _require(isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and out.dtype == outs[0].dtype and out.device == outs[0].device,
+                 'outs must be contiguous ROCm device tensors of one float dtype on one device')
+        _check_mx_terms([term], out.numel(), format, out.device)
+    _ctx_for(outs[0], ctx).dequantize_mx_batch_ptr([t[0].data_ptr() for t in terms], [t[1].data_ptr() for t in terms], [o.data_ptr() for o in outs],
+                                                   torch_to_piquant_dtype(outs[0].dtype), [o.numel() for o in outs], MX_FORMATS[format],
+                                                   _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return outs
+
+
+def reduce_quantize_mx(acc: torch.Tensor, terms, *, format: str, out=None, ctx: Optional[Context] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mx(acc + sum_i dequantize_mx(terms[i]))`` in ONE launch (piquant_hip_reduce_quantize_mx): bit for bit ``dequantize_mx(terms[i],
+    reduce_op='add')`` into a copy of ``acc`` for every i in order -- the sum rounded to ``acc``'s dtype after each term -- followed by
+    ``quantize_mx`` of the copy.  ``acc`` is not written.  ``terms`` is a list of (codes, scales) of ``acc.numel()`` elements in ``format``, at
+    most 16 (ValueError); none: ``quantize_mx(acc)``.  ``out``: None, or the (codes, scales) to write.  Returns (codes, scales)."""
+    _check_mx_format(format)
+    _require(isinstance(acc, torch.Tensor) and acc.dtype in _DEQUANT_TYPES, 'acc must be a float32 or bfloat16 tensor')
+    _check_float_input(acc)
+    _require(acc.is_cuda, 'reduce_quantize_mx needs a ROCm device tensor')
+    _check_mx_terms(terms, acc.numel(), format, acc.device)
+    _require(len(terms) <= 16, f'reduce_quantize_mx takes at most 16 terms, got {len(terms)}')
+    if out is None:
+        out = tuple(torch.empty(n, dtype=torch.uint8, device=acc.device) for n in mx_nbytes(acc.numel(), format))
+    else:
+        _check_mx_terms([out], acc.numel(), format, acc.device)
+    if not acc.is_contiguous():
+        acc = acc.contiguous()
+    _ctx_for(acc, ctx).reduce_quantize_mx_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), [t[0].data_ptr() for t in terms],
+                                              [t[1].data_ptr() for t in terms], out[0].data_ptr(), out[1].data_ptr(), acc.numel(), MX_FORMATS[format],
+                                              _device_ptrs=True)
+    return out[0], out[1]
+
+
+def dequantize_sum_mx(terms, *, format: str, out: torch.Tensor, reduce_op: str = 'set', ctx: Optional[Context] = None) -> torch.Tensor:
+    """``out (reduce_op)= sum_i dequantize_mx(terms[i])`` with one launch per 16 terms and one pass over ``out``
+    (piquant_hip_dequantize_sum_mx): the bytes of ``dequantize_mx(terms[0], out=out, reduce_op=reduce_op)`` followed by
+    ``dequantize_mx(terms[i], out=out, reduce_op='add')`` for the others, in order.  'set' never reads ``out``.  At least one term."""
+    _check_mx_format(format)
+    _require(isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous(), 'out must be a contiguous ROCm device tensor')
+    _check_modes(float_dtype=out.dtype, reduce_op=reduce_op)
+    _check_mx_terms(terms, out.numel(), format, out.device)
+    _require(len(terms) >= 1, 'dequantize_sum_mx needs at least one term')
+    _ctx_for(out, ctx).dequantize_sum_mx_ptr([t[0].data_ptr() for t in terms], [t[1].data_ptr() for t in terms], out.data_ptr(),
+                                             torch_to_piquant_dtype(out.dtype), out.numel(), MX_FORMATS[format], _REDUCE_OPS[reduce_op], _device_ptrs=True)
+    return out
+
+
 def _check_seed(seed) -> int:
     """The rotation's seed: any Python int, taken modulo 2^64 (``_NA``: the call was made without one)."""
     _require(seed is not _NA, 'seed= is required: the rotation is defined by it, and the inverse needs the same one')

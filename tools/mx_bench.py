@@ -10,6 +10,15 @@ quantize_uniform; dequantize_mx SET likewise.  Each row gives us per call, the a
 comparator's own spread (max - min over its windows).  Writes profiles/mx_bench.json.
 
     python tools/mx_bench.py [--windows 7] [--rotate-gb 3.3] [--out FILE]
+
+--rows wire measures the MX wire's fused calls instead, each next to its composition of public calls in the same run (same protocol; the terms'
+records rotate too) and writes profiles/mx_wire_bench.json: reduce_quantize_mx (float32 + 1 / 7 terms -> FP8 and FP4, bfloat16 + 1 / 7 terms -> FP4)
+against dequantize_mx ADD per term + quantize_mx, dequantize_sum_mx (float32 = / += 1 / 7 terms in both formats, bfloat16 += 7 FP4 terms) against
+dequantize_mx per term, the 7-member quantize batch and the 8-member dequantize batch of numel / 8 against loops of single launches, and the
+same-width grouped fused call at G = 32 as comparator.  A row gives fused and composition us, their ratio, the ratio of their algorithmic bytes and
+whether fused / composition <= 1.15 x byte ratio ("met" / "missed"), with the windows of both.
+
+    python tools/mx_bench.py --rows wire [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -68,12 +77,138 @@ def judge(rows, res, mx_row, comparator):
     rows.append(mx_row)
 
 
+def wire_row(rows, kind, pair, res, fused_bytes, comp_bytes):
+    (us_f, s_f), (us_c, s_c) = res["fused"], res["composition"]
+    ratio, byte_ratio = us_f / us_c, fused_bytes / comp_bytes
+    r = {"kind": kind, "pair": pair, "fused_us": round(us_f, 3), "composition_us": round(us_c, 3), "ratio": round(ratio, 3), "byte_ratio": round(byte_ratio, 3),
+         "target": "met" if ratio <= 1.15 * byte_ratio else "missed", "fused_bytes": int(fused_bytes), "composition_bytes": int(comp_bytes),
+         "fused_windows_us": [round(v, 3) for v in s_f], "composition_windows_us": [round(v, 3) for v in s_c]}
+    if "grouped" in res:
+        r["grouped_us"], r["grouped_windows_us"] = round(res["grouped"][0], 3), [round(v, 3) for v in res["grouped"][1]]
+    print(f"{kind:20s} {pair:26s} fused {us_f:8.2f} us  composition {us_c:8.2f} us  ratio {ratio:.3f}  bytes {byte_ratio:.3f}  {r['target']}", flush=True)
+    rows.append(r)
+
+
+def wire_main(args):
+    """The fused calls of the MX wire against their compositions (module docstring)."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    ctx = piquant.Context.get(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_blocking(False)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    SET, ADD, NEAREST = piquant.ReduceOp.SET, piquant.ReduceOp.ADD, piquant.RoundMode.NEAREST
+    ng = pt.num_groups(NUMEL, G)
+    rows = []
+    reduce_rows = [("f32", "fp8_e4m3", 1), ("f32", "fp8_e4m3", 7), ("f32", "fp4_e2m1", 1), ("f32", "fp4_e2m1", 7), ("bf16", "fp4_e2m1", 1), ("bf16", "fp4_e2m1", 7)]
+    sum_rows = [("f32", fmt, op, k) for fmt in WIDTH for op in (SET, ADD) for k in (1, 7)] + [("bf16", "fp4_e2m1", ADD, 7)]
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
+        per_window = max(nbuf, 16)
+        xs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=gen).to(tdt) for _ in range(nbuf)]
+        ys = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        for fmt, (qname, qdt) in WIDTH.items():
+            f, (ncodes, nblocks) = pt.MX_FORMATS[fmt], pt.mx_nbytes(NUMEL, fmt)
+            counts = sorted({k for fn, fm, k in reduce_rows if (fn, fm) == (fname, fmt)} | {k for fn, fm, _, k in sum_rows if (fn, fm) == (fname, fmt)})
+            if not counts:
+                continue
+            nset = max(3, int(args.rotate_gb * 1e9 / (max(counts) * ncodes)) + 1)   # term sets: rotated like the floats
+            tc = [[torch.empty(ncodes, dtype=torch.uint8, device=dev) for _ in range(max(counts))] for _ in range(nset)]
+            ts = [[torch.empty(nblocks, dtype=torch.uint8, device=dev) for _ in range(max(counts))] for _ in range(nset)]
+            gs = [[torch.empty(ng, dtype=torch.float32, device=dev) for _ in range(max(counts))] for _ in range(nset)]
+            gz = [[torch.empty(ng, dtype=torch.uint8, device=dev) for _ in range(max(counts))] for _ in range(nset)]
+            for j in range(nset):   # valid records of both wires in the same code buffers' width: MX records for the MX calls, parameters for the grouped
+                for t in range(max(counts)):
+                    ctx.quantize_mx_ptr(xs[(j + t) % nbuf].data_ptr(), fdt, tc[j][t].data_ptr(), ts[j][t].data_ptr(), NUMEL, f, _device_ptrs=True)
+                    gs[j][t].fill_(0.01)
+                    gz[j][t].fill_(7)
+            oc, os_ = torch.empty(ncodes, dtype=torch.uint8, device=dev), torch.empty(nblocks, dtype=torch.uint8, device=dev)
+            osc, ozp = torch.empty(ng, dtype=torch.float32, device=dev), torch.empty(ng, dtype=torch.uint8, device=dev)
+            ptrs = lambda bufs, k: [b.data_ptr() for b in bufs[:k]]   # noqa: E731
+
+            def composition_reduce(i, k):
+                ys[i % nbuf].copy_(xs[i % nbuf])                      # the composition's copy of acc: acc itself is not written
+                for t in range(k):
+                    ctx.dequantize_mx_ptr(tc[i % nset][t].data_ptr(), ts[i % nset][t].data_ptr(), ys[i % nbuf].data_ptr(), fdt, NUMEL, f, ADD, _device_ptrs=True)
+                ctx.quantize_mx_ptr(ys[i % nbuf].data_ptr(), fdt, oc.data_ptr(), os_.data_ptr(), NUMEL, f, _device_ptrs=True)
+
+            def composition_sum(i, k, op):
+                for t in range(k):
+                    ctx.dequantize_mx_ptr(tc[i % nset][t].data_ptr(), ts[i % nset][t].data_ptr(), ys[i % nbuf].data_ptr(), fdt, NUMEL, f, op if t == 0 else ADD,
+                                          _device_ptrs=True)
+
+            term = ncodes + nblocks
+            for k in [k for fn, fm, k in reduce_rows if (fn, fm) == (fname, fmt)]:
+                calls = {
+                    "fused": lambda i, k=k: ctx.reduce_quantize_mx_ptr(xs[i % nbuf].data_ptr(), fdt, ptrs(tc[i % nset], k), ptrs(ts[i % nset], k), oc.data_ptr(),
+                                                                      os_.data_ptr(), NUMEL, f, _device_ptrs=True),
+                    "composition": lambda i, k=k: composition_reduce(i, k),
+                    "grouped": lambda i, k=k: ctx.reduce_quantize_grouped_ptr(ys[i % nbuf].data_ptr(), fdt, ptrs(tc[i % nset], k), ptrs(gs[i % nset], k),
+                                                                            ptrs(gz[i % nset], k), oc.data_ptr(), qdt, NUMEL, G, osc.data_ptr(), ozp.data_ptr(),
+                                                                            NEAREST, _device_ptrs=True),
+                }
+                res = timed_alternating(calls, nbuf * nset, args.windows, per_window, stream)
+                fl = NUMEL * esize
+                wire_row(rows, "reduce_quantize_mx", f"{fname} + {k} -> {fmt}", res, fl + (k + 1) * term, 2 * fl + k * (term + 2 * fl) + fl + term)
+            for op, k in [(op, k) for fn, fm, op, k in sum_rows if (fn, fm) == (fname, fmt)]:
+                calls = {
+                    "fused": lambda i, k=k, op=op: ctx.dequantize_sum_mx_ptr(ptrs(tc[i % nset], k), ptrs(ts[i % nset], k), ys[i % nbuf].data_ptr(), fdt, NUMEL, f, op,
+                                                                             _device_ptrs=True),
+                    "composition": lambda i, k=k, op=op: composition_sum(i, k, op),
+                    "grouped": lambda i, k=k, op=op: ctx.dequantize_sum_grouped_ptr(ptrs(tc[i % nset], k), qdt, ptrs(gs[i % nset], k), ptrs(gz[i % nset], k),
+                                                                                   ys[i % nbuf].data_ptr(), fdt, NUMEL, G, op, _device_ptrs=True),
+                }
+                res = timed_alternating(calls, nbuf * nset, args.windows, per_window, stream)
+                fl, add = NUMEL * esize, op == ADD
+                wire_row(rows, "dequantize_sum_mx", f"{fmt} x {k} {'+=' if add else '='} {fname}", res, k * term + (2 if add else 1) * fl,
+                         k * term + (2 * k - (0 if add else 1)) * fl)
+            if fname == "f32":   # the batches: 7 / 8 members of numel / 8 against loops of single launches
+                m = NUMEL // 8
+                mc, mb = pt.mx_nbytes(m, fmt)
+                stride = -(-mb // 16) * 16                              # every member's scale bytes on a 16-byte boundary, in a buffer of their own
+                bsc = torch.empty(8 * stride, dtype=torch.uint8, device=dev)
+                cut = lambda t, n, k: [t[j * n:(j + 1) * n] for j in range(k)]   # noqa: E731
+                q = {
+                    "fused": lambda i: ctx.quantize_mx_batch_ptr(ptrs(cut(xs[i % nbuf], m, 7), 7), fdt, ptrs(cut(tc[i % nset][0], mc, 7), 7),
+                                                                 ptrs(cut(bsc, stride, 7), 7), [m] * 7, f, _device_ptrs=True),
+                    "composition": lambda i: [ctx.quantize_mx_ptr(x.data_ptr(), fdt, c.data_ptr(), sc.data_ptr(), m, f, _device_ptrs=True)
+                                              for x, c, sc in zip(cut(xs[i % nbuf], m, 7), cut(tc[i % nset][0], mc, 7), cut(bsc, stride, 7))],
+                }
+                res = timed_alternating(q, nbuf * nset, args.windows, per_window, stream)
+                wire_row(rows, "quantize_mx_batch", f"7 x {fname} -> {fmt}", res, 7 * (m * esize + mc + mb), 7 * (m * esize + mc + mb))
+                d = {
+                    "fused": lambda i: ctx.dequantize_mx_batch_ptr(ptrs(cut(tc[i % nset][0], mc, 8), 8), ptrs(cut(bsc, stride, 8), 8),
+                                                                   ptrs(cut(ys[i % nbuf], m, 8), 8), fdt, [m] * 8, f, SET, _device_ptrs=True),
+                    "composition": lambda i: [ctx.dequantize_mx_ptr(c.data_ptr(), sc.data_ptr(), y.data_ptr(), fdt, m, f, SET, _device_ptrs=True)
+                                              for c, sc, y in zip(cut(tc[i % nset][0], mc, 8), cut(bsc, stride, 8), cut(ys[i % nbuf], m, 8))],
+                }
+                res = timed_alternating(d, nbuf * nset, args.windows, per_window, stream)
+                wire_row(rows, "dequantize_mx_batch", f"8 x {fmt} -> {fname}", res, 8 * (m * esize + mc + mb), 8 * (m * esize + mc + mb))
+            del tc, ts, gs, gz
+        del xs, ys
+        torch.cuda.empty_cache()
+    out = {"numel": NUMEL, "device": torch.cuda.get_device_name(0), "windows": args.windows, "rotate_gb": args.rotate_gb, "group_size": G,
+           "command": "python tools/mx_bench.py --rows wire",
+           "protocol": "alternating windows of back-to-back calls, HIP events, median over windows; rotated float buffers and term sets; target: fused / "
+                       "composition <= 1.15 x byte ratio",
+           "not_measured": "other sizes, the guarded kernels, more than one GPU", "rows": rows}
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print(f"wrote {args.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", choices=("calls", "wire"), default="calls")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "mx_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("mx_wire_bench.json" if args.rows == "wire" else "mx_bench.json"))
+    if args.rows == "wire":
+        return wire_main(args)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ctx = piquant.Context.get(0)
