@@ -1,30 +1,18 @@
 // The group-wise entry points of include/piquant_hip.h: plain, batch, fused reduce, error feedback (EF), reduce + EF, EF with a float32 residual
-// for a bfloat16 tensor, quantize-dequantize, the three calls of the randomized Hadamard rotation, the reduce and dequantize-sum in the rotated domain, the two error-feedback calls of the rotated domain, the batches of the rotated quantize, dequantize and error-feedback quantize, and the quantize with a per-group clip search and its batch.  All are stream-ordered, take device (or pinned) buffers only and read the same way: validate, lock and guard, resolve,
-// draw the round mode ONCE, open the scopes, launch through the helpers below, wait.  The rules the entries share are stated on the helper that
-// owns them.
-#include "context.hpp"
+// for a bfloat16 tensor, quantize-dequantize, the calls of the randomized Hadamard rotation (single, batch, reduce, dequantize-sum, and error feedback
+// in the rotated domain) and the quantize with a per-group clip search.  All are stream-ordered, take device (or pinned) buffers only and read as
+// capi_frame.hpp says: validate, take the CallLock, resolve, draw the round mode ONCE, end in one run_call.  An extern "C" entry does its own type
+// checks and forwards to the body of its shape; the rules the entries share are stated on the helper or body that owns them.
+#include "capi_frame.hpp"
 
 using namespace pq;
 
 namespace {
 
-// An entry point and, for a list argument, the index in the list: what every message names.
-struct Where {
-    const char* entry;
-    long index = -1;
-};
-
-[[noreturn]] void bad(const Where& w, const char* what) {
-    if (w.index < 0) panic("%s: %s", w.entry, what);
-    panic("%s: %s (list index %ld)", w.entry, what, w.index);
-}
-
 void check_group_size(size_t group_size, const char* entry = nullptr) {
     if (group_size < static_cast<size_t>(kGroupedMinG) || group_size > static_cast<size_t>(kGroupedMaxG) || (group_size & (group_size - 1)) != 0)
         panic("%s%sgroup size %zu is not a power of two in [%d, %d]", entry ? entry : "", entry ? ": " : "", group_size, kGroupedMinG, kGroupedMaxG);
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // What needs neither the lock nor the device: no NULL among one tensor's buffers (the residual only where the call has one), scales 4-byte aligned.
 void check_tensor(const Where& w, bool ef, const void* in, const void* residual, const void* out, const float* scales, const uint8_t* zero_points) {
@@ -40,14 +28,8 @@ void check_requant_tensor(const Where& w, bool params_given, const void* in, con
     if (reinterpret_cast<uintptr_t>(scales) % 4 != 0) bad(w, "scales must be 4-byte aligned");
 }
 
-// A buffer as the kernels take it: pageable host memory has no group-wise path.
-void* device_ptr(const Where& w, const Resolved& r) {
-    if (r.pageable) bad(w, "device (or pinned) buffers are needed");
-    return r.dev;
-}
-
-// One tensor's buffers, resolved (caller holds ctx->mu); a NULL residual or out, or a NULL parameter pair (check_requant_tensor), is left out.  The parameter arrays are always classified: the
-// context's assume-device mode speaks for the tensors the caller passes, not for them.
+// One tensor's buffers, resolved (caller holds the CallLock); a NULL residual or out, or a NULL parameter pair (check_requant_tensor), is left out.
+// The parameter arrays are always classified: the context's assume-device mode speaks for the tensors the caller passes, not for them.
 GroupedTensor resolve_tensor(const piquant_context_t* ctx, const Where& w, const void* in, const void* residual, const void* out, const float* scales,
                              const uint8_t* zero_points, size_t numel) {
     GroupedTensor t {};
@@ -60,25 +42,33 @@ GroupedTensor resolve_tensor(const piquant_context_t* ctx, const Where& w, const
     return t;
 }
 
-// The members of a batch, in order: an empty one is skipped, one that `streams` turns down runs `alone` in its place in the sequence (the guarded
-// kernel, same bytes), the others collect in `b`, which is flushed every kGroupedBatchMaxTensors members and at the end (the batch launchers return
-// at count == 0).  member(i) checks and resolves member i.
-template <class Batch, class Member, class Streams, class Alone, class Flush>
-void run_batch(Batch& b, const size_t* numels, size_t count, Member member, Streams streams, Alone alone, Flush flush) {
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        const GroupedTensor t = member(i);
-        if (!streams(t)) {
-            alone(t);
-            continue;
-        }
-        b.t[b.count] = t;
-        if (++b.count == kGroupedBatchMaxTensors) {
-            flush();
-            b.count = 0;
-        }
-    }
-    flush();
+// The residual of an error-feedback call: of the tensor's type, or float32 for a bfloat16 tensor (the kernels of kernels_grouped_ef_f32r.hip).
+enum class Residual { Same, F32 };
+
+Residual residual_kind(const char* entry, piquant_dtype_t dtype_in, piquant_dtype_t dtype_residual) {
+    if (dtype_residual == dtype_in) return Residual::Same;
+    if (dtype_in == PIQUANT_DTYPE_BF16 && dtype_residual == PIQUANT_DTYPE_F32) return Residual::F32;
+    panic("%s: a %s residual for a %s tensor (the tensor's type, or float32 for a bfloat16 tensor, is needed)", entry, dtype_of(dtype_residual).name,
+          dtype_of(dtype_in).name);
+}
+
+// When a tensor takes its call's streaming kernel; anything else runs through the guarded one, the same bytes.  One predicate per rule:
+// in and out 16-byte aligned -- every call without a residual;
+bool streams_in_out(const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); }
+
+// residual and out 16-byte aligned and the tensor as its lane-rows are loaded, 16 bytes or 8 (`rows8`: a row is four elements of two bytes) -- the
+// error-feedback calls, which differ in when the rows are the short ones:
+bool ef_rows_stream(const GroupedTensor& t, bool rows8) {
+    return (reinterpret_cast<uintptr_t>(t.in) & (rows8 ? 7u : 15u)) == 0 && aligned16(t.residual) && aligned16(t.out);
+}
+// a bfloat16 tensor with a float32 residual (a residual of the tensor's type is loaded 16 bytes a lane whatever the type);
+bool ef_streams(Residual k, const GroupedTensor& t) { return ef_rows_stream(t, k == Residual::F32); }
+// in the rotated domain the residual is always float32: any tensor that is not.
+bool rotated_ef_streams(piquant_dtype_t dtype_in, const GroupedTensor& t) { return ef_rows_stream(t, dtype_in != PIQUANT_DTYPE_F32); }
+
+// Types that differ leave room for a tensor or a residual that is not even aligned to its element: no kernel takes that.
+void check_ef_elements(const Where& w, const GroupedTensor& t, piquant_dtype_t dtype_in) {
+    check_element_aligned(w, "the tensor or its residual", t.in, dtype_in, t.residual, PIQUANT_DTYPE_F32);
 }
 
 // The terms of a reduce, each resolved as the grouped dequantize ADD that adds it into acc takes it, and whether all of them are 16-byte aligned.
@@ -116,29 +106,6 @@ size_t fused_from(size_t count, bool all_aligned) {
     return count > static_cast<size_t>(kGroupedReduceMaxInputs) ? count - kGroupedReduceMaxInputs : 0;
 }
 
-// The residual of an error-feedback call: of the tensor's type, or float32 for a bfloat16 tensor (the kernels of kernels_grouped_ef_f32r.hip).
-enum class Residual { Same, F32 };
-
-Residual residual_kind(const char* entry, piquant_dtype_t dtype_in, piquant_dtype_t dtype_residual) {
-    if (dtype_residual == dtype_in) return Residual::Same;
-    if (dtype_in == PIQUANT_DTYPE_BF16 && dtype_residual == PIQUANT_DTYPE_F32) return Residual::F32;
-    panic("%s: a %s residual for a %s tensor (the tensor's type, or float32 for a bfloat16 tensor, is needed)", entry, dtype_of(dtype_residual).name,
-          dtype_of(dtype_in).name);
-}
-
-// The streaming EF kernels' rule: tensor, residual and output 16-byte aligned; with a float32 residual the bfloat16 tensor needs 8 bytes only
-// (its lane-row is four elements).
-bool ef_streams(Residual k, const GroupedTensor& t) {
-    const bool in_ok = k == Residual::F32 ? (reinterpret_cast<uintptr_t>(t.in) & 7u) == 0 : aligned16(t.in);
-    return in_ok && aligned16(t.residual) && aligned16(t.out);
-}
-
-// Types that differ leave room for a tensor or a residual that is not even aligned to its element: no kernel takes that.
-void check_ef_elements(Residual k, const Where& w, const GroupedTensor& t) {
-    if (k == Residual::F32 && (reinterpret_cast<uintptr_t>(t.in) % 2 != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0))
-        bad(w, "the tensor or its residual is not aligned to its element size");
-}
-
 void launch_ef_batch(Residual k, const GroupedEfBatchLaunch& b, hipStream_t stream) {
     if (k == Residual::F32) launch_quantize_grouped_ef_f32r_batch(b, stream);
     else launch_quantize_grouped_ef_batch(b, stream);
@@ -155,32 +122,104 @@ void ef_quantize_one(piquant_context_t* ctx, Residual k, const GroupedEfLaunch& 
     else launch_ef_guarded(k, q, ctx->stream, ctx->num_cu);
 }
 
+// Every quantize batch behind its type and group-size checks: plain, rotated, clipped and the error-feedback ones (`residuals` a list; nullptr
+// otherwise).  ONE threshold (or per-element seed and base) for the whole batch, drawn whenever count > 0 -- also when every member is empty.
+// What an entry brings: check(w, t, i), what it checks or adds once member i is resolved; its alignment rule; alone(q) and flush(b), the guarded
+// and the batch launch; and device_params, as run_call takes it.
+template <class Residuals, class Check, class Streams, class Alone, class Flush>
+void quantize_batch(piquant_context_t* ctx, const char* entry, const void* const* inputs, piquant_dtype_t dtype_in, Residuals residuals, void* const* outputs,
+                    piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales, uint8_t* const* zero_points, size_t count,
+                    bool params_given, piquant_round_mode_t mode, bool device_params, Check check, Streams streams, Alone alone, Flush flush) {
+    constexpr bool ef = !std::is_null_pointer_v<Residuals>;
+    if (count == 0) return;   // before a stochastic threshold would be drawn
+    bool lists = inputs && outputs && numels && scales && zero_points;
+    if constexpr (ef) lists = lists && residuals;
+    if (!lists) panic("%s: NULL argument", entry);
+    const CallLock lock(ctx);
+    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given, round_mode_fields(ctx, mode)}, {}, 0};
+    run_call(ctx, device_params, [&] {
+        run_batch(
+            b, numels, count,
+            [&](size_t i) {
+                const Where w {entry, static_cast<long>(i)};
+                const void* residual = nullptr;
+                if constexpr (ef) residual = residuals[i];
+                check_tensor(w, ef, inputs[i], residual, outputs[i], scales[i], zero_points[i]);
+                GroupedTensor t = resolve_tensor(ctx, w, inputs[i], residual, outputs[i], scales[i], zero_points[i], numels[i]);
+                check(w, t, i);
+                return t;
+            },
+            streams, [&](const GroupedTensor& t) { alone(GroupedQuantLaunch {t, b}); }, [&] { flush(b); });
+    });
+}
+
 // piquant_hip_quantize_grouped_ef_batch and the float32-residual path of piquant_hip_quantize_grouped_ef_mixed_batch, behind their type checks.
-// ONE threshold (or per-element seed and base) for the whole batch, drawn whenever count > 0 -- also when every member is empty.
 void quantize_grouped_ef_batch(piquant_context_t* ctx, const char* entry, Residual k, const void* const* inputs, piquant_dtype_t dtype_in,
                                void* const* residuals, void* const* outputs, piquant_dtype_t dtype_out, const size_t* numels, size_t group_size,
                                float* const* scales, uint8_t* const* zero_points, size_t count, piquant_round_mode_t mode) {
     check_group_size(group_size);
-    if (count == 0) return;   // before a stochastic threshold would be drawn
-    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    GroupedEfBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, true, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i]);
-            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i], numels[i]);
-            check_ef_elements(k, w, t);
-            return t;
+    quantize_batch(
+        ctx, entry, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, false, mode,
+        true,   // the residual is written by the previous step's call: always behind it
+        [&](const Where& w, const GroupedTensor& t, size_t) {
+            if (k == Residual::F32) check_ef_elements(w, t, dtype_in);
         },
         [&](const GroupedTensor& t) { return ef_streams(k, t); },
-        [&](const GroupedTensor& t) { launch_ef_guarded(k, GroupedEfLaunch {t, b}, ctx->stream, ctx->num_cu); },
-        [&] { launch_ef_batch(k, b, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+        [&](const GroupedEfLaunch& q) { launch_ef_guarded(k, q, ctx->stream, ctx->num_cu); },
+        [&](const GroupedEfBatchLaunch& b) { launch_ef_batch(k, b, ctx->stream); });
+}
+
+// The two dequantize batches behind their type and group-size checks; check_out: the rotated one, whose kernels write whole elements of `out`.
+template <class Alone, class Flush>
+void dequantize_batch(piquant_context_t* ctx, const char* entry, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
+                      piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, const float* const* scales, const uint8_t* const* zero_points,
+                      size_t count, piquant_reduce_op_t op, bool check_out, Alone alone, Flush flush) {
+    if (count == 0) return;
+    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
+    const CallLock lock(ctx);
+    GroupedDequantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, to_op(op)}, {}, 0};
+    // the parameters are written by whatever was enqueued just before
+    run_call(ctx, true, [&] {
+        run_batch(
+            b, numels, count,
+            [&](size_t i) {
+                const Where w {entry, static_cast<long>(i)};
+                check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
+                const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
+                if (check_out) check_element_aligned(w, "out", t.out, dtype_out);
+                return t;
+            },
+            streams_in_out, [&](const GroupedTensor& t) { alone(GroupedDequantLaunch {t, b}); }, [&] { flush(b); });
+    });
+}
+
+// The two single quantize calls behind their type and group-size checks; check_in: the rotated one.  Given parameters are written by whatever was
+// enqueued just before, so they are the call's device_params.
+template <class Launch>
+void quantize_single(piquant_context_t* ctx, const Where& w, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                     size_t group_size, float* scales, uint8_t* zero_points, bool params_given, piquant_round_mode_t mode, bool check_in, Launch launch) {
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    const CallLock lock(ctx);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    if (check_in) check_element_aligned(w, "in", t.in, dtype_in);
+    // the call's one threshold (or the per-element seed and base), as quantize_uniform draws it
+    const GroupedQuantLaunch q {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given, round_mode_fields(ctx, mode)}};
+    run_call(ctx, params_given, [&] { launch(q); });
+}
+
+// The two single dequantize calls, likewise; check_out: the rotated one.
+template <class Launch>
+void dequantize_single(piquant_context_t* ctx, const Where& w, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
+                       size_t group_size, const float* scales, const uint8_t* zero_points, piquant_reduce_op_t op, bool check_out, Launch launch) {
+    if (numel == 0) return;
+    check_tensor(w, false, in, nullptr, out, scales, zero_points);
+    const CallLock lock(ctx);
+    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
+    if (check_out) check_element_aligned(w, "out", t.out, dtype_out);
+    const GroupedDequantLaunch d {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, to_op(op)}};
+    // the parameters are written by whatever was enqueued just before
+    run_call(ctx, true, [&] { launch(d); });
 }
 
 // The three reduce entries behind their type checks: out = quantize_grouped(acc + terms [+ residual]), with error feedback when `ef`.
@@ -196,29 +235,59 @@ void reduce_quantize_grouped(piquant_context_t* ctx, const char* entry, bool ef,
     const Where w {entry};
     check_tensor(w, ef, acc, residual, out, scales, zero_points);
     if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
+    const CallLock lock(ctx);
     const GroupedTensor t = resolve_tensor(ctx, w, acc, ef ? residual : nullptr, out, scales, zero_points, numel);
-    if (ef) check_ef_elements(k, w, t);
+    if (ef && k == Residual::F32) check_ef_elements(w, t, dtype_acc);
     const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, const_cast<void*>(t.in) /* acc */, numel);
-    const bool aligned = terms.aligned && (ef ? ef_streams(k, t) : aligned16(t.in) && aligned16(t.out));
+    const bool aligned = terms.aligned && (ef ? ef_streams(k, t) : streams_in_out(t));
     const GroupedQuantCall call {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // terms, parameters and residual are written by what was enqueued before: always behind it
-    const size_t first = fused_from(count, aligned);
-    add_terms(ctx, terms, 0, first, GroupedDequantCall {call.group_size, dtype_out, dtype_acc, OP_ADD});
-    if (first < count) {
-        GroupedReduceLaunch r {t, call, {}, static_cast<int>(count - first)};
-        std::copy(terms.term.begin() + static_cast<std::ptrdiff_t>(first), terms.term.end(), r.term);
-        if (!ef) launch_reduce_quantize_grouped(r, ctx->stream);
-        else if (k == Residual::F32) launch_reduce_quantize_grouped_ef_f32r(r, ctx->stream);
-        else launch_reduce_quantize_grouped_ef(r, ctx->stream);
-    } else if (ef) {   // no terms, or the two-step form: quantize_grouped_ef(acc, residual)
-        ef_quantize_one(ctx, k, GroupedEfLaunch {t, call});
-    } else {           // quantize_grouped(acc)
-        launch_quantize_grouped(GroupedQuantLaunch {t, call}, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    // terms, parameters and residual are written by what was enqueued before: always behind it
+    run_call(ctx, true, [&] {
+        const size_t first = fused_from(count, aligned);
+        add_terms(ctx, terms, 0, first, GroupedDequantCall {call.group_size, dtype_out, dtype_acc, OP_ADD});
+        if (first < count) {
+            GroupedReduceLaunch r {t, call, {}, static_cast<int>(count - first)};
+            std::copy(terms.term.begin() + static_cast<std::ptrdiff_t>(first), terms.term.end(), r.term);
+            if (!ef) launch_reduce_quantize_grouped(r, ctx->stream);
+            else if (k == Residual::F32) launch_reduce_quantize_grouped_ef_f32r(r, ctx->stream);
+            else launch_reduce_quantize_grouped_ef(r, ctx->stream);
+        } else if (ef) {   // no terms, or the two-step form: quantize_grouped_ef(acc, residual)
+            ef_quantize_one(ctx, k, GroupedEfLaunch {t, call});
+        } else {           // quantize_grouped(acc)
+            launch_quantize_grouped(GroupedQuantLaunch {t, call}, ctx->stream, ctx->num_cu);
+        }
+    });
+}
+
+// The quantizing step of a grouped collective in the rotated domain, behind its type checks: ONE launch, streaming when acc, out and every term's
+// packed bytes are aligned as the kernel loads them, guarded otherwise.  More than kGroupedReduceMaxInputs terms abort: the float32 running sum has
+// nowhere to be spilled to.  `ef`: with a float32 residual of rotated values (grouped_rot_ef_kernels.hpp), where the reduce without terms IS the
+// quantize and launches its kernel.
+void reduce_quantize_grouped_rotated(piquant_context_t* ctx, const char* entry, bool ef, const void* acc, piquant_dtype_t dtype_acc, float* residual,
+                                     const void* const* inputs, const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count,
+                                     void* out, piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
+                                     uint64_t seed, piquant_round_mode_t mode) {
+    check_group_size(group_size, entry);
+    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
+    if (numel == 0) return;   // before a stochastic threshold would be drawn
+    const Where w {entry};
+    check_tensor(w, ef, acc, residual, out, scales, zero_points);
+    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
+    const CallLock lock(ctx);
+    const GroupedTensor t = resolve_tensor(ctx, w, acc, ef ? residual : nullptr, out, scales, zero_points, numel);
+    if (ef) check_ef_elements(w, t, dtype_acc);
+    else check_element_aligned(w, "acc", t.in, dtype_acc);
+    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, t.out, numel);
+    const bool guarded = !(terms.aligned && (ef ? rotated_ef_streams(dtype_acc, t) : streams_in_out(t)));
+    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
+    GroupedReduceLaunch r {t, {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)}, {}, static_cast<int>(count)};
+    std::copy(terms.term.begin(), terms.term.end(), r.term);
+    // terms, parameters and residual are written by what was enqueued before (the residual by the previous step's call): always behind it
+    run_call(ctx, true, [&] {
+        if (!ef) launch_reduce_quantize_grouped_rotated(r, seed, guarded, ctx->stream, ctx->num_cu);
+        else if (count == 0) launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, r}, seed, guarded, ctx->stream, ctx->num_cu);
+        else launch_reduce_quantize_grouped_rotated_ef(r, seed, guarded, ctx->stream, ctx->num_cu);
+    });
 }
 
 // Both quantize-dequantize entries behind their NULL-context check; `single`: the one tensor of piquant_hip_quantize_dequantize_grouped, whose messages
@@ -234,30 +303,25 @@ void quantize_dequantize_grouped_batch(piquant_context_t* ctx, const char* entry
     if (count == 0) return;   // before a stochastic threshold would be drawn
     const bool no_params = !scales && !zero_points;   // NULL lists: no parameters wanted
     if (!inputs || !outputs || !numels || (!scales != !zero_points) || (no_params && params_given != 0)) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const bool add = op == PIQUANT_REDUCE_OP_ADD;
-    GroupedRequantBatchLaunch b {{{static_cast<int64_t>(group_size), dtype_in_out, quant_dtype, params_given != 0, round_mode_fields(ctx, mode)},
-                                  add ? OP_ADD : OP_SET}, {}, 0};
-    const size_t esize = dtype_in_out == PIQUANT_DTYPE_F32 ? 4 : 2;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, add || b.params_given);   // the accumulator and given parameters are written by what was enqueued before
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, single ? -1 : static_cast<long>(i)};
-            float* sc = no_params ? nullptr : scales[i];
-            uint8_t* zp = no_params ? nullptr : zero_points[i];
-            check_requant_tensor(w, b.params_given, inputs[i], outputs[i], sc, zp);
-            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], sc, zp, numels[i]);
-            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0 || reinterpret_cast<uintptr_t>(t.out) % esize != 0)
-                bad(w, "in or out is not aligned to its element size");
-            return t;
-        },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_quantize_dequantize_grouped_guarded(GroupedRequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
-        [&] { launch_quantize_dequantize_grouped_batch(b, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    const CallLock lock(ctx);
+    GroupedRequantBatchLaunch b {{{static_cast<int64_t>(group_size), dtype_in_out, quant_dtype, params_given != 0, round_mode_fields(ctx, mode)}, to_op(op)}, {}, 0};
+    // the accumulator and given parameters are written by what was enqueued before
+    run_call(ctx, b.op == OP_ADD || b.params_given, [&] {
+        run_batch(
+            b, numels, count,
+            [&](size_t i) {
+                const Where w {entry, single ? -1 : static_cast<long>(i)};
+                float* sc = no_params ? nullptr : scales[i];
+                uint8_t* zp = no_params ? nullptr : zero_points[i];
+                check_requant_tensor(w, b.params_given, inputs[i], outputs[i], sc, zp);
+                const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], sc, zp, numels[i]);
+                check_element_aligned(w, "in or out", t.in, dtype_in_out, t.out, dtype_in_out);
+                return t;
+            },
+            streams_in_out,
+            [&](const GroupedTensor& t) { launch_quantize_dequantize_grouped_guarded(GroupedRequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
+            [&] { launch_quantize_dequantize_grouped_batch(b, ctx->stream); });
+    });
 }
 
 }  // namespace
@@ -270,19 +334,8 @@ void piquant_hip_quantize_grouped(piquant_context_t* ctx, const void* in, piquan
     if (!ctx) bad(w, "context is NULL");
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    check_tensor(w, false, in, nullptr, out, scales, zero_points);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
-    // the call's one threshold (or the per-element seed and base), as quantize_uniform draws it
-    const GroupedQuantLaunch q {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given != 0, round_mode_fields(ctx, mode)}};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, q.params_given);   // given parameters are written by whatever was enqueued just before
-        launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    quantize_single(ctx, w, in, dtype_in, out, dtype_out, numel, group_size, scales, zero_points, params_given != 0, mode, false,
+                    [&](const GroupedQuantLaunch& q) { launch_quantize_grouped(q, ctx->stream, ctx->num_cu); });
 }
 
 void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out, size_t numel,
@@ -291,224 +344,8 @@ void piquant_hip_dequantize_grouped(piquant_context_t* ctx, const void* in, piqu
     if (!ctx) bad(w, "context is NULL");
     check_dequant_types(dtype_in, dtype_out, op);
     check_group_size(group_size);
-    if (numel == 0) return;
-    check_tensor(w, false, in, nullptr, out, scales, zero_points);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
-    const GroupedDequantLaunch d {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-        launch_dequantize_grouped(d, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// The MX block formats (mx_kernels.hpp): fixed blocks of 32 under one E8M0 scale byte instead of groups with (scale, zero point); the same checks,
-// scopes and buffer rules as the two entries above.
-static_assert(PIQUANT_HIP_MX_FP4_E2M1 == MX_FP4_E2M1 && PIQUANT_HIP_MX_FP8_E4M3 == MX_FP8_E4M3, "piquant_hip_mx_format_t and the kernels' format codes");
-
-void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
-                             piquant_hip_mx_format_t fmt) {
-    const Where w {"piquant_hip_quantize_mx"};
-    if (!ctx) bad(w, "context is NULL");
-    if (dtype_in != PIQUANT_DTYPE_F32 && dtype_in != PIQUANT_DTYPE_BF16) bad(w, "the input must be float32 or bfloat16");
-    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
-    if (numel == 0) return;
-    if (!in || !codes || !scales) bad(w, "NULL buffer");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const MxQuantLaunch q {device_ptr(w, ctx->resolve_ptr(in)), device_ptr(w, ctx->resolve_ptr(codes)), static_cast<uint8_t*>(device_ptr(w, resolve(scales))),
-                           static_cast<int64_t>(numel), dtype_in, fmt};
-    if (reinterpret_cast<uintptr_t>(q.in) % (dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "in is not aligned to its element size");
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx);
-        launch_quantize_mx(q, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out, size_t numel,
-                               piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
-    const Where w {"piquant_hip_dequantize_mx"};
-    if (!ctx) bad(w, "context is NULL");
-    if (dtype_out != PIQUANT_DTYPE_F32 && dtype_out != PIQUANT_DTYPE_BF16) bad(w, "the output must be float32 or bfloat16");
-    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) bad(w, "the reduce op must be SET or ADD");
-    if (numel == 0) return;
-    if (!codes || !scales || !out) bad(w, "NULL buffer");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const MxDequantLaunch d {device_ptr(w, ctx->resolve_ptr(codes)), static_cast<const uint8_t*>(device_ptr(w, resolve(scales))),
-                             device_ptr(w, ctx->resolve_ptr(out)), static_cast<int64_t>(numel), dtype_out, fmt, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET};
-    if (reinterpret_cast<uintptr_t>(d.out) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the scale bytes are written by whatever was enqueued just before
-        launch_dequantize_mx(d, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// The MX wire (mx_reduce_kernels.hpp): the fused reduce, the dequantize-sum and the two batches.  What the four share: the checks of the two entries
-// above, the terms resolved once (no allocation: at most kMxMaxInputs a launch, on the stack), everything always behind what was enqueued before.
-namespace {
-
-void check_mx_call(const Where& w, const piquant_context_t* ctx, piquant_dtype_t dtype, piquant_hip_mx_format_t fmt) {
-    if (!ctx) bad(w, "context is NULL");
-    if (dtype != PIQUANT_DTYPE_F32 && dtype != PIQUANT_DTYPE_BF16) bad(w, "the float type must be float32 or bfloat16");
-    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
-}
-
-void* mx_float_ptr(const piquant_context_t* ctx, const Where& w, const void* p, piquant_dtype_t dtype) {
-    void* dev = device_ptr(w, ctx->resolve_ptr(p));
-    if (reinterpret_cast<uintptr_t>(dev) % (dtype == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "the float tensor is not aligned to its element size");
-    return dev;
-}
-
-// terms [from, from + n) into `term`; false when one of their buffers is not 16-byte aligned
-bool resolve_mx_terms(const piquant_context_t* ctx, const char* entry, const void* const* codes, const uint8_t* const* scales, size_t from, size_t n,
-                      MxTerm* term) {
-    bool aligned = true;
-    for (size_t i = 0; i < n; ++i) {
-        const Where w {entry, static_cast<long>(from + i)};
-        if (!codes[from + i] || !scales[from + i]) bad(w, "NULL buffer");
-        term[i] = MxTerm {device_ptr(w, ctx->resolve_ptr(codes[from + i])), static_cast<const uint8_t*>(device_ptr(w, resolve(scales[from + i])))};
-        aligned = aligned && aligned16(term[i].codes) && aligned16(term[i].scales);
-    }
-    return aligned;
-}
-
-}  // namespace
-
-void piquant_hip_reduce_quantize_mx(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* codes, const uint8_t* const* scales,
-                                    size_t count, void* out_codes, uint8_t* out_scales, size_t numel, piquant_hip_mx_format_t fmt) {
-    const char* entry = "piquant_hip_reduce_quantize_mx";
-    const Where w {entry};
-    check_mx_call(w, ctx, dtype_acc, fmt);
-    if (count > static_cast<size_t>(kMxMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kMxMaxInputs);
-    if (numel == 0) return;
-    if (!acc || !out_codes || !out_scales) bad(w, "NULL buffer");
-    if (count != 0 && (!codes || !scales)) bad(w, "NULL term list");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    MxReduceLaunch r {mx_float_ptr(ctx, w, acc, dtype_acc), device_ptr(w, ctx->resolve_ptr(out_codes)), static_cast<uint8_t*>(device_ptr(w, resolve(out_scales))),
-                      static_cast<int64_t>(numel), dtype_acc, fmt, {}, static_cast<int>(count)};
-    const bool aligned = resolve_mx_terms(ctx, entry, codes, scales, 0, count, r.term) && aligned16(r.acc) && aligned16(r.codes) && aligned16(r.scales);
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // acc and the terms are written by what was enqueued before: always behind it
-        launch_reduce_quantize_mx(r, !aligned, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// Everything 16-byte aligned: one launch per kMxMaxInputs terms, the first with the call's op and the others ADD -- the composition rounds to
-// dtype_out at every term, so where the launches are cut changes no byte.  Anything misaligned: the composition itself, one dequantize_mx per term.
-void piquant_hip_dequantize_sum_mx(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, size_t count, void* out,
-                                   piquant_dtype_t dtype_out, size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
-    const char* entry = "piquant_hip_dequantize_sum_mx";
-    const Where w {entry};
-    check_mx_call(w, ctx, dtype_out, fmt);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) bad(w, "the reduce op must be SET or ADD");
-    if (count == 0) bad(w, "no terms (count must be at least 1)");
-    if (!codes || !scales) bad(w, "NULL term list");
-    if (numel == 0) return;
-    if (!out) bad(w, "NULL buffer");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    void* out_dev = mx_float_ptr(ctx, w, out, dtype_out);
-    bool aligned = aligned16(out_dev);
-    for (size_t from = 0; from < count; from += kMxMaxInputs) {   // every term is checked before anything is launched
-        MxTerm term[kMxMaxInputs];
-        aligned = resolve_mx_terms(ctx, entry, codes, scales, from, std::min(count - from, static_cast<size_t>(kMxMaxInputs)), term) && aligned;
-    }
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the terms and an ADD's out are written by what was enqueued before: always behind it
-        for (size_t from = 0; from < count; from += kMxMaxInputs) {
-            const size_t n = std::min(count - from, static_cast<size_t>(kMxMaxInputs));
-            MxDequantSumLaunch d {out_dev, static_cast<int64_t>(numel), dtype_out, fmt, from == 0 && op == PIQUANT_REDUCE_OP_SET ? OP_SET : OP_ADD, {},
-                                  static_cast<int>(n)};
-            resolve_mx_terms(ctx, entry, codes, scales, from, n, d.term);
-            if (aligned) {
-                launch_dequantize_sum_mx(d, ctx->stream);
-                continue;
-            }
-            for (size_t i = 0; i < n; ++i)
-                launch_dequantize_mx(MxDequantLaunch {d.term[i].codes, d.term[i].scales, out_dev, d.numel, dtype_out, fmt, i == 0 ? d.op : OP_ADD}, ctx->stream,
-                                     ctx->num_cu);
-        }
-    }
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-// The batches: piquant_hip_quantize_grouped_batch's rule.  Empty members are skipped, a member with a buffer that is not 16-byte aligned runs alone
-// through the single launch (the guarded kernel, the same bytes), the others collect and leave every kMxMaxInputs members and at the end.
-void piquant_hip_quantize_mx_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes, uint8_t* const* scales,
-                                   const size_t* numels, size_t count, piquant_hip_mx_format_t fmt) {
-    const char* entry = "piquant_hip_quantize_mx_batch";
-    check_mx_call(Where {entry}, ctx, dtype_in, fmt);
-    if (count == 0) return;
-    if (!inputs || !codes || !scales || !numels) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    MxQuantBatchLaunch b {};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx);
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        const Where w {entry, static_cast<long>(i)};
-        if (!inputs[i] || !codes[i] || !scales[i]) bad(w, "NULL buffer");
-        const MxQuantLaunch q {mx_float_ptr(ctx, w, inputs[i], dtype_in), device_ptr(w, ctx->resolve_ptr(codes[i])),
-                               static_cast<uint8_t*>(device_ptr(w, resolve(scales[i]))), static_cast<int64_t>(numels[i]), dtype_in, fmt};
-        if (!(aligned16(q.in) && aligned16(q.codes) && aligned16(q.scales))) {
-            launch_quantize_mx(q, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        b.t[b.count] = q;
-        if (++b.count == kMxMaxInputs) {
-            launch_quantize_mx_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_quantize_mx_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
-}
-
-void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, void* const* outputs,
-                                     piquant_dtype_t dtype_out, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
-    const char* entry = "piquant_hip_dequantize_mx_batch";
-    check_mx_call(Where {entry}, ctx, dtype_out, fmt);
-    if (op != PIQUANT_REDUCE_OP_SET && op != PIQUANT_REDUCE_OP_ADD) panic("%s: the reduce op must be SET or ADD", entry);
-    if (count == 0) return;
-    if (!codes || !scales || !outputs || !numels) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    MxDequantBatchLaunch b {};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the scale bytes are written by whatever was enqueued just before
-    for (size_t i = 0; i < count; ++i) {
-        if (numels[i] == 0) continue;
-        const Where w {entry, static_cast<long>(i)};
-        if (!codes[i] || !scales[i] || !outputs[i]) bad(w, "NULL buffer");
-        const MxDequantLaunch d {device_ptr(w, ctx->resolve_ptr(codes[i])), static_cast<const uint8_t*>(device_ptr(w, resolve(scales[i]))),
-                                 mx_float_ptr(ctx, w, outputs[i], dtype_out), static_cast<int64_t>(numels[i]), dtype_out, fmt,
-                                 op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET};
-        if (!(aligned16(d.codes) && aligned16(d.scales) && aligned16(d.out))) {
-            launch_dequantize_mx(d, ctx->stream, ctx->num_cu);
-            continue;
-        }
-        b.t[b.count] = d;
-        if (++b.count == kMxMaxInputs) {
-            launch_dequantize_mx_batch(b, ctx->stream);
-            b.count = 0;
-        }
-    }
-    launch_dequantize_mx_batch(b, ctx->stream);
-    if (ctx->blocking) wait_stream(ctx);
+    dequantize_single(ctx, w, in, dtype_in, out, dtype_out, numel, group_size, scales, zero_points, op, false,
+                      [&](const GroupedDequantLaunch& d) { launch_dequantize_grouped(d, ctx->stream, ctx->num_cu); });
 }
 
 // The three rotated calls (grouped_rot_kernels.hpp): the two entries above with the rotation's seed, and the stand-alone transform.  In and out
@@ -521,18 +358,11 @@ void piquant_hip_hadamard_grouped(piquant_context_t* ctx, const void* in, piquan
     check_group_size(group_size, w.entry);
     if (numel == 0) return;
     if (!in || !out) bad(w, "NULL buffer");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
+    const CallLock lock(ctx);
     const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, nullptr, nullptr, numel);
-    const size_t esize = dtype == PIQUANT_DTYPE_F32 ? 4 : 2;
-    if (reinterpret_cast<uintptr_t>(t.in) % esize != 0 || reinterpret_cast<uintptr_t>(t.out) % esize != 0) bad(w, "in or out is not aligned to its element size");
+    check_element_aligned(w, "in or out", t.in, dtype, t.out, dtype);
     const GroupedHadamardLaunch h {t.in, t.out, t.numel, static_cast<int64_t>(group_size), dtype, seed, inverse != 0};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, false);
-        launch_hadamard_grouped(h, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    run_call(ctx, false, [&] { launch_hadamard_grouped(h, !streams_in_out(t), ctx->stream, ctx->num_cu); });
 }
 
 void piquant_hip_quantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
@@ -541,20 +371,8 @@ void piquant_hip_quantize_grouped_rotated(piquant_context_t* ctx, const void* in
     if (!ctx) bad(w, "context is NULL");
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    check_tensor(w, false, in, nullptr, out, scales, zero_points);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
-    if (reinterpret_cast<uintptr_t>(t.in) % (dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "in is not aligned to its element size");
-    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
-    const GroupedQuantLaunch q {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, false);
-        launch_quantize_grouped_rotated(q, seed, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    quantize_single(ctx, w, in, dtype_in, out, dtype_out, numel, group_size, scales, zero_points, false, mode, true,
+                    [&](const GroupedQuantLaunch& q) { launch_quantize_grouped_rotated(q, seed, !streams_in_out(q), ctx->stream, ctx->num_cu); });
 }
 
 void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* out, piquant_dtype_t dtype_out,
@@ -564,87 +382,32 @@ void piquant_hip_dequantize_grouped_rotated(piquant_context_t* ctx, const void* 
     if (!ctx) bad(w, "context is NULL");
     check_dequant_types(dtype_in, dtype_out, op);
     check_group_size(group_size);
-    if (numel == 0) return;
-    check_tensor(w, false, in, nullptr, out, scales, zero_points);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, in, nullptr, out, scales, zero_points, numel);
-    if (reinterpret_cast<uintptr_t>(t.out) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
-    const GroupedDequantLaunch d {t, {static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-        launch_dequantize_grouped_rotated(d, seed, !(aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    dequantize_single(ctx, w, in, dtype_in, out, dtype_out, numel, group_size, scales, zero_points, op, true,
+                      [&](const GroupedDequantLaunch& d) { launch_dequantize_grouped_rotated(d, seed, !streams_in_out(d), ctx->stream, ctx->num_cu); });
 }
 
-// The two steps of a grouped collective in the rotated domain: ONE launch each, streaming when acc / out and every term's packed bytes are 16-byte
-// aligned, guarded otherwise.  More than kGroupedReduceMaxInputs terms abort: the float32 running sum has nowhere to be spilled to.
 void piquant_hip_reduce_quantize_grouped_rotated(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* inputs,
                                                  const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
                                                  piquant_dtype_t dtype_out, size_t numel, size_t group_size, float* scales, uint8_t* zero_points,
                                                  uint64_t seed, piquant_round_mode_t mode) {
     const char* entry = "piquant_hip_reduce_quantize_grouped_rotated";
-    const Where w {entry};
-    if (!ctx) bad(w, "context is NULL");
+    if (!ctx) bad(Where {entry}, "context is NULL");
     check_dynamic_types(dtype_acc, dtype_out, mode);
-    check_group_size(group_size, entry);
-    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    check_tensor(w, false, acc, nullptr, out, scales, zero_points);
-    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, acc, nullptr, out, scales, zero_points, numel);
-    if (reinterpret_cast<uintptr_t>(t.in) % (dtype_acc == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "acc is not aligned to its element size");
-    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, t.out, numel);
-    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
-    GroupedReduceLaunch r {t, {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)}, {}, static_cast<int>(count)};
-    std::copy(terms.term.begin(), terms.term.end(), r.term);
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // terms and parameters are written by what was enqueued before: always behind it
-        launch_reduce_quantize_grouped_rotated(r, seed, !(terms.aligned && aligned16(t.in) && aligned16(t.out)), ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    reduce_quantize_grouped_rotated(ctx, entry, false, acc, dtype_acc, nullptr, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
+                                    group_size, scales, zero_points, seed, mode);
 }
 
-// Error feedback in the rotated domain: the two quantizing calls above with a float32 residual of rotated values (grouped_rot_ef_kernels.hpp).
-// ONE launch each: streaming when the tensor is aligned as its rows are loaded (16 bytes; 8 for bfloat16) and residual, out and every term's packed
-// bytes are 16-byte aligned, guarded otherwise.  Without terms the reduce IS the quantize: one body serves both entries.
+// Without terms the reduce IS the quantize, and says so in its messages: one entry serves both.
 void piquant_hip_reduce_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, float* residual,
                                                     const void* const* inputs, const float* const* input_scales,
                                                     const uint8_t* const* input_zero_points, size_t count, void* out, piquant_dtype_t dtype_out,
                                                     size_t numel, size_t group_size, float* scales, uint8_t* zero_points, uint64_t seed,
                                                     piquant_round_mode_t mode) {
     const char* entry = count == 0 ? "piquant_hip_quantize_grouped_rotated_ef" : "piquant_hip_reduce_quantize_grouped_rotated_ef";
-    const Where w {entry};
-    if (!ctx) bad(w, "context is NULL");
+    if (!ctx) bad(Where {entry}, "context is NULL");
     check_dynamic_types(dtype_acc, dtype_out, mode);
-    check_group_size(group_size, entry);
-    if (count > static_cast<size_t>(kGroupedReduceMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kGroupedReduceMaxInputs);
-    if (numel == 0) return;   // before a stochastic threshold would be drawn
-    check_tensor(w, true, acc, residual, out, scales, zero_points);
-    if (count != 0 && (!inputs || !input_scales || !input_zero_points)) bad(w, "NULL term list");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    const GroupedTensor t = resolve_tensor(ctx, w, acc, residual, out, scales, zero_points, numel);
-    const bool f32 = dtype_acc == PIQUANT_DTYPE_F32;
-    if (reinterpret_cast<uintptr_t>(t.in) % (f32 ? 4 : 2) != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0)
-        bad(w, "the tensor or its residual is not aligned to its element size");
-    const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, t.out, numel);
-    const bool streams = terms.aligned && (reinterpret_cast<uintptr_t>(t.in) & (f32 ? 15u : 7u)) == 0 && aligned16(t.residual) && aligned16(t.out);
-    // the call's one threshold (or the per-element seed and base), as piquant_hip_quantize_grouped draws it
-    GroupedReduceLaunch r {t, {static_cast<int64_t>(group_size), dtype_acc, dtype_out, false, round_mode_fields(ctx, mode)}, {}, static_cast<int>(count)};
-    std::copy(terms.term.begin(), terms.term.end(), r.term);
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
-        if (count == 0) launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, r}, seed, !streams, ctx->stream, ctx->num_cu);
-        else launch_reduce_quantize_grouped_rotated_ef(r, seed, !streams, ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    reduce_quantize_grouped_rotated(ctx, entry, true, acc, dtype_acc, residual, inputs, input_scales, input_zero_points, count, out, dtype_out, numel,
+                                    group_size, scales, zero_points, seed, mode);
 }
 
 void piquant_hip_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, float* residual, void* out,
@@ -654,6 +417,8 @@ void piquant_hip_quantize_grouped_rotated_ef(piquant_context_t* ctx, const void*
                                                    zero_points, seed, mode);
 }
 
+// The second step of a grouped collective in the rotated domain: ONE launch for at most kGroupedReduceMaxInputs terms, streaming when out and every
+// term's packed bytes are 16-byte aligned, guarded otherwise.
 void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in,
                                                 const float* const* input_scales, const uint8_t* const* input_zero_points, size_t count, void* out,
                                                 piquant_dtype_t dtype_out, size_t numel, size_t group_size, uint64_t seed, piquant_reduce_op_t op) {
@@ -667,22 +432,19 @@ void piquant_hip_dequantize_sum_grouped_rotated(piquant_context_t* ctx, const vo
     if (!inputs || !input_scales || !input_zero_points) bad(w, "NULL term list");
     if (numel == 0) return;   // a no-op whatever the buffers are: an empty tensor's address may be NULL
     if (!out) bad(w, "NULL buffer");
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
+    const CallLock lock(ctx);
     void* out_dev = device_ptr(w, ctx->resolve_ptr(out));
-    if (reinterpret_cast<uintptr_t>(out_dev) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    check_element_aligned(w, "out", out_dev, dtype_out);
     const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, out_dev, numel);
-    GroupedDequantSumLaunch d {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, out_dev,
-                               static_cast<int64_t>(numel), {}, static_cast<int>(count)};
+    GroupedDequantSumLaunch d {{static_cast<int64_t>(group_size), dtype_in, dtype_out, to_op(op)}, out_dev, static_cast<int64_t>(numel), {},
+                               static_cast<int>(count)};
     std::copy(terms.term.begin(), terms.term.end(), d.term);
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
-        launch_dequantize_sum_grouped_rotated(d, seed, !(terms.aligned && aligned16(out_dev)), ctx->stream, ctx->num_cu);
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
+    run_call(ctx, true, [&] { launch_dequantize_sum_grouped_rotated(d, seed, !(terms.aligned && aligned16(out_dev)), ctx->stream, ctx->num_cu); });
 }
 
+// The batches: quantize_batch's and dequantize_batch's rules.  A member that fails its single call's alignment rule runs alone, in its place in the
+// sequence, through that call's guarded launch.
 void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
                                         piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
                                         uint8_t* const* zero_points, size_t count, int params_given, piquant_round_mode_t mode) {
@@ -690,25 +452,12 @@ void piquant_hip_quantize_grouped_batch(piquant_context_t* ctx, const void* cons
     if (!ctx) panic("%s: context is NULL", entry);
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size);
-    if (count == 0) return;   // before a stochastic threshold would be drawn
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
-    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, params_given != 0, round_mode_fields(ctx, mode)}, {}, 0};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, b.params_given);
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
-            return resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
-        },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_quantize_grouped(GroupedQuantLaunch {t, b}, ctx->stream, ctx->num_cu); },
-        [&] { launch_quantize_grouped_batch(b, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    quantize_batch(
+        ctx, entry, inputs, dtype_in, nullptr, outputs, dtype_out, numels, group_size, scales, zero_points, count, params_given != 0, mode,
+        params_given != 0,   // given parameters are written by whatever was enqueued just before
+        [](const Where&, const GroupedTensor&, size_t) {}, streams_in_out,
+        [&](const GroupedQuantLaunch& q) { launch_quantize_grouped(q, ctx->stream, ctx->num_cu); },
+        [&](const GroupedQuantBatchLaunch& b) { launch_quantize_grouped_batch(b, ctx->stream); });
 }
 
 void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
@@ -718,29 +467,12 @@ void piquant_hip_dequantize_grouped_batch(piquant_context_t* ctx, const void* co
     if (!ctx) panic("%s: context is NULL", entry);
     check_dequant_types(dtype_in, dtype_out, op);
     check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    GroupedDequantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, {}, 0};
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
-            return resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
-        },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_dequantize_grouped(GroupedDequantLaunch {t, b}, ctx->stream, ctx->num_cu); },
-        [&] { launch_dequantize_grouped_batch(b, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    dequantize_batch(
+        ctx, entry, inputs, dtype_in, outputs, dtype_out, numels, group_size, scales, zero_points, count, op, false,
+        [&](const GroupedDequantLaunch& d) { launch_dequantize_grouped(d, ctx->stream, ctx->num_cu); },
+        [&](const GroupedDequantBatchLaunch& b) { launch_dequantize_grouped_batch(b, ctx->stream); });
 }
 
-// The batches of the three rotated calls: the rules of the two batches above and of quantize_grouped_ef_batch (ONE threshold, or per-element seed and
-// base, per batch, drawn whenever count > 0; empty members skipped; one streaming launch per kGroupedBatchMaxTensors members), with the rotation's
-// seed.  A member that fails its single call's alignment rule runs alone, in its place in the sequence, through that call's guarded launch.
 void piquant_hip_quantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
                                                 piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
                                                 uint8_t* const* zero_points, size_t count, uint64_t seed, piquant_round_mode_t mode) {
@@ -748,28 +480,12 @@ void piquant_hip_quantize_grouped_rotated_batch(piquant_context_t* ctx, const vo
     if (!ctx) panic("%s: context is NULL", entry);
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size);
-    if (count == 0) return;   // before a stochastic threshold would be drawn
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
-    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
-    const size_t esize = dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, false);
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
-            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
-            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0) bad(w, "in is not aligned to its element size");
-            return t;
-        },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_quantize_grouped_rotated(GroupedQuantLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
-        [&] { launch_quantize_grouped_rotated_batch(b, seed, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    quantize_batch(
+        ctx, entry, inputs, dtype_in, nullptr, outputs, dtype_out, numels, group_size, scales, zero_points, count, false, mode,
+        false,   // the parameters are computed: nothing here is written by the call before
+        [&](const Where& w, const GroupedTensor& t, size_t) { check_element_aligned(w, "in", t.in, dtype_in); }, streams_in_out,
+        [&](const GroupedQuantLaunch& q) { launch_quantize_grouped_rotated(q, seed, true, ctx->stream, ctx->num_cu); },
+        [&](const GroupedQuantBatchLaunch& b) { launch_quantize_grouped_rotated_batch(b, seed, ctx->stream); });
 }
 
 void piquant_hip_dequantize_grouped_rotated_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
@@ -779,27 +495,10 @@ void piquant_hip_dequantize_grouped_rotated_batch(piquant_context_t* ctx, const 
     if (!ctx) panic("%s: context is NULL", entry);
     check_dequant_types(dtype_in, dtype_out, op);
     check_group_size(group_size);
-    if (count == 0) return;
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    GroupedDequantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET}, {}, 0};
-    const size_t esize = dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the parameters are written by whatever was enqueued just before
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
-            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
-            if (reinterpret_cast<uintptr_t>(t.out) % esize != 0) bad(w, "out is not aligned to its element size");
-            return t;
-        },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_dequantize_grouped_rotated(GroupedDequantLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
-        [&] { launch_dequantize_grouped_rotated_batch(b, seed, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    dequantize_batch(
+        ctx, entry, inputs, dtype_in, outputs, dtype_out, numels, group_size, scales, zero_points, count, op, true,
+        [&](const GroupedDequantLaunch& d) { launch_dequantize_grouped_rotated(d, seed, true, ctx->stream, ctx->num_cu); },
+        [&](const GroupedDequantBatchLaunch& b) { launch_dequantize_grouped_rotated_batch(b, seed, ctx->stream); });
 }
 
 void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, float* const* residuals,
@@ -810,34 +509,18 @@ void piquant_hip_quantize_grouped_rotated_ef_batch(piquant_context_t* ctx, const
     if (!ctx) panic("%s: context is NULL", entry);
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size, entry);
-    if (count == 0) return;   // before a stochastic threshold would be drawn
-    if (!inputs || !residuals || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
-    GroupedEfBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
-    const bool f32 = dtype_in == PIQUANT_DTYPE_F32;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, true);   // the residual is written by the previous step's call: always behind it
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, true, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i]);
-            const GroupedTensor t = resolve_tensor(ctx, w, inputs[i], residuals[i], outputs[i], scales[i], zero_points[i], numels[i]);
-            if (reinterpret_cast<uintptr_t>(t.in) % (f32 ? 4 : 2) != 0 || reinterpret_cast<uintptr_t>(t.residual) % 4 != 0)
-                bad(w, "the tensor or its residual is not aligned to its element size");
-            return t;
-        },
-        [&](const GroupedTensor& t) { return (reinterpret_cast<uintptr_t>(t.in) & (f32 ? 15u : 7u)) == 0 && aligned16(t.residual) && aligned16(t.out); },
-        [&](const GroupedTensor& t) { launch_quantize_grouped_rotated_ef(GroupedEfLaunch {t, b}, seed, true, ctx->stream, ctx->num_cu); },
-        [&] { launch_quantize_grouped_rotated_ef_batch(b, seed, ctx->stream); });
-    if (ctx->blocking) wait_stream(ctx);
+    quantize_batch(
+        ctx, entry, inputs, dtype_in, residuals, outputs, dtype_out, numels, group_size, scales, zero_points, count, false, mode,
+        true,   // the residual is written by the previous step's call: always behind it
+        [&](const Where& w, const GroupedTensor& t, size_t) { check_ef_elements(w, t, dtype_in); },
+        [&](const GroupedTensor& t) { return rotated_ef_streams(dtype_in, t); },
+        [&](const GroupedEfLaunch& q) { launch_quantize_grouped_rotated_ef(q, seed, true, ctx->stream, ctx->num_cu); },
+        [&](const GroupedEfBatchLaunch& b) { launch_quantize_grouped_rotated_ef_batch(b, seed, ctx->stream); });
 }
 
 // The clip search (grouped_clip_kernels.hpp): piquant_hip_quantize_grouped_batch's rules with computed parameters, the candidates' count and the
-// members' choices.  A member whose in or out is not 16-byte aligned runs alone through the guarded launch: the same bytes.  steps == 1 searches
-// nothing: it IS quantize_grouped with computed parameters, so its launches are made and the members' choices are zeroed on the stream.
+// members' choices.  steps == 1 searches nothing: it IS quantize_grouped with computed parameters, so its launches are made and the members' choices
+// are zeroed on the stream.
 void piquant_hip_quantize_grouped_clipped_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* outputs,
                                                 piquant_dtype_t dtype_out, const size_t* numels, size_t group_size, float* const* scales,
                                                 uint8_t* const* zero_points, uint8_t* const* choices, size_t count, int steps,
@@ -847,37 +530,24 @@ void piquant_hip_quantize_grouped_clipped_batch(piquant_context_t* ctx, const vo
     check_dynamic_types(dtype_in, dtype_out, mode);
     check_group_size(group_size, entry);
     if (steps < 1 || steps > 12) panic("%s: steps %d is not in [1, 12]", entry, steps);
-    if (count == 0) return;   // before a stochastic threshold would be drawn
-    if (!inputs || !outputs || !numels || !scales || !zero_points) panic("%s: NULL argument", entry);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    // ONE threshold (or per-element seed and base) for the whole batch, also when every member is empty
-    GroupedQuantBatchLaunch b {{static_cast<int64_t>(group_size), dtype_in, dtype_out, false, round_mode_fields(ctx, mode)}, {}, 0};
-    const size_t esize = dtype_in == PIQUANT_DTYPE_F32 ? 4 : 2;
-    StopEventScope completion(ctx);
-    IndependentCallScope independent(ctx, false);
-    run_batch(
-        b, numels, count,
-        [&](size_t i) {
-            const Where w {entry, static_cast<long>(i)};
-            check_tensor(w, false, inputs[i], nullptr, outputs[i], scales[i], zero_points[i]);
-            GroupedTensor t = resolve_tensor(ctx, w, inputs[i], nullptr, outputs[i], scales[i], zero_points[i], numels[i]);
-            if (reinterpret_cast<uintptr_t>(t.in) % esize != 0) bad(w, "in is not aligned to its element size");
+    quantize_batch(
+        ctx, entry, inputs, dtype_in, nullptr, outputs, dtype_out, numels, group_size, scales, zero_points, count, false, mode,
+        false,   // the parameters are computed: nothing here is written by the call before
+        [&](const Where& w, GroupedTensor& t, size_t i) {
+            check_element_aligned(w, "in", t.in, dtype_in);
             if (choices && choices[i]) t.choices = static_cast<uint8_t*>(device_ptr(w, resolve(choices[i])));
             if (steps == 1 && t.choices) PQ_HIP(hipMemsetAsync(t.choices, 0, (numels[i] + group_size - 1) / group_size, ctx->stream));
-            return t;
         },
-        [](const GroupedTensor& t) { return aligned16(t.in) && aligned16(t.out); },
-        [&](const GroupedTensor& t) {
-            if (steps == 1) launch_quantize_grouped(GroupedQuantLaunch {t, b}, ctx->stream, ctx->num_cu);
-            else launch_quantize_grouped_clipped_guarded(GroupedQuantLaunch {t, b}, steps, ctx->stream, ctx->num_cu);
+        streams_in_out,
+        [&](const GroupedQuantLaunch& q) {
+            if (steps == 1) launch_quantize_grouped(q, ctx->stream, ctx->num_cu);
+            else launch_quantize_grouped_clipped_guarded(q, steps, ctx->stream, ctx->num_cu);
         },
-        [&] {
+        [&](const GroupedQuantBatchLaunch& b) {
             if (steps == 1 && b.count == 1) launch_quantize_grouped(GroupedQuantLaunch {b.t[0], b}, ctx->stream, ctx->num_cu);   // the single kernel
             else if (steps == 1) launch_quantize_grouped_batch(b, ctx->stream);
             else launch_quantize_grouped_clipped_batch(b, steps, ctx->stream);
         });
-    if (ctx->blocking) wait_stream(ctx);
 }
 
 // The single call is a batch of one, which launches the single-tensor kernel; an empty tensor returns behind the argument checks and draws nothing.
@@ -915,16 +585,13 @@ void piquant_hip_dequantize_sum_grouped(piquant_context_t* ctx, const void* cons
     if (!inputs || !input_scales || !input_zero_points) bad(w, "NULL term list");
     if (!out) bad(w, "NULL buffer");
     if (numel == 0) return;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
+    const CallLock lock(ctx);
     void* out_dev = device_ptr(w, ctx->resolve_ptr(out));
-    if (reinterpret_cast<uintptr_t>(out_dev) % (dtype_out == PIQUANT_DTYPE_F32 ? 4 : 2) != 0) bad(w, "out is not aligned to its element size");
+    check_element_aligned(w, "out", out_dev, dtype_out);
     const Terms terms = resolve_terms(ctx, entry, inputs, input_scales, input_zero_points, count, out_dev, numel);
-    const int first_op = op == PIQUANT_REDUCE_OP_ADD ? OP_ADD : OP_SET;
-    const GroupedDequantCall call {static_cast<int64_t>(group_size), dtype_in, dtype_out, first_op};
-    {   // both scopes end before the wait
-        StopEventScope completion(ctx);
-        IndependentCallScope independent(ctx, true);   // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
+    const GroupedDequantCall call {static_cast<int64_t>(group_size), dtype_in, dtype_out, to_op(op)};
+    // terms, parameters and an ADD's out are written by what was enqueued before: always behind it
+    run_call(ctx, true, [&] {
         if (terms.aligned && aligned16(out_dev)) {
             for (size_t from = 0; from < count; from += kGroupedReduceMaxInputs) {
                 const size_t n = std::min(count - from, static_cast<size_t>(kGroupedReduceMaxInputs));
@@ -937,8 +604,7 @@ void piquant_hip_dequantize_sum_grouped(piquant_context_t* ctx, const void* cons
             add_terms(ctx, terms, 0, 1, call);
             add_terms(ctx, terms, 1, count, GroupedDequantCall {call.group_size, dtype_in, dtype_out, OP_ADD});
         }
-    }
-    if (ctx->blocking) wait_stream(ctx);
+    });
 }
 
 void piquant_hip_quantize_grouped_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* residuals,
