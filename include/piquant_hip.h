@@ -759,6 +759,34 @@ PIQUANT_EXPORT void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, cons
                                                     piquant_dtype_t dtype_out, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt,
                                                     piquant_reduce_op_t op);
 
+/* Error feedback on the MX wire: what a lossy gradient all-reduce over MX records needs to stay usable over many steps.  The residual R is float32
+ * WHATEVER the tensor's type (a bfloat16 residual rounds away as much as it keeps), has numel elements and is read and written.
+ * piquant_hip_quantize_mx_ef, dtype_in float32 or bfloat16: exactly what this sequence writes --
+ *   1. y_i = rn_f32(widen(x_i) + R_i), widen exact;
+ *   2. (codes, scales) = piquant_hip_quantize_mx(y, F32);
+ *   3. d_i = element i of piquant_hip_dequantize_mx(codes, scales, F32, SET);
+ *   4. R_i = rn_f32(y_i - d_i), a subtraction of its own (no contraction with the scaling, no reassociation).
+ *   `in` is not written; nothing at or past the tensor's end is touched in any buffer; in, residual, codes and scales must not overlap.  A NaN y_i
+ *   leaves a NaN in R_i (payload and sign outside the contract).  An infinite y_i saturates to the largest code under the largest scale its block
+ *   can get, which dequantize_mx gives back as an infinity of y_i's sign: by 4 the residual of that element is then a NaN too, and the other
+ *   elements of its block quantize to zero and keep R_i = y_i -- an infinity does not survive a lossy wire, with or without a residual.
+ * piquant_hip_quantize_mx_ef_batch: member i (its own input, residual, codes, scales and numels[i]) gets the bytes of the single call.  ONE launch
+ *   per 16 members; empty members are skipped, a member with a buffer that is not 16-byte aligned goes through the single call in its place.
+ * piquant_hip_reduce_quantize_mx_ef: the sum is formed exactly as piquant_hip_reduce_quantize_mx forms it (the terms added in order into a copy of
+ *   acc, the sum rounded to dtype_acc after each), then steps 1-4 run on it: the residual is added BEHIND the terms, as in
+ *   piquant_hip_reduce_quantize_grouped_ef.  acc is not written.  count == 0 is quantize_mx_ef(acc, residual); count > 16 aborts like the plain call.
+ * All three: nearest only; ONE launch (streaming for 16-byte aligned buffers, a guarded kernel with the same bytes otherwise); device (or pinned)
+ * buffers only; stream-ordered on the context's stream and always behind the previous call -- the residual is the previous step's output; no host
+ * synchronisation, no allocation (hipGraph-capturable); numel == 0 is a no-op. */
+PIQUANT_EXPORT void piquant_hip_quantize_mx_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, float* residual, void* codes,
+                                               uint8_t* scales, size_t numel, piquant_hip_mx_format_t fmt);
+PIQUANT_EXPORT void piquant_hip_quantize_mx_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, float* const* residuals,
+                                                     void* const* codes, uint8_t* const* scales, const size_t* numels, size_t count,
+                                                     piquant_hip_mx_format_t fmt);
+PIQUANT_EXPORT void piquant_hip_reduce_quantize_mx_ef(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, float* residual,
+                                                      const void* const* codes, const uint8_t* const* scales, size_t count, void* out_codes,
+                                                      uint8_t* out_scales, size_t numel, piquant_hip_mx_format_t fmt);
+
 /* Host helpers: key <-> float, and the (min,max) -> (scale, zero_point) epilogue in double precision
  * (reference src/piquant.cpp:213-220, 245-258).  keys[0] encodes min, keys[1] encodes -max. */
 PIQUANT_EXPORT void piquant_hip_decode_minmax_keys(const int32_t keys[2], float* out_min, float* out_max);

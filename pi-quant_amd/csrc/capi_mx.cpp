@@ -1,6 +1,6 @@
-// The MX entry points of include/piquant_hip.h (mx_kernels.hpp, mx_reduce_kernels.hpp): fixed blocks of 32 FP4 E2M1 / FP8 E4M3 codes under one E8M0
-// scale byte -- no groups, no zero points, no round mode, so nothing is drawn.  The two single calls, and the wire: the fused reduce, the
-// dequantize-sum and the two batches.  All are stream-ordered, take device (or pinned) buffers only and read as capi_frame.hpp says; the terms of the
+// The MX entry points of include/piquant_hip.h (mx_kernels.hpp, mx_reduce_kernels.hpp, mx_ef_kernels.hpp): fixed blocks of 32 FP4 E2M1 / FP8 E4M3
+// codes under one E8M0 scale byte -- no groups, no zero points, no round mode, so nothing is drawn.  The two single calls, the wire (the fused reduce,
+// the dequantize-sum and the two batches) and the three error-feedback calls on a float32 residual.  All are stream-ordered, take device (or pinned) buffers only and read as capi_frame.hpp says; the terms of the
 // wire are resolved without allocating (at most kMxMaxInputs a launch, on the stack).
 #include "capi_frame.hpp"
 
@@ -25,6 +25,11 @@ void* mx_float_ptr(const piquant_context_t* ctx, const Where& w, const void* p, 
     void* dev = device_ptr(w, ctx->resolve_ptr(p));
     check_element_aligned(w, "the float tensor", dev, dtype);
     return dev;
+}
+
+// the float32 residual of the error-feedback calls
+float* mx_residual_ptr(const piquant_context_t* ctx, const Where& w, float* residual) {
+    return static_cast<float*>(mx_float_ptr(ctx, w, residual, PIQUANT_DTYPE_F32));
 }
 
 // The scale bytes are classified whatever the context assumes of the tensors the caller passes.
@@ -179,6 +184,61 @@ void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, const void* const* 
             [&](const MxDequantLaunch& d) { launch_dequantize_mx(d, ctx->stream, ctx->num_cu); },
             [&] { launch_dequantize_mx_batch(b, ctx->stream); });
     });
+}
+
+// ---- error feedback (mx_ef_kernels.hpp): the residual is float32 and read: every call runs behind what was enqueued before it ----
+
+void piquant_hip_quantize_mx_ef(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, float* residual, void* codes, uint8_t* scales, size_t numel,
+                                piquant_hip_mx_format_t fmt) {
+    const Where w {"piquant_hip_quantize_mx_ef"};
+    check_mx_call(w, ctx, "input", dtype_in, fmt);
+    if (numel == 0) return;
+    if (!in || !residual || !codes || !scales) bad(w, "NULL buffer");
+    const CallLock lock(ctx);
+    const MxEfLaunch q {mx_float_ptr(ctx, w, in, dtype_in), mx_residual_ptr(ctx, w, residual), device_ptr(w, ctx->resolve_ptr(codes)), mx_scales_ptr(w, scales),
+                        static_cast<int64_t>(numel), dtype_in, fmt};
+    run_call(ctx, true, [&] { launch_quantize_mx_ef(q, ctx->stream, ctx->num_cu); });
+}
+
+void piquant_hip_quantize_mx_ef_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, float* const* residuals, void* const* codes,
+                                      uint8_t* const* scales, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt) {
+    const char* entry = "piquant_hip_quantize_mx_ef_batch";
+    check_mx_call(Where {entry}, ctx, "float type", dtype_in, fmt);
+    if (count == 0) return;
+    if (!inputs || !residuals || !codes || !scales || !numels) panic("%s: NULL argument", entry);
+    const CallLock lock(ctx);
+    MxEfBatchLaunch b {};
+    run_call(ctx, true, [&] {
+        run_batch(
+            b, numels, count,
+            [&](size_t i) {
+                const Where w {entry, static_cast<long>(i)};
+                if (!inputs[i] || !residuals[i] || !codes[i] || !scales[i]) bad(w, "NULL buffer");
+                return MxEfLaunch {mx_float_ptr(ctx, w, inputs[i], dtype_in), mx_residual_ptr(ctx, w, residuals[i]), device_ptr(w, ctx->resolve_ptr(codes[i])),
+                                   mx_scales_ptr(w, scales[i]), static_cast<int64_t>(numels[i]), dtype_in, fmt};
+            },
+            [](const MxEfLaunch& q) { return aligned16(q.in) && aligned16(q.residual) && aligned16(q.codes) && aligned16(q.scales); },
+            [&](const MxEfLaunch& q) { launch_quantize_mx_ef(q, ctx->stream, ctx->num_cu); },
+            [&] { launch_quantize_mx_ef_batch(b, ctx->stream); });
+    });
+}
+
+void piquant_hip_reduce_quantize_mx_ef(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, float* residual, const void* const* codes,
+                                       const uint8_t* const* scales, size_t count, void* out_codes, uint8_t* out_scales, size_t numel,
+                                       piquant_hip_mx_format_t fmt) {
+    const char* entry = "piquant_hip_reduce_quantize_mx_ef";
+    const Where w {entry};
+    check_mx_call(w, ctx, "float type", dtype_acc, fmt);
+    if (count > static_cast<size_t>(kMxMaxInputs)) panic("%s: %zu terms, at most %d", entry, count, kMxMaxInputs);
+    if (numel == 0) return;
+    if (!acc || !residual || !out_codes || !out_scales) bad(w, "NULL buffer");
+    if (count != 0 && (!codes || !scales)) bad(w, "NULL term list");
+    const CallLock lock(ctx);
+    MxReduceEfLaunch r {mx_float_ptr(ctx, w, acc, dtype_acc), mx_residual_ptr(ctx, w, residual), device_ptr(w, ctx->resolve_ptr(out_codes)),
+                        mx_scales_ptr(w, out_scales), static_cast<int64_t>(numel), dtype_acc, fmt, {}, static_cast<int>(count)};
+    const bool aligned = resolve_mx_terms(ctx, entry, codes, scales, 0, count, r.term) && aligned16(r.acc) && aligned16(r.residual) && aligned16(r.codes) &&
+                         aligned16(r.scales);
+    run_call(ctx, true, [&] { launch_reduce_quantize_mx_ef(r, !aligned, ctx->stream, ctx->num_cu); });
 }
 
 }  // extern "C"

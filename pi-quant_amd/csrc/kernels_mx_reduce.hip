@@ -9,23 +9,6 @@
 
 namespace pq {
 
-namespace {
-
-template <class Launch>
-MxTerms mx_terms_of(const Launch& l, const char* what, int min_count) {
-    static_assert(kMxMaxInputs == kMxMaxTerms, "host and device term limits");
-    if (l.count < min_count || l.count > kMxMaxTerms) panic("%s: %d terms, %d to %d per launch", what, l.count, min_count, kMxMaxTerms);
-    MxTerms terms {};
-    for (int i = 0; i < l.count; ++i) {
-        terms.codes[i] = static_cast<const uint8_t*>(l.term[i].codes);
-        terms.scales[i] = l.term[i].scales;
-    }
-    terms.count = l.count;
-    return terms;
-}
-
-}  // namespace
-
 void launch_reduce_quantize_mx(const MxReduceLaunch& r, bool guarded, hipStream_t stream, int num_cu) {
     if (r.numel <= 0) return;
     const MxTerms terms = mx_terms_of(r, "reduce_quantize_mx", 0);

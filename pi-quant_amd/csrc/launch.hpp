@@ -322,6 +322,36 @@ void launch_reduce_quantize_mx(const MxReduceLaunch& r, bool guarded, hipStream_
 void launch_dequantize_sum_mx(const MxDequantSumLaunch& d, hipStream_t stream);
 void launch_quantize_mx_batch(const MxQuantBatchLaunch& b, hipStream_t stream);
 void launch_dequantize_mx_batch(const MxDequantBatchLaunch& b, hipStream_t stream);
+// Error feedback on the MX wire (mx_ef_kernels.hpp; kernels_mx_ef.hip): y = rn_f32(widen(x) + residual), (codes, scales) = quantize_mx(y),
+// residual <- rn_f32(y - dequantize_mx(codes, scales)); the residual is float32 whatever dt_in is.  ONE launch each, the alignment rules of the plain
+// launches with the residual among the buffers; the reduce forms its sum as launch_reduce_quantize_mx does and adds the residual behind the terms.
+struct MxEfLaunch {
+    const void* in;        // numel elements of dt_in
+    float* residual;       // numel float32, read and written
+    void* codes;
+    uint8_t* scales;
+    int64_t numel;
+    int dt_in;             // DT_F32 / DT_BF16
+    int fmt;
+};
+struct MxEfBatchLaunch {
+    MxEfLaunch t[kMxMaxInputs];
+    int count;
+};
+struct MxReduceEfLaunch {
+    const void* acc;       // numel elements of dt_acc
+    float* residual;
+    void* codes;
+    uint8_t* scales;
+    int64_t numel;
+    int dt_acc;
+    int fmt;
+    MxTerm term[kMxMaxInputs];
+    int count;
+};
+void launch_quantize_mx_ef(const MxEfLaunch& q, hipStream_t stream, int num_cu);
+void launch_quantize_mx_ef_batch(const MxEfBatchLaunch& b, hipStream_t stream);
+void launch_reduce_quantize_mx_ef(const MxReduceEfLaunch& r, bool guarded, hipStream_t stream, int num_cu);
 // Min/max scan.  `state` is a minmax_state_ints() int32 device buffer armed once with launch_arm_slots: one 8-byte result word
 // per block (the "gather" end: every block stores its word, the highest block folds them) and, for scans that accumulate
 // into one state (MM_NONE), 64 slot key pairs on separate 128-byte lines plus arrival counters.  Either way the block that finishes

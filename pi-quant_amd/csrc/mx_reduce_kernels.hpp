@@ -34,6 +34,20 @@ struct MxTerms {
     int count;
 };
 
+// the kernels' term table from a launch's term[] and count (launch.hpp: MxReduceLaunch, MxDequantSumLaunch, MxReduceEfLaunch); host side
+template <class Launch>
+inline MxTerms mx_terms_of(const Launch& l, const char* what, int min_count) {
+    static_assert(kMxMaxInputs == kMxMaxTerms, "host and device term limits");
+    if (l.count < min_count || l.count > kMxMaxTerms) panic("%s: %d terms, %d to %d per launch", what, l.count, min_count, kMxMaxTerms);
+    MxTerms terms {};
+    for (int i = 0; i < l.count; ++i) {
+        terms.codes[i] = static_cast<const uint8_t*>(l.term[i].codes);
+        terms.scales[i] = l.term[i].scales;
+    }
+    terms.count = l.count;
+    return terms;
+}
+
 template <int DT_ACC, int FMT>
 using MxQuantRows = u32x4[MxQuantTile<DT_ACC, FMT>::NV];    // the resident rows of a fused reduce's tile
 template <int FMT, int DT_OUT>

@@ -525,6 +525,36 @@ class Context:
         C.piquant_hip_dequantize_mx_batch(self._ctx, (_C.c_void_p * n)(*codes_ptrs), (_C.c_void_p * n)(*scales_ptrs), (_C.c_void_p * n)(*ptrs_out),
                                           dtype_out.value, (_C.c_size_t * n)(*numels), n, fmt, reduce_op.value)
 
+    def quantize_mx_ef_ptr(self, ptr_in: int, dtype_in: DataType, residual_ptr: int, codes_ptr: int, scales_ptr: int, numel: int, fmt: int,
+                           _device_ptrs: bool = False) -> None:
+        """Error-feedback MX quantize in one launch (``piquant_hip_quantize_mx_ef``): ``quantize_mx_ptr`` of ``in + residual`` in float32;
+        ``residual_ptr`` (``numel`` float32, whatever ``dtype_in``) is read and left holding what the codes lost."""
+        assert dtype_in.is_dequantized and fmt in (0, 1)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx_ef(self._ctx, ptr_in, dtype_in.value, residual_ptr, codes_ptr, scales_ptr, numel, fmt)
+
+    def quantize_mx_ef_batch_ptr(self, ptrs_in, dtype_in: DataType, residual_ptrs, codes_ptrs, scales_ptrs, numels, fmt: int,
+                                 _device_ptrs: bool = False) -> None:
+        """``quantize_mx_ef_ptr`` for several independent (tensor, residual) pairs, up to 16 per kernel launch
+        (``piquant_hip_quantize_mx_ef_batch``)."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and fmt in (0, 1) and n == len(residual_ptrs) == len(codes_ptrs) == len(scales_ptrs) == len(numels)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx_ef_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*residual_ptrs),
+                                           (_C.c_void_p * n)(*codes_ptrs), (_C.c_void_p * n)(*scales_ptrs), (_C.c_size_t * n)(*numels), n, fmt)
+
+    def reduce_quantize_mx_ef_ptr(self, ptr_acc: int, dtype_acc: DataType, residual_ptr: int, codes_ptrs, scales_ptrs, out_codes_ptr: int,
+                                  out_scales_ptr: int, numel: int, fmt: int, _device_ptrs: bool = False) -> None:
+        """``quantize_mx_ef(acc + sum_i dequantize_mx(term_i), residual)`` in one launch (``piquant_hip_reduce_quantize_mx_ef``); ``acc`` is only
+        read.  At most 16 terms: more is a ValueError here (the C call aborts)."""
+        n = len(codes_ptrs)
+        if n > 16:
+            raise ValueError(f'reduce_quantize_mx_ef takes at most 16 terms, got {n}')
+        assert dtype_acc.is_dequantized and fmt in (0, 1) and n == len(scales_ptrs)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_reduce_quantize_mx_ef(self._ctx, ptr_acc, dtype_acc.value, residual_ptr, (_C.c_void_p * n)(*codes_ptrs),
+                                            (_C.c_void_p * n)(*scales_ptrs), n, out_codes_ptr, out_scales_ptr, numel, fmt)
+
     def quantize_grouped_batch_ptr(self, ptrs_in, dtype_in: DataType, ptrs_out, dtype_out: DataType, numels, group_size: int, scales_ptrs,
                                    zero_points_ptrs, params_given: bool, round_mode: RoundMode, _device_ptrs: bool = False) -> None:
         """``quantize_grouped_ptr`` for several independent tensors (own parameter arrays each), up to 16 per kernel launch

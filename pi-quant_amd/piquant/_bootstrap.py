@@ -64,6 +64,10 @@ _DECLS = [
     ('piquant_hip_reduce_quantize_mx', None, [_vp, _vp, _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _vp, _sz, _int]),
     ('piquant_hip_quantize_mx_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz, _int]),
     ('piquant_hip_dequantize_mx_batch', None, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _int, C.POINTER(_sz), _sz, _int, _int]),
+    ('piquant_hip_quantize_mx_ef', None, [_vp, _vp, _int, _vp, _vp, _vp, _sz, _int]),
+    ('piquant_hip_quantize_mx_ef_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(_sz), _sz, _int]),
+    ('piquant_hip_reduce_quantize_mx_ef', None, [_vp, _vp, _int, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _vp, _sz, _int]),
     ('piquant_hip_quantize_grouped_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int, C.POINTER(_sz), _sz, C.POINTER(C.c_void_p),
                                                   C.POINTER(C.c_void_p), _sz, _int, _int]),
     ('piquant_hip_dequantize_grouped_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), _int, C.POINTER(_sz), _sz,

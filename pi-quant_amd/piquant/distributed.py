@@ -665,6 +665,28 @@ class _DeviceOps:
             self._cx(out).dequantize_sum_mx_ptr([r[0] for r in recs], [r[1] for r in recs], out.data_ptr(), torch_to_piquant_dtype(out.dtype), n,
                                                 _MX_FORMATS[fmt], _REDUCE_OPS[reduce_op], _device_ptrs=True)
 
+    # ---- the MX wire with error feedback (``mx_error_feedback``): ``residual`` is the float32 slice that belongs to the values ----
+    def encode_mx_ef(self, x: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, fmt: str) -> None:
+        codes, sc = self._record_mx(buf, x.numel(), fmt)
+        self._cx(x).quantize_mx_ef_ptr(x.data_ptr(), torch_to_piquant_dtype(x.dtype), residual.data_ptr(), codes, sc, x.numel(), _MX_FORMATS[fmt],
+                                       _device_ptrs=True)
+
+    def encode_batch_mx_ef(self, xs, residuals, bufs, fmt: str) -> None:
+        """encode_mx_ef(xs[i], residuals[i], bufs[i]) for all i with one kernel launch per 16 chunks."""
+        if xs:
+            recs = [self._record_mx(b, x.numel(), fmt) for x, b in zip(xs, bufs)]
+            self._cx(xs[0]).quantize_mx_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r.data_ptr() for r in residuals],
+                                                     [r[0] for r in recs], [r[1] for r in recs], [x.numel() for x in xs], _MX_FORMATS[fmt],
+                                                     _device_ptrs=True)
+
+    def reduce_encode_mx_ef(self, bufs, acc: torch.Tensor, residual: torch.Tensor, buf: torch.Tensor, fmt: str) -> None:
+        """encode_mx_ef(acc + the wire buffers, added in order; residual) into ``buf`` as ONE launch; ``acc`` is only read."""
+        n = acc.numel()
+        recs = [self._record_mx(b, n, fmt) for b in bufs]
+        codes, sc = self._record_mx(buf, n, fmt)
+        self._cx(acc).reduce_quantize_mx_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [r[0] for r in recs],
+                                                [r[1] for r in recs], codes, sc, n, _MX_FORMATS[fmt], _device_ptrs=True)
+
     # ---- the grouped wire in the rotated domain (``rotation_seed``): the same records, holding the rotated values ----
     def encode_grouped_rotated(self, x: torch.Tensor, buf: torch.Tensor, qdtype: torch.dtype, round_mode: str, group_size: int, seed: int) -> None:
         sc, zp, data = self._record(buf, x.numel(), qdtype, group_size)
@@ -879,7 +901,8 @@ class _Wire:
     def __init__(self, ops, quant_dtype: torch.dtype, round_mode: str, group_size: Optional[int] = None, residual: Optional[torch.Tensor] = None,
                  requantize: bool = False, rotation_seed: Optional[int] = None, clip_steps: Optional[int] = None, mx_format: Optional[str] = None):
         self.ops, self.round_mode, self.group_size = ops, round_mode, group_size
-        self.mx = mx_format                      # the MX wire (mx_wire_layout): never with a group size, a seed, a residual or a clip search (_check_mx_format)
+        self.mx = mx_format                      # the MX wire (mx_wire_layout): never with a group size, a seed or a clip search; its residual is
+                                                 # the float32 one of ``mx_error_feedback`` (_check_mx_format, _check_mx_error_feedback)
         self.seed = rotation_seed
         self.clip_steps = clip_steps             # the encodes search each group's clipping range (never with a seed or a residual: _check_clip_steps)
         self.quant_dtype, self.qdt = quant_dtype, torch_to_piquant_dtype(quant_dtype)     # the torch dtype the ops take, its DataType for the lengths
@@ -895,8 +918,10 @@ class _Wire:
         return grouped_wire_layout(numel, self.group_size, self.qdt.bit_size).nbytes
 
     def encode(self, x, buf, chunk, ef: bool = True) -> None:
-        """``ef`` False: the rotated owner's encode without ``requantize``, which leaves the residual alone."""
-        if self.mx is not None:
+        """``ef`` False: an encode that leaves the residual alone (the rotated owner's without ``requantize``); every wire with a residual honours it."""
+        if self.mx is not None and self.residual is not None and ef:
+            self.ops.encode_mx_ef(x, self.residual[chunk[0]:chunk[1]], buf, self.mx)
+        elif self.mx is not None:
             self.ops.encode_mx(x, buf, self.mx)
         elif self.group_size is None:
             self.ops.encode(x, buf, self.quant_dtype, self.round_mode)
@@ -912,7 +937,9 @@ class _Wire:
             self.ops.encode_grouped_ef(x, self.residual[chunk[0]:chunk[1]], buf, self.quant_dtype, self.round_mode, self.group_size)
 
     def encode_batch(self, xs, bufs, chunks) -> None:
-        if self.mx is not None:
+        if self.mx is not None and self.residual is not None:
+            self.ops.encode_batch_mx_ef(xs, [self.residual[b:e] for b, e in chunks], bufs, self.mx)
+        elif self.mx is not None:
             self.ops.encode_batch_mx(xs, bufs, self.mx)
         elif self.group_size is None:
             self.ops.encode_batch(xs, bufs, self.quant_dtype, self.round_mode)
@@ -930,7 +957,9 @@ class _Wire:
 
     def reduce_encode(self, terms, acc, buf, chunk) -> None:
         """encode(acc + the records in ``terms``, added in order) into ``buf``, one launch; the residual takes part only with ``requantize``."""
-        if self.mx is not None:
+        if self.mx is not None and self.requantize:
+            self.ops.reduce_encode_mx_ef(terms, acc, self.residual[chunk[0]:chunk[1]], buf, self.mx)
+        elif self.mx is not None:
             self.ops.reduce_encode_mx(terms, acc, buf, self.mx)
         elif self.group_size is None:
             self.ops.reduce_encode(terms, acc, buf, self.quant_dtype, self.round_mode)
@@ -1081,6 +1110,7 @@ def quantized_all_reduce(
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
     mx_format: Optional[str] = None,
+    mx_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1192,12 +1222,21 @@ def quantized_all_reduce(
     anything moves: together with ``group_size``, ``error_feedback``, ``error_feedback_requantize``, ``rotation_seed``, ``rotated_error_feedback``,
     ``clip_steps`` or ``transport='p2p'``, with a ``quant_dtype`` other than the default, with a ``round_mode`` other than 'nearest', and in the
     direct schedule with more than 17 ranks.  (Unmeasured on more than one GPU.)
+
+    ``mx_error_feedback`` (``mx_format`` only; a keyword of its own, ``error_feedback`` keeps raising with ``mx_format``): a float32 tensor -- whatever
+    the tensor's dtype -- contiguous, on the tensor's device and of its numel, updated in place.  Every encode of the rank's own values becomes
+    ``quantize_mx_ef`` on the matching chunk of it (the mesh's peer chunks: ONE ``quantize_mx_ef_batch`` launch); with ``error_feedback_requantize``,
+    which is accepted together with it, every ring hop and the mesh owner's step become ONE ``reduce_quantize_mx_ef`` launch on their chunk, so each
+    element of the residual is touched exactly once per call.  It belongs to one (world size, rank, algorithm, ``error_feedback_requantize``,
+    format).  ValueError before anything moves: without ``mx_format``, with ``error_feedback``, ``rotated_error_feedback``, ``group_size`` or
+    ``transport='p2p'``, and for a residual that is not such a tensor.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
                      error_feedback_requantize=error_feedback_requantize, rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback,
-                     clip_steps=clip_steps, transport=transport)
+                     clip_steps=clip_steps, transport=transport, mx_error_feedback=mx_error_feedback)
+    _check_mx_error_feedback(mx_error_feedback, tensor, mx_format, transport)
     _check_clip_steps(clip_steps, group_size, all_reduce=True)
     if algorithm not in ('ring', 'direct'):
         raise ValueError(f"algorithm must be 'ring' or 'direct', got {algorithm!r}")
@@ -1205,22 +1244,23 @@ def quantized_all_reduce(
         raise ValueError(f"transport must be 'collective' or 'p2p', got {transport!r}")
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
-    _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
-                                     transport)
+    if mx_error_feedback is None:   # the MX residual takes the re-quantizations as it is: no group size to ask for
+        _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
+                                         transport)
     seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, transport, error_feedback)
     if algorithm == 'direct':
         return quantized_all_reduce_direct(tensor, quant_dtype=quant_dtype, round_mode=round_mode, group=group, ctx=ctx, transport=transport, timeout=timeout,
                                            group_size=group_size, error_feedback=error_feedback, error_feedback_requantize=error_feedback_requantize,
-                                           rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, mx_format=mx_format, _ops=_ops,
-                                           _single_rank_collectives=_single_rank_collectives)
+                                           rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, mx_format=mx_format,
+                                           mx_error_feedback=mx_error_feedback, _ops=_ops, _single_rank_collectives=_single_rank_collectives)
     if transport != 'collective':
         raise ValueError("transport='p2p' is the mesh schedule's (algorithm='direct'); the ring forwards through its neighbours")
     world = dist.get_world_size(group)
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, _wire_residual(error_feedback, rotated_error_feedback, mx_error_feedback, seed),
                  error_feedback_requantize, seed, mx_format=mx_format)
     _ring(wire, _Chunks.of(wire, tensor.view(-1), world), group, world, rank, tensor.device)
     return tensor
@@ -1242,6 +1282,7 @@ def quantized_all_reduce_direct(
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
     mx_format: Optional[str] = None,
+    mx_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1289,19 +1330,23 @@ def quantized_all_reduce_direct(
     group size).
 
     ``mx_format``: the MX wire of ``quantized_all_reduce`` -- step 1 is ONE ``quantize_mx_batch`` launch, steps 3-4 ONE ``reduce_quantize_mx`` launch
-    over the G-1 received records in increasing rank order, the decode ONE ``dequantize_mx_batch`` launch.  At most 17 ranks; collective transport,
+    over the G-1 received records in increasing rank order, the decode ONE ``dequantize_mx_batch`` launch.  With ``mx_error_feedback`` (as in
+    ``quantized_all_reduce``) step 1 is ONE ``quantize_mx_ef_batch`` launch on the peers' chunks of the residual and, with
+    ``error_feedback_requantize``, steps 3-4 ONE ``reduce_quantize_mx_ef`` launch on the rank's own chunk.  At most 17 ranks; collective transport,
     nearest rounding and none of the grouped wire's keywords.
     """
     if not (tensor.is_contiguous() and tensor.dtype in (torch.float32, torch.bfloat16)):
         raise ValueError('quantized_all_reduce needs a contiguous float32 or bfloat16 tensor')
     _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
                      error_feedback_requantize=error_feedback_requantize, rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback,
-                     clip_steps=clip_steps, transport=transport)
+                     clip_steps=clip_steps, transport=transport, mx_error_feedback=mx_error_feedback)
+    _check_mx_error_feedback(mx_error_feedback, tensor, mx_format, transport)
     _check_clip_steps(clip_steps, group_size, all_reduce=True)
     _check_all_reduce_group_size(group_size, transport)
     _check_error_feedback(error_feedback, tensor, group_size, transport)
-    _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
-                                     transport)
+    if mx_error_feedback is None:   # the MX residual takes the re-quantizations as it is: no group size to ask for
+        _check_error_feedback_requantize(error_feedback_requantize, error_feedback if error_feedback is not None else rotated_error_feedback, group_size,
+                                         transport)
     seed = _check_rotation_seed(rotation_seed, group_size, transport, error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, transport, error_feedback)
     world = dist.get_world_size(group)
@@ -1310,7 +1355,7 @@ def quantized_all_reduce_direct(
     _check_mx_terms(mx_format, world, 'the direct schedule')
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, _wire_residual(error_feedback, rotated_error_feedback, mx_error_feedback, seed),
                  error_feedback_requantize, seed, mx_format=mx_format)
     flat = tensor.view(-1)
     ch = _Chunks.of(wire, flat, world)
@@ -1441,17 +1486,18 @@ _MX_MAX_TERMS = 16   # piquant_hip_reduce_quantize_mx: one launch, the sum never
 
 
 def _check_mx_format(mx_format, *, quant_dtype, round_mode, group_size, error_feedback=None, error_feedback_requantize=False, rotation_seed=None,
-                     rotated_error_feedback=None, clip_steps=None, transport: str = 'collective', default_group_size=None) -> None:
+                     rotated_error_feedback=None, clip_steps=None, transport: str = 'collective', default_group_size=None, mx_error_feedback=None) -> None:
     """ValueError before anything moves: the MX wire is a wire of its own -- its blocks of 32 are no groups, its scale bytes no (scale, zero point),
     its rounding nearest -- so it goes with none of the grouped wire's keywords, no ``quant_dtype`` and no peer-to-peer transport.
-    ``default_group_size``: what ``group_size`` is when the caller did not pass it (128 for the two sharded collectives)."""
+    ``default_group_size``: what ``group_size`` is when the caller did not pass it (128 for the two sharded collectives).  Its own residual,
+    ``mx_error_feedback``, is what ``error_feedback_requantize`` goes with here."""
     if mx_format is None:
         return
     if not (isinstance(mx_format, str) and mx_format in _MX_FORMATS):
         raise ValueError(f'mx_format must be None or one of {sorted(_MX_FORMATS)}, got {mx_format!r}')
     if group_size != default_group_size:
         raise ValueError('mx_format= is not supported with group_size= (an MX block is 32 elements under one scale byte; leave group_size at its default)')
-    for name, given in (('error_feedback', error_feedback is not None), ('error_feedback_requantize', bool(error_feedback_requantize)),
+    for name, given in (('error_feedback', error_feedback is not None), ('error_feedback_requantize', bool(error_feedback_requantize) and mx_error_feedback is None),
                         ('rotation_seed', rotation_seed is not None), ('rotated_error_feedback', rotated_error_feedback is not None),
                         ('clip_steps', clip_steps is not None)):
         if given:
@@ -1462,6 +1508,28 @@ def _check_mx_format(mx_format, *, quant_dtype, round_mode, group_size, error_fe
         raise ValueError(f'mx_format= names the wire format itself: quant_dtype must stay at its default, got {quant_dtype}')
     if round_mode != 'nearest':
         raise ValueError(f"mx_format= rounds to nearest only (quantize_mx has no stochastic mode), got round_mode={round_mode!r}")
+
+
+def _check_mx_error_feedback(residual, tensor: torch.Tensor, mx_format, transport: str = 'collective') -> None:
+    """ValueError before anything moves: an MX residual without the MX wire (whose own check, ``_check_mx_format``, has by now turned down the
+    grouped wire's residuals, a group size and the peer-to-peer transport), or one that is not float32, contiguous, on the tensor's device and of
+    its numel (it is written by raw pointer)."""
+    if residual is None:
+        return
+    if mx_format is None:
+        raise ValueError('mx_error_feedback= needs the MX wire: pass mx_format= (the grouped wire has error_feedback= and rotated_error_feedback=)')
+    if transport == 'p2p':
+        raise ValueError("mx_error_feedback= is not supported with transport='p2p'; use transport='collective'")
+    from .torch import _check_mx_residual
+
+    _check_mx_residual(residual, tensor, 'mx_error_feedback')
+
+
+def _wire_residual(error_feedback, rotated_error_feedback, mx_error_feedback, seed):
+    """The one residual of a call (the checks have left at most one): the MX wire's, the rotated domain's under a seed, or the grouped wire's."""
+    if mx_error_feedback is not None:
+        return mx_error_feedback
+    return error_feedback if seed is None else rotated_error_feedback
 
 
 def _check_mx_terms(mx_format, world: int, what: str) -> None:
@@ -1494,6 +1562,7 @@ def quantized_reduce_scatter(
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
     mx_format: Optional[str] = None,
+    mx_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1537,14 +1606,19 @@ def quantized_reduce_scatter(
     ``mx_format`` (as in ``quantized_all_reduce``; ``group_size`` must be left at its default, which is then not used): step 1 is ONE
     ``quantize_mx_batch`` launch per 16 chunks, step 3 ONE ``dequantize_sum_mx(..., 'add')`` launch into the own chunk.  Followed by
     ``quantized_all_gather`` with the same format it leaves exactly the bytes of ``quantized_all_reduce(algorithm='direct', mx_format=...)``, whose
-    ``reduce_quantize_mx`` is defined as these ADDs followed by ``quantize_mx``.  At most 17 ranks.
+    ``reduce_quantize_mx`` is defined as these ADDs followed by ``quantize_mx``.  At most 17 ranks.  ``mx_error_feedback`` (the float32 residual of
+    ``quantized_all_reduce``): step 1 becomes ONE ``quantize_mx_ef_batch`` launch on the peers' chunks of it; the own chunk is not touched.  Followed by
+    ``quantized_all_gather`` with the same residual it leaves the tensor and residual bytes of the direct all-reduce with
+    ``error_feedback_requantize=True``.
 
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU, like the rest
     of this module's multi-GPU paths.)"""
     _check_sharded_collective('quantized_reduce_scatter', tensor, group_size, error_feedback)
     _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
-                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128)
+                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128,
+                     mx_error_feedback=mx_error_feedback)
+    _check_mx_error_feedback(mx_error_feedback, tensor, mx_format)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
@@ -1556,7 +1630,7 @@ def quantized_reduce_scatter(
     if world == 1 and not _single_rank_collectives:
         b_own, e_own = ring_chunks(flat.numel(), world, torch_to_piquant_dtype(quant_dtype).bit_size)[rank]
         return flat[b_own:e_own]
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, _wire_residual(error_feedback, rotated_error_feedback, mx_error_feedback, seed),
                  rotation_seed=seed, clip_steps=clip_steps, mx_format=mx_format)
     ch = _Chunks.of(wire, flat, world)
     x_own = ch.views[rank]
@@ -1579,6 +1653,7 @@ def quantized_all_gather(
     rotated_error_feedback: Optional[torch.Tensor] = None,
     clip_steps: Optional[int] = None,
     mx_format: Optional[str] = None,
+    mx_error_feedback: Optional[torch.Tensor] = None,
     _ops=None,
     _single_rank_collectives: bool = False,
 ) -> torch.Tensor:
@@ -1607,13 +1682,15 @@ def quantized_all_gather(
     unchanged.  Not with ``rotation_seed``, ``error_feedback`` or ``rotated_error_feedback``.
 
     ``mx_format`` (as in ``quantized_reduce_scatter``): step 1 is ``quantize_mx`` of the own chunk, step 3 ONE ``dequantize_mx_batch(..., 'set')``
-    launch per 16 chunks.
+    launch per 16 chunks.  ``mx_error_feedback``: step 1 becomes ``quantize_mx_ef`` on the rank's own chunk of the residual, no other chunk is touched.
 
     ``group_size`` must be a group size (``None`` raises); every argument check raises ValueError before anything moves.  A one-rank group
     returns at once (``_ops`` and ``_single_rank_collectives`` as in ``quantized_all_reduce``).  (Unmeasured on more than one GPU.)"""
     _check_sharded_collective('quantized_all_gather', tensor, group_size, error_feedback)
     _check_mx_format(mx_format, quant_dtype=quant_dtype, round_mode=round_mode, group_size=group_size, error_feedback=error_feedback,
-                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128)
+                     rotation_seed=rotation_seed, rotated_error_feedback=rotated_error_feedback, clip_steps=clip_steps, default_group_size=128,
+                     mx_error_feedback=mx_error_feedback)
+    _check_mx_error_feedback(mx_error_feedback, tensor, mx_format)
     seed = _check_rotation_seed(rotation_seed, group_size, 'collective', error_feedback)
     _check_rotated_error_feedback(rotated_error_feedback, tensor, group_size, rotation_seed, 'collective', error_feedback)
     _check_clip_steps(clip_steps, group_size, rotation_seed, error_feedback, rotated_error_feedback)
@@ -1621,7 +1698,7 @@ def quantized_all_gather(
     rank = dist.get_rank(group)
     if world == 1 and not _single_rank_collectives:
         return tensor
-    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, error_feedback if seed is None else rotated_error_feedback,
+    wire = _Wire(_ops or _DeviceOps(ctx), quant_dtype, round_mode, group_size, _wire_residual(error_feedback, rotated_error_feedback, mx_error_feedback, seed),
                  rotation_seed=seed, clip_steps=clip_steps, mx_format=mx_format)
     ch = _Chunks.of(wire, tensor.view(-1), world)
     mine = torch.zeros(ch.slot, dtype=torch.uint8, device=tensor.device)

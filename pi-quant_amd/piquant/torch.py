@@ -874,6 +874,81 @@ def dequantize_sum_mx(terms, *, format: str, out: torch.Tensor, reduce_op: str =
     return out
 
 
+def _check_mx_residual(residual, tensor: torch.Tensor, what: str = 'residual') -> None:
+    """The residual of an MX error-feedback call is float32 whatever the tensor's dtype, and written by raw pointer: contiguous, on the tensor's
+    device, of the tensor's numel."""
+    _require(isinstance(residual, torch.Tensor) and residual.dtype == torch.float32,
+             f'{what} must be a torch.float32 tensor (the MX residual is float32 for float32 and bfloat16 tensors alike)')
+    _require(residual.numel() == tensor.numel(), f'{what} must have the numel of the tensor ({tensor.numel()}), got {residual.numel()}')
+    _require(residual.device == tensor.device, f'{what} must live on the device of the tensor ({tensor.device}), got {residual.device}')
+    _require(residual.is_contiguous(), f'{what} must be contiguous (it is updated in place)')
+
+
+def _mx_out(out, numel: int, format: str, device):
+    """``out`` of the MX calls that take one: None (fresh buffers), or the (codes, scales) to write."""
+    if out is None:
+        return tuple(torch.empty(n, dtype=torch.uint8, device=device) for n in mx_nbytes(numel, format))
+    _require(isinstance(out, (list, tuple)) and len(out) == 2, 'out must be (codes, scales)')
+    _check_mx_terms([out], numel, format, device)
+    return out[0], out[1]
+
+
+def quantize_mx_ef(tensor: torch.Tensor, residual: torch.Tensor, *, format: str, out=None, ctx: Optional[Context] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Error-feedback ``quantize_mx`` in ONE launch (piquant_hip_quantize_mx_ef): ``y = float32(tensor) + residual``, ``(codes, scales) =
+    quantize_mx(y)``, ``residual <- y - dequantize_mx(codes, scales)`` -- bit for bit that composition in float32.  ``residual`` is a contiguous
+    float32 tensor of the tensor's numel and device whatever the tensor's dtype, updated in place; ``tensor`` is not written.  ``out``: None, or
+    the (codes, scales) to write.  Returns (codes, scales)."""
+    _check_mx_format(format)
+    _check_float_input(tensor)
+    _check_mx_residual(residual, tensor)
+    codes, scales = _mx_out(out, tensor.numel(), format, tensor.device)
+    if not tensor.is_contiguous():
+        tensor = tensor.contiguous()
+    _ctx_for(tensor, ctx).quantize_mx_ef_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), residual.data_ptr(), codes.data_ptr(), scales.data_ptr(),
+                                             tensor.numel(), MX_FORMATS[format], _device_ptrs=True)
+    return codes, scales
+
+
+def quantize_mx_ef_batch(tensors, residuals, *, format: str, ctx: Optional[Context] = None):
+    """``quantize_mx_ef(tensors[i], residuals[i])`` for every i with ONE launch per 16 pairs (piquant_hip_quantize_mx_ef_batch); returns the list
+    of (codes, scales), each the bytes of the single call.  One float dtype and one device; empty tensors take no part."""
+    _check_mx_format(format)
+    _require(isinstance(tensors, (list, tuple)) and isinstance(residuals, (list, tuple)) and len(tensors) == len(residuals),
+             'tensors and residuals must be lists of one length')
+    for i, (t, r) in enumerate(zip(tensors, residuals)):
+        _check_float_input(t, f'tensors[{i}]')
+        _require(t.dtype == tensors[0].dtype and t.device == tensors[0].device, 'the tensors of a batch share one dtype and one device')
+        _check_mx_residual(r, t, f'residuals[{i}]')
+    if not tensors:
+        return []
+    xs = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    outs = [_mx_out(None, x.numel(), format, x.device) for x in xs]
+    _ctx_for(xs[0], ctx).quantize_mx_ef_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [r.data_ptr() for r in residuals],
+                                                  [o[0].data_ptr() for o in outs], [o[1].data_ptr() for o in outs], [x.numel() for x in xs],
+                                                  MX_FORMATS[format], _device_ptrs=True)
+    return outs
+
+
+def reduce_quantize_mx_ef(acc: torch.Tensor, residual: torch.Tensor, terms, *, format: str, out=None,
+                          ctx: Optional[Context] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``quantize_mx_ef(acc + sum_i dequantize_mx(terms[i]), residual)`` in ONE launch (piquant_hip_reduce_quantize_mx_ef): the sum is formed as
+    ``reduce_quantize_mx`` forms it (the terms added in order, rounded to ``acc``'s dtype after each), the residual is added behind the terms in
+    float32.  ``acc`` is not written, ``residual`` (float32, as in ``quantize_mx_ef``) is updated in place.  At most 16 terms (ValueError); none:
+    ``quantize_mx_ef(acc, residual)``.  Returns (codes, scales)."""
+    _check_mx_format(format)
+    _check_float_input(acc, 'acc')
+    _check_mx_residual(residual, acc)
+    _check_mx_terms(terms, acc.numel(), format, acc.device)
+    _require(len(terms) <= 16, f'reduce_quantize_mx_ef takes at most 16 terms, got {len(terms)}')
+    codes, scales = _mx_out(out, acc.numel(), format, acc.device)
+    if not acc.is_contiguous():
+        acc = acc.contiguous()
+    _ctx_for(acc, ctx).reduce_quantize_mx_ef_ptr(acc.data_ptr(), torch_to_piquant_dtype(acc.dtype), residual.data_ptr(), [t[0].data_ptr() for t in terms],
+                                                 [t[1].data_ptr() for t in terms], codes.data_ptr(), scales.data_ptr(), acc.numel(), MX_FORMATS[format],
+                                                 _device_ptrs=True)
+    return codes, scales
+
+
 def _check_seed(seed) -> int:
     """The rotation's seed: any Python int, taken modulo 2^64 (``_NA``: the call was made without one)."""
     _require(seed is not _NA, 'seed= is required: the rotation is defined by it, and the inverse needs the same one')

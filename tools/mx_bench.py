@@ -19,6 +19,13 @@ same-width grouped fused call at G = 32 as comparator.  A row gives fused and co
 whether fused / composition <= 1.15 x byte ratio ("met" / "missed"), with the windows of both.
 
     python tools/mx_bench.py --rows wire [--windows 7] [--rotate-gb 3.3] [--out FILE]
+
+--rows ef measures the error-feedback calls the same way and writes profiles/mx_ef_bench.json: quantize_mx_ef {float32, bfloat16} x {FP4, FP8}
+against torch.add -> quantize_mx -> dequantize_mx -> torch.sub, the 7-member batch of numel / 8 against 7 single launches of the fused call, and
+reduce_quantize_mx_ef (float32 / bfloat16 + 1 / 7 FP4 terms) against a copy of acc, dequantize_mx ADD per term and that composition.  The residuals
+rotate like the floats.
+
+    python tools/mx_bench.py --rows ef [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -198,17 +205,116 @@ def wire_main(args):
     print(f"wrote {args.out}")
 
 
+def ef_main(args):
+    """The error-feedback calls of the MX wire against their compositions of public calls (module docstring)."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    ctx = piquant.Context.get(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_blocking(False)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    SET, ADD, F32 = piquant.ReduceOp.SET, piquant.ReduceOp.ADD, piquant.DataType.F32
+    rows = []
+    reduce_rows = [("f32", "fp4_e2m1"), ("bf16", "fp4_e2m1")]
+    nres = max(3, int(args.rotate_gb * 1e9 / (NUMEL * 4)) + 1)
+    rs = [torch.empty(NUMEL, device=dev).uniform_(-0.1, 0.1, generator=gen) for _ in range(nres)]   # the residuals, and the composition's y and d
+    ys = [torch.empty(NUMEL, device=dev) for _ in range(nres)]
+    ds = [torch.empty(NUMEL, device=dev) for _ in range(nres)]
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
+        per_window = max(nbuf, 16)
+        xs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=gen).to(tdt) for _ in range(nbuf)]
+        accs = [torch.empty(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]                       # the reduce composition's copy of acc
+        for fmt in WIDTH:
+            f, (ncodes, nblocks) = pt.MX_FORMATS[fmt], pt.mx_nbytes(NUMEL, fmt)
+            oc, os_ = torch.empty(ncodes, dtype=torch.uint8, device=dev), torch.empty(nblocks, dtype=torch.uint8, device=dev)
+            fl, term = NUMEL * esize, ncodes + nblocks
+            comp_bytes = (fl + 8 * NUMEL) + (4 * NUMEL + term) + (term + 4 * NUMEL) + 12 * NUMEL   # add, quantize_mx, dequantize_mx, sub
+
+            def composition(i, x, n=NUMEL, r=None, c=oc, s=os_):
+                r = rs[i % nres] if r is None else r
+                y, d = ys[i % nres][:n], ds[i % nres][:n]
+                torch.add(x, r, out=y)
+                ctx.quantize_mx_ptr(y.data_ptr(), F32, c.data_ptr(), s.data_ptr(), n, f, _device_ptrs=True)
+                ctx.dequantize_mx_ptr(c.data_ptr(), s.data_ptr(), d.data_ptr(), F32, n, f, SET, _device_ptrs=True)
+                torch.sub(y, d, out=r)
+
+            calls = {
+                "fused": lambda i: ctx.quantize_mx_ef_ptr(xs[i % nbuf].data_ptr(), fdt, rs[i % nres].data_ptr(), oc.data_ptr(), os_.data_ptr(), NUMEL, f,
+                                                          _device_ptrs=True),
+                "composition": lambda i: composition(i, xs[i % nbuf]),
+            }
+            res = timed_alternating(calls, nbuf * nres, args.windows, per_window, stream)
+            wire_row(rows, "quantize_mx_ef", f"{fname} -> {fmt}", res, fl + 8 * NUMEL + term, comp_bytes)
+            if fname == "f32":   # the batch: 7 members of numel / 8 against 7 single launches of the fused call
+                m = NUMEL // 8
+                mc, mb = pt.mx_nbytes(m, fmt)
+                stride = -(-mb // 16) * 16
+                bsc = torch.empty(7 * stride, dtype=torch.uint8, device=dev)
+                cut = lambda t, n: [t[j * n:(j + 1) * n] for j in range(7)]   # noqa: E731
+                ptrs = lambda ts: [t.data_ptr() for t in ts]                  # noqa: E731
+                q = {
+                    "fused": lambda i: ctx.quantize_mx_ef_batch_ptr(ptrs(cut(xs[i % nbuf], m)), fdt, ptrs(cut(rs[i % nres], m)), ptrs(cut(oc, mc)),
+                                                                    ptrs(cut(bsc, stride)), [m] * 7, f, _device_ptrs=True),
+                    "composition": lambda i: [ctx.quantize_mx_ef_ptr(x.data_ptr(), fdt, r.data_ptr(), c.data_ptr(), s.data_ptr(), m, f, _device_ptrs=True)
+                                              for x, r, c, s in zip(cut(xs[i % nbuf], m), cut(rs[i % nres], m), cut(oc, mc), cut(bsc, stride))],
+                }
+                res = timed_alternating(q, nbuf * nres, args.windows, per_window, stream)
+                wire_row(rows, "quantize_mx_ef_batch", f"7 x {fname} -> {fmt}", res, 7 * (m * esize + 8 * m + mc + mb), 7 * (m * esize + 8 * m + mc + mb))
+            if (fname, fmt) in reduce_rows:
+                nset = max(3, int(args.rotate_gb * 1e9 / (7 * ncodes)) + 1)
+                tc = [[torch.empty(ncodes, dtype=torch.uint8, device=dev) for _ in range(7)] for _ in range(nset)]
+                ts = [[torch.empty(nblocks, dtype=torch.uint8, device=dev) for _ in range(7)] for _ in range(nset)]
+                for j in range(nset):
+                    for t in range(7):
+                        ctx.quantize_mx_ptr(xs[(j + t) % nbuf].data_ptr(), fdt, tc[j][t].data_ptr(), ts[j][t].data_ptr(), NUMEL, f, _device_ptrs=True)
+
+                def composition_reduce(i, k):
+                    acc = accs[i % nbuf]
+                    acc.copy_(xs[i % nbuf])                             # the composition's copy of acc: acc itself is not written
+                    for t in range(k):
+                        ctx.dequantize_mx_ptr(tc[i % nset][t].data_ptr(), ts[i % nset][t].data_ptr(), acc.data_ptr(), fdt, NUMEL, f, ADD, _device_ptrs=True)
+                    composition(i, acc)
+
+                for k in (1, 7):
+                    calls = {
+                        "fused": lambda i, k=k: ctx.reduce_quantize_mx_ef_ptr(xs[i % nbuf].data_ptr(), fdt, rs[i % nres].data_ptr(),
+                                                                             [c.data_ptr() for c in tc[i % nset][:k]], [s.data_ptr() for s in ts[i % nset][:k]],
+                                                                             oc.data_ptr(), os_.data_ptr(), NUMEL, f, _device_ptrs=True),
+                        "composition": lambda i, k=k: composition_reduce(i, k),
+                    }
+                    res = timed_alternating(calls, nbuf * nres * nset, args.windows, per_window, stream)
+                    wire_row(rows, "reduce_quantize_mx_ef", f"{fname} + {k} -> {fmt}", res, fl + k * term + 8 * NUMEL + term,
+                             2 * fl + k * (term + 2 * fl) + comp_bytes)
+                del tc, ts
+        del xs, accs
+        torch.cuda.empty_cache()
+    out = {"numel": NUMEL, "device": torch.cuda.get_device_name(0), "windows": args.windows, "rotate_gb": args.rotate_gb,
+           "command": "python tools/mx_bench.py --rows ef",
+           "protocol": "alternating windows of back-to-back calls, HIP events, median over windows; rotated float buffers, residuals and term sets; "
+                       "composition: torch.add -> quantize_mx -> dequantize_mx -> torch.sub (the reduce: a copy of acc and dequantize_mx ADD per term in "
+                       "front); target: fused / composition <= 1.15 x byte ratio",
+           "spread": "run-to-run spread not measured (one run); every row carries the windows of both sides",
+           "not_measured": "other sizes, the guarded kernels, more than one GPU", "rows": rows}
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print(f"wrote {args.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", choices=("calls", "wire"), default="calls")
+    ap.add_argument("--rows", choices=("calls", "wire", "ef"), default="calls")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / ("mx_wire_bench.json" if args.rows == "wire" else "mx_bench.json"))
+        args.out = str(ROOT / "profiles" / {"calls": "mx_bench.json", "wire": "mx_wire_bench.json", "ef": "mx_ef_bench.json"}[args.rows])
     if args.rows == "wire":
         return wire_main(args)
+    if args.rows == "ef":
+        return ef_main(args)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     ctx = piquant.Context.get(0)
