@@ -725,8 +725,22 @@ PIQUANT_EXPORT int piquant_hip_peer_timeout(piquant_context_t* ctx, uint32_t* ou
  * The hardware conversions are the hot path, not the definition: the kernels add what makes them agree with it (mx_kernels.hpp).  ONE launch each;
  * quantize reads its input once (no scan, no atomics, no barrier).  Buffers 16-byte aligned take the streaming kernels, anything else (the float
  * side aligned to its element) guarded kernels that write the same bytes.  Device (or pinned) buffers only; stream-ordered on the context's stream,
- * no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op. */
-typedef enum { PIQUANT_HIP_MX_FP4_E2M1 = 0, PIQUANT_HIP_MX_FP8_E4M3 = 1 } piquant_hip_mx_format_t;
+ * no host synchronisation, no allocation (hipGraph-capturable).  numel == 0 is a no-op.
+ * MXFP6 (PIQUANT_HIP_MX_FP6_E2M3 = 2, PIQUANT_HIP_MX_FP6_E3M2 = 3; piquant_hip_quantize_mx and piquant_hip_dequantize_mx only -- every other MX
+ * call refuses them): 6-bit elements, a sign (0x20), then exponent and mantissa; neither format has a NaN or an infinity.
+ *   E2M3: bias 1, emax = 2, subnormals m * 2^-3, normals (1 + m / 8) * 2^(e - 1) for e = 1 .. 3, largest finite value 7.5.
+ *   E3M2: bias 3, emax = 4, subnormals m * 2^-4, normals (1 + m / 4) * 2^(e - 3) for e = 1 .. 7, largest finite value 28.
+ *   Quantize: steps 1-7 above with these emax values; saturation to +-7.5 / +-28, also for an infinite x_i; a NaN x_i gives code 0 and takes no
+ *   part in amax (the E2M1 rule).  Dequantize: as above; there is no NaN code, s = 0xFF gives NaN.
+ *   codes, FP6: dense -- element i occupies bits [6i, 6i + 6) of the little-endian bit string of the byte array (bit k of the string is bit k % 8
+ *   of byte k / 8), so a full block is exactly bytes [24b, 24b + 24) and the array is ceil(6 * numel / 8) bytes; the bits of a ragged end that
+ *   belong to no element are 0.  scales: as above.  (mx_fp6_kernels.hpp; not measured past 2^31 elements.) */
+typedef enum {
+    PIQUANT_HIP_MX_FP4_E2M1 = 0,
+    PIQUANT_HIP_MX_FP8_E4M3 = 1,
+    PIQUANT_HIP_MX_FP6_E2M3 = 2,
+    PIQUANT_HIP_MX_FP6_E3M2 = 3
+} piquant_hip_mx_format_t;
 PIQUANT_EXPORT void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
                                             piquant_hip_mx_format_t fmt);
 PIQUANT_EXPORT void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out,

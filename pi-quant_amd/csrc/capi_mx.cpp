@@ -6,15 +6,25 @@
 
 using namespace pq;
 
-static_assert(PIQUANT_HIP_MX_FP4_E2M1 == MX_FP4_E2M1 && PIQUANT_HIP_MX_FP8_E4M3 == MX_FP8_E4M3, "piquant_hip_mx_format_t and the kernels' format codes");
+static_assert(PIQUANT_HIP_MX_FP4_E2M1 == MX_FP4_E2M1 && PIQUANT_HIP_MX_FP8_E4M3 == MX_FP8_E4M3 && PIQUANT_HIP_MX_FP6_E2M3 == MX_FP6_E2M3 &&
+                  PIQUANT_HIP_MX_FP6_E3M2 == MX_FP6_E3M2,
+              "piquant_hip_mx_format_t and the kernels' format codes");
 
 namespace {
 
-// What every MX call checks first; `float_name` is what the message calls the float side ("input", "output", "float type").
-void check_mx_call(const Where& w, const piquant_context_t* ctx, const char* float_name, piquant_dtype_t dtype, piquant_hip_mx_format_t fmt) {
+bool is_fp6(piquant_hip_mx_format_t fmt) { return fmt == PIQUANT_HIP_MX_FP6_E2M3 || fmt == PIQUANT_HIP_MX_FP6_E3M2; }
+
+// What every MX call checks first; `float_name` is what the message calls the float side ("input", "output", "float type").  The FP6 formats are
+// served by the two single calls only (`fp6`).
+void check_mx_call(const Where& w, const piquant_context_t* ctx, const char* float_name, piquant_dtype_t dtype, piquant_hip_mx_format_t fmt,
+                   bool fp6 = false) {
     if (!ctx) bad(w, "context is NULL");
     if (dtype != PIQUANT_DTYPE_F32 && dtype != PIQUANT_DTYPE_BF16) bad(w, "the %s must be float32 or bfloat16", float_name);
-    if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) bad(w, "the format must be FP4 E2M1 or FP8 E4M3");
+    if (is_fp6(fmt)) {
+        if (!fp6) bad(w, "FP6 is not supported here: the format must be FP4 E2M1 or FP8 E4M3 (FP6 E2M3 / E3M2: quantize_mx and dequantize_mx only)");
+    } else if (fmt != PIQUANT_HIP_MX_FP4_E2M1 && fmt != PIQUANT_HIP_MX_FP8_E4M3) {
+        bad(w, "the format must be FP4 E2M1, FP8 E4M3, FP6 E2M3 or FP6 E3M2");
+    }
 }
 
 void check_mx_op(const Where& w, piquant_reduce_op_t op) {
@@ -58,20 +68,23 @@ extern "C" {
 void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
                              piquant_hip_mx_format_t fmt) {
     const Where w {"piquant_hip_quantize_mx"};
-    check_mx_call(w, ctx, "input", dtype_in, fmt);
+    check_mx_call(w, ctx, "input", dtype_in, fmt, true);
     if (numel == 0) return;
     if (!in || !codes || !scales) bad(w, "NULL buffer");
     const CallLock lock(ctx);
     const MxQuantLaunch q {device_ptr(w, ctx->resolve_ptr(in)), device_ptr(w, ctx->resolve_ptr(codes)), mx_scales_ptr(w, scales), static_cast<int64_t>(numel),
                            dtype_in, fmt};
     check_element_aligned(w, "in", q.in, dtype_in);
-    run_call(ctx, false, [&] { launch_quantize_mx(q, ctx->stream, ctx->num_cu); });
+    run_call(ctx, false, [&] {
+        if (is_fp6(fmt)) launch_quantize_mx_fp6(q, ctx->stream, ctx->num_cu);
+        else launch_quantize_mx(q, ctx->stream, ctx->num_cu);
+    });
 }
 
 void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out, size_t numel,
                                piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
     const Where w {"piquant_hip_dequantize_mx"};
-    check_mx_call(w, ctx, "output", dtype_out, fmt);
+    check_mx_call(w, ctx, "output", dtype_out, fmt, true);
     check_mx_op(w, op);
     if (numel == 0) return;
     if (!codes || !scales || !out) bad(w, "NULL buffer");
@@ -80,7 +93,10 @@ void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const 
                              static_cast<int64_t>(numel), dtype_out, fmt, to_op(op)};
     check_element_aligned(w, "out", d.out, dtype_out);
     // the scale bytes are written by whatever was enqueued just before
-    run_call(ctx, true, [&] { launch_dequantize_mx(d, ctx->stream, ctx->num_cu); });
+    run_call(ctx, true, [&] {
+        if (is_fp6(fmt)) launch_dequantize_mx_fp6(d, ctx->stream, ctx->num_cu);
+        else launch_dequantize_mx(d, ctx->stream, ctx->num_cu);
+    });
 }
 
 void piquant_hip_reduce_quantize_mx(piquant_context_t* ctx, const void* acc, piquant_dtype_t dtype_acc, const void* const* codes, const uint8_t* const* scales,

@@ -258,7 +258,9 @@ void launch_clip_unsearched(int32_t* device_choice, double* device_errors, hipSt
 // The MX block formats (mx_kernels.hpp; kernels_mx.hip): 32 elements of FP4 E2M1 / FP8 E4M3 (fmt: MX_FP4_E2M1 = 0, MX_FP8_E4M3 = 1, the values of
 // piquant_hip_mx_format_t) under one E8M0 scale byte.  ONE launch each.  Every buffer 16-byte aligned: the streaming kernels; anything else (the
 // float side aligned to its element): the guarded ones, the same bytes.
-enum : int { MX_FP4_E2M1 = 0, MX_FP8_E4M3 = 1 };
+// MXFP6 (mx_fp6_kernels.hpp; kernels_mx_fp6.hip): MX_FP6_E2M3 = 2, MX_FP6_E3M2 = 3, 6-bit codes as a dense bit string (24 bytes a block), through
+// launchers of their own on the same launch records; the wire and the error-feedback launches below are FP4 / FP8 only.
+enum : int { MX_FP4_E2M1 = 0, MX_FP8_E4M3 = 1, MX_FP6_E2M3 = 2, MX_FP6_E3M2 = 3 };
 struct MxQuantLaunch {
     const void* in;        // numel elements of dt_in
     void* codes;           // ceil(numel * bits / 8) bytes
@@ -278,6 +280,8 @@ struct MxDequantLaunch {
 };
 void launch_quantize_mx(const MxQuantLaunch& q, hipStream_t stream, int num_cu);
 void launch_dequantize_mx(const MxDequantLaunch& d, hipStream_t stream, int num_cu);
+void launch_quantize_mx_fp6(const MxQuantLaunch& q, hipStream_t stream, int num_cu);
+void launch_dequantize_mx_fp6(const MxDequantLaunch& d, hipStream_t stream, int num_cu);
 // The MX wire (mx_reduce_kernels.hpp; kernels_mx_reduce.hip, kernels_mx_batch.hip): at most kMxMaxInputs terms, or batch members, per launch.
 //   reduce       (codes, scales) = quantize_mx(acc + sum_i dequantize_mx(term[i])), the terms added in order and the sum rounded to dt_acc after each;
 //                acc is only read.  ONE launch for 0 .. kMxMaxInputs terms: the streaming kernel when every buffer is 16-byte aligned, `guarded`

@@ -473,16 +473,16 @@ class Context:
                                          reduce_op.value)
 
     def quantize_mx_ptr(self, ptr_in: int, dtype_in: DataType, codes_ptr: int, scales_ptr: int, numel: int, fmt: int, _device_ptrs: bool = False) -> None:
-        """MX block quantize (``piquant_hip_quantize_mx``): ``fmt`` 0 = FP4 E2M1 (``ceil(numel / 2)`` code bytes), 1 = FP8 E4M3 (``numel``), one
-        E8M0 scale byte per 32 elements in ``scales_ptr``."""
-        assert dtype_in.is_dequantized and fmt in (0, 1)
+        """MX block quantize (``piquant_hip_quantize_mx``): ``fmt`` 0 = FP4 E2M1 (``ceil(numel / 2)`` code bytes), 1 = FP8 E4M3 (``numel``),
+        2 = FP6 E2M3, 3 = FP6 E3M2 (``ceil(6 * numel / 8)``, the dense 6-bit string), one E8M0 scale byte per 32 elements in ``scales_ptr``."""
+        assert dtype_in.is_dequantized and fmt in (0, 1, 2, 3)
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_quantize_mx(self._ctx, ptr_in, dtype_in.value, codes_ptr, scales_ptr, numel, fmt)
 
     def dequantize_mx_ptr(self, codes_ptr: int, scales_ptr: int, ptr_out: int, dtype_out: DataType, numel: int, fmt: int, reduce_op: ReduceOp,
                           _device_ptrs: bool = False) -> None:
         """MX block dequantize (``piquant_hip_dequantize_mx``), the buffers of ``quantize_mx_ptr``."""
-        assert dtype_out.is_dequantized and fmt in (0, 1)
+        assert dtype_out.is_dequantized and fmt in (0, 1, 2, 3)
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_dequantize_mx(self._ctx, codes_ptr, scales_ptr, ptr_out, dtype_out.value, numel, fmt, reduce_op.value)
 

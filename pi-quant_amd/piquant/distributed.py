@@ -17,6 +17,7 @@ import torch.distributed as dist
 
 from . import Context, DataType, decode_minmax_keys, quant_params_from_minmax
 from .torch import MX_FORMATS as _MX_FORMATS
+_MX_WIRE_FORMATS = ('fp4_e2m1', 'fp8_e4m3')   # what mx_format= accepts: the FP6 formats have no batch, reduce or error-feedback kernels yet
 from .torch import _QUANT_TYPES, _REDUCE_OPS, _ROUND_MODES, _ctx_for, _residual_dtype, torch_to_piquant_dtype
 
 
@@ -454,9 +455,12 @@ class MxWireLayout(NamedTuple):
 def mx_wire_layout(numel: int, format: str) -> MxWireLayout:
     """Layout of the MX wire record of a chunk of ``numel`` elements (``quantized_all_reduce(mx_format=...)``): nblocks = ceil(numel / 32) E8M0
     scale bytes, zero padding up to a multiple of 16 bytes, then the FP4 E2M1 (``ceil(numel / 2)`` bytes) or FP8 E4M3 (``numel`` bytes) codes --
-    one parameter byte per 32 elements where the grouped wire carries 5 per group.  The record of an empty chunk is empty."""
+    one parameter byte per 32 elements where the grouped wire carries 5 per group.  The record of an empty chunk is empty.  The FP6 formats are
+    not on the wire (ValueError)."""
     from .torch import mx_nbytes
 
+    if format not in _MX_WIRE_FORMATS:
+        raise ValueError(f'the MX wire format must be one of {sorted(_MX_WIRE_FORMATS)}, got {format!r}')
     ncodes, nblocks = mx_nbytes(numel, format)
     codes = -(-nblocks // 16) * 16
     return MxWireLayout(0, codes, codes + ncodes)
@@ -1493,8 +1497,8 @@ def _check_mx_format(mx_format, *, quant_dtype, round_mode, group_size, error_fe
     ``mx_error_feedback``, is what ``error_feedback_requantize`` goes with here."""
     if mx_format is None:
         return
-    if not (isinstance(mx_format, str) and mx_format in _MX_FORMATS):
-        raise ValueError(f'mx_format must be None or one of {sorted(_MX_FORMATS)}, got {mx_format!r}')
+    if not (isinstance(mx_format, str) and mx_format in _MX_WIRE_FORMATS):
+        raise ValueError(f'mx_format must be None or one of {sorted(_MX_WIRE_FORMATS)}, got {mx_format!r}')
     if group_size != default_group_size:
         raise ValueError('mx_format= is not supported with group_size= (an MX block is 32 elements under one scale byte; leave group_size at its default)')
     for name, given in (('error_feedback', error_feedback is not None), ('error_feedback_requantize', bool(error_feedback_requantize) and mx_error_feedback is None),

@@ -719,18 +719,22 @@ def dequantize_grouped(tensor: torch.Tensor, scales: torch.Tensor, zero_points: 
     return out
 
 
-# ---- MX block formats: 32 elements of FP4 E2M1 / FP8 E4M3 under one power-of-two scale byte ------------------------------------------------
+# ---- MX block formats: 32 elements of FP4 E2M1 / FP6 E2M3 / FP6 E3M2 / FP8 E4M3 under one power-of-two scale byte --------------------------
 MX_BLOCK = 32
-MX_FORMATS: dict[str, int] = {'fp4_e2m1': 0, 'fp8_e4m3': 1}   # piquant_hip_mx_format_t
+MX_FORMATS: dict[str, int] = {'fp4_e2m1': 0, 'fp8_e4m3': 1, 'fp6_e2m3': 2, 'fp6_e3m2': 3}   # piquant_hip_mx_format_t
+_MX_FP6 = ('fp6_e2m3', 'fp6_e3m2')   # quantize_mx and dequantize_mx only
 
 
 def mx_nbytes(numel: int, format: str) -> Tuple[int, int]:
-    """(code bytes, scale bytes) of ``numel`` elements in an MX format."""
-    return ((int(numel) + 1) // 2 if MX_FORMATS[format] == 0 else int(numel)), (int(numel) + MX_BLOCK - 1) // MX_BLOCK
+    """(code bytes, scale bytes) of ``numel`` elements in an MX format; the FP6 codes are a dense 6-bit string, ``ceil(6 * numel / 8)`` bytes."""
+    numel, fmt = int(numel), MX_FORMATS[format]
+    return ((numel + 1) // 2 if fmt == 0 else numel if fmt == 1 else (3 * numel + 3) // 4), (numel + MX_BLOCK - 1) // MX_BLOCK
 
 
-def _check_mx_format(format) -> None:
+def _check_mx_format(format, fp6: bool = False) -> None:
+    """``fp6``: whether the call serves the FP6 formats (the two single calls do; the batch, wire and error-feedback calls do not yet)."""
     _require(isinstance(format, str) and format in MX_FORMATS, f'format must be one of {sorted(MX_FORMATS)}, got {format!r}')
+    _require(fp6 or format not in _MX_FP6, f'{format} is not supported here: FP6 is served by quantize_mx and dequantize_mx only')
 
 
 def _check_mx_bytes(t, nbytes: int, what: str) -> None:
@@ -741,11 +745,13 @@ def _check_mx_bytes(t, nbytes: int, what: str) -> None:
 def quantize_mx(tensor: torch.Tensor, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
                 out_scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """OCP microscaling quantization (``include/piquant_hip.h``, piquant_hip_quantize_mx): the flattened tensor is cut into blocks of 32 elements
-    (the last may be ragged), each stored as FP4 E2M1 (``'fp4_e2m1'``) or FP8 E4M3 (``'fp8_e4m3'``) codes under one power-of-two scale byte.
-    Nearest rounding, ties to even, saturating.  Returns (codes, scales), flat uint8 tensors on the tensor's device: ``ceil(numel / 2)`` (FP4, even
-    index in the low nibble) or ``numel`` (FP8) code bytes and ``ceil(numel / 32)`` scale bytes.  They ``.view()`` as
-    ``torch.float4_e2m1fn_x2`` / ``torch.float8_e4m3fn`` and ``torch.float8_e8m0fnu``.  One asynchronous launch on the current stream."""
-    _check_mx_format(format)
+    (the last may be ragged), each stored as FP4 E2M1 (``'fp4_e2m1'``), FP6 E2M3 (``'fp6_e2m3'``), FP6 E3M2 (``'fp6_e3m2'``) or FP8 E4M3
+    (``'fp8_e4m3'``) codes under one power-of-two scale byte.  Nearest rounding, ties to even, saturating.  Returns (codes, scales), flat uint8
+    tensors on the tensor's device: ``ceil(numel / 2)`` (FP4, even index in the low nibble), ``ceil(6 * numel / 8)`` (FP6: element i in bits
+    [6i, 6i + 6) of the little-endian bit string, 24 bytes a block) or ``numel`` (FP8) code bytes and ``ceil(numel / 32)`` scale bytes.  FP4 and
+    FP8 ``.view()`` as ``torch.float4_e2m1fn_x2`` / ``torch.float8_e4m3fn``, the scales as ``torch.float8_e8m0fnu``.  One asynchronous launch on
+    the current stream."""
+    _check_mx_format(format, fp6=True)
     _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
     ncodes, nscales = mx_nbytes(tensor.numel(), format)
     if out is not None:
@@ -769,13 +775,14 @@ def dequantize_mx(codes: torch.Tensor, scales: torch.Tensor, *, format: str, dty
                   ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Inverse of ``quantize_mx``: element i of the result (``reduce_op='set'``) or of ``out`` (``'add'``) is ``value(code_i) * 2^(scales[i // 32] -
     127)``; scale byte 0xFF and the FP8 NaN codes give NaN.  ``shape`` is the logical shape (``out``'s, or flat over every code, by default); its
-    element count decides how many codes are read -- an FP4 buffer alone cannot tell an odd count from the next even one."""
-    _check_mx_format(format)
+    element count decides how many codes are read -- an FP4 buffer alone cannot tell an odd count from the next even one, nor an FP6 buffer
+    (``'fp6_e2m3'`` / ``'fp6_e3m2'``) a count from the next one that fills the same bytes: the default is the largest, ``8 * bytes // 6``."""
+    _check_mx_format(format, fp6=True)
     _check_modes(float_dtype=dtype, reduce_op=reduce_op)
     _require(isinstance(codes, torch.Tensor) and codes.dtype == torch.uint8 and codes.dim() == 1 and codes.is_contiguous(),
              'codes must be a contiguous 1-D uint8 tensor')
     if shape is None:
-        shape = out.shape if isinstance(out, torch.Tensor) else (codes.numel() * (2 if MX_FORMATS[format] == 0 else 1),)
+        shape = out.shape if isinstance(out, torch.Tensor) else ({0: codes.numel() * 2, 1: codes.numel()}.get(MX_FORMATS[format], codes.numel() * 8 // 6),)
     numel = _numel_of(shape)
     ncodes, nscales = mx_nbytes(numel, format)
     _require(codes.numel() == ncodes, f'codes holds {codes.numel()} bytes, {numel} {format} elements are {ncodes}')

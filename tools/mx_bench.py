@@ -26,6 +26,12 @@ reduce_quantize_mx_ef (float32 / bfloat16 + 1 / 7 FP4 terms) against a copy of a
 rotate like the floats.
 
     python tools/mx_bench.py --rows ef [--windows 7] [--rotate-gb 3.3] [--out FILE]
+
+--rows fp6 measures quantize_mx, dequantize_mx SET and dequantize_mx ADD in FP6 E2M3 and E3M2 for both float types, each next to the FP4 and the
+FP8 call of the same shape in the same run (the four formats in turn, same protocol) and writes profiles/mx_fp6_bench.json: an FP6 row says
+whether its time is within 1.15 x the FP8 time x the ratio of their algorithmic bytes ("met" / "missed") and whether it is below the FP8 time.
+
+    python tools/mx_bench.py --rows fp6 [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -302,15 +308,68 @@ def ef_main(args):
     print(f"wrote {args.out}")
 
 
+def fp6_main(args):
+    """quantize_mx and dequantize_mx (SET and ADD) in the two FP6 formats next to the FP4 and FP8 calls of the same shape (module docstring)."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    ctx = piquant.Context.get(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_blocking(False)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    SET, ADD = piquant.ReduceOp.SET, piquant.ReduceOp.ADD
+    fmts = ("fp4_e2m1", "fp6_e2m3", "fp6_e3m2", "fp8_e4m3")
+    nblocks = pt.mx_nbytes(NUMEL, "fp8_e4m3")[1]
+    rows = []
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
+        per_window = max(2 * nbuf, 32)
+        xs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=gen).to(tdt) for _ in range(nbuf)]
+        ys = [torch.zeros(NUMEL, dtype=tdt, device=dev) for _ in range(nbuf)]
+        codes = {fmt: [torch.empty(pt.mx_nbytes(NUMEL, fmt)[0], dtype=torch.uint8, device=dev) for _ in range(nbuf)] for fmt in fmts}
+        mxs = {fmt: [torch.empty(nblocks, dtype=torch.uint8, device=dev) for _ in range(nbuf)] for fmt in fmts}
+        quant = {fmt: (lambda i, fmt=fmt: ctx.quantize_mx_ptr(xs[i].data_ptr(), fdt, codes[fmt][i].data_ptr(), mxs[fmt][i].data_ptr(), NUMEL, pt.MX_FORMATS[fmt],
+                                                              _device_ptrs=True)) for fmt in fmts}
+        results = [("quantize_mx", 1, timed_alternating(quant, nbuf, args.windows, per_window, stream))]
+        for name, op, passes in (("dequantize_mx SET", SET, 1), ("dequantize_mx ADD", ADD, 2)):   # the codes quantize_mx left; ADD reads and writes the floats
+            dequant = {fmt: (lambda i, fmt=fmt, op=op: ctx.dequantize_mx_ptr(codes[fmt][i].data_ptr(), mxs[fmt][i].data_ptr(), ys[i].data_ptr(), fdt, NUMEL,
+                                                                              pt.MX_FORMATS[fmt], op, _device_ptrs=True)) for fmt in fmts}
+            results.append((name, passes, timed_alternating(dequant, nbuf, args.windows, per_window, stream)))
+        for kind, passes, res in results:
+            nbytes = {fmt: passes * NUMEL * esize + pt.mx_nbytes(NUMEL, fmt)[0] + nblocks for fmt in fmts}
+            for fmt in ("fp4_e2m1", "fp8_e4m3"):
+                rows.append(row(kind, f"{fname} {fmt}", res[fmt][0], nbytes[fmt], res[fmt][1]))
+            for fmt in ("fp6_e2m3", "fp6_e3m2"):
+                r = row(kind, f"{fname} {fmt}", res[fmt][0], nbytes[fmt], res[fmt][1])
+                r["over_fp8"], r["byte_ratio"] = round(res[fmt][0] / res["fp8_e4m3"][0], 3), round(nbytes[fmt] / nbytes["fp8_e4m3"], 3)
+                r["target"] = "met" if res[fmt][0] <= 1.15 * res["fp8_e4m3"][0] * nbytes[fmt] / nbytes["fp8_e4m3"] else "missed"
+                r["faster_than_fp8"] = bool(res[fmt][0] < res["fp8_e4m3"][0])
+                print(f"    FP6 / FP8 = {r['over_fp8']:.3f}, bytes {r['byte_ratio']:.3f}: {r['target']}", flush=True)
+                rows.append(r)
+        del xs, ys, codes, mxs
+        torch.cuda.empty_cache()
+    out = {"numel": NUMEL, "device": torch.cuda.get_device_name(0), "windows": args.windows, "rotate_gb": args.rotate_gb,
+           "command": "python tools/mx_bench.py --rows fp6",
+           "protocol": "alternating windows of back-to-back calls (FP4, E2M3, E3M2, FP8 in turn), HIP events, median over windows; rotated float and code "
+                       "buffers; target: FP6 us <= 1.15 x FP8 us x FP6 bytes / FP8 bytes",
+           "spread": "run-to-run spread not measured (one run); every row carries its windows",
+           "not_measured": "other sizes, the guarded kernels, past 2^31 elements", "rows": rows}
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print(f"wrote {args.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", choices=("calls", "wire", "ef"), default="calls")
+    ap.add_argument("--rows", choices=("calls", "wire", "ef", "fp6"), default="calls")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / {"calls": "mx_bench.json", "wire": "mx_wire_bench.json", "ef": "mx_ef_bench.json"}[args.rows])
+        args.out = str(ROOT / "profiles" / {"calls": "mx_bench.json", "wire": "mx_wire_bench.json", "ef": "mx_ef_bench.json", "fp6": "mx_fp6_bench.json"}[args.rows])
+    if args.rows == "fp6":
+        return fp6_main(args)
     if args.rows == "wire":
         return wire_main(args)
     if args.rows == "ef":
