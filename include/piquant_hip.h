@@ -708,7 +708,7 @@ PIQUANT_EXPORT int piquant_hip_peer_timeout(piquant_context_t* ctx, uint32_t* ou
  *   scales:      uint8[nblocks], linear.  Byte s means 2^(s - 127); 0xFF means NaN.
  *   E2M1: values +-{0, 0.5, 1, 1.5, 2, 3, 4, 6}, emax = 2, no NaN, no infinity.  E4M3 (the "fn" variant): emax = 8, largest finite value 448,
  *   subnormals down to 2^-9, 0x7F and 0xFF are NaN, no infinity.
- * piquant_hip_quantize_mx (nearest only), block b with elements x_i widened exactly to float32:
+ * piquant_hip_quantize_mx (nearest; piquant_hip_quantize_mx_sr below rounds stochastically), block b with elements x_i widened exactly to float32:
  *   1. amax = the largest |x_i| over the elements that are not NaN (infinities take part); 0 when there is none.
  *   2. E = max(exponent field of amax, 1): a zero or denormal amax counts as exponent -126, an infinite one gives E = 255.
  *   3. s = max(E - emax, 0), never 0xFF; scales[b] = s.
@@ -745,6 +745,33 @@ PIQUANT_EXPORT void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* 
                                             piquant_hip_mx_format_t fmt);
 PIQUANT_EXPORT void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out,
                                               size_t numel, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op);
+
+/* Stochastic rounding for the MX formats: E[dequantize_mx(quantize_mx_sr(x))] = x for every finite x, at no cost in memory.
+ * piquant_hip_quantize_mx_sr, all four formats: a 64-bit `seed` and a 64-bit `index_base`; element i of the call has the global index
+ *   g = index_base + i (modulo 2^64).  Everything not stated here -- widening, NaN left out of amax, NaN and infinity codes, an all-NaN block, the
+ *   ragged last block, code packing, the scale bytes' layout -- is exactly piquant_hip_quantize_mx's.
+ *   Scale with headroom.  E and M are the exponent and mantissa fields of the block's amax (float32); s0 = max(E - emax, 0) as in the nearest call.
+ *     If emax <= E < 255 and M is greater than the mantissa field of the format's top magnitude, s = s0 + 1; otherwise s = s0.  The top mantissa
+ *     fields: E2M1 6.0 -> 0x400000, E2M3 7.5 -> 0x700000, E3M2 28 -> 0x600000, E4M3 448 -> 0x600000.  With this rule no finite element exceeds the
+ *     top in the scaled domain: nothing is clipped, so the rounding is unbiased.  An infinite amax keeps the nearest call's rule (s = 255 - emax).
+ *   Rounding.  v = |x_i| * 2^(127 - s) as an exact real; lo is the largest magnitude of the format <= v and hi the next one up, the format's
+ *     denormals included; f = (v - lo) / (hi - lo); t = floor(element_threshold(seed, g) * 2^24), the counter hash of the per-element stochastic
+ *     mode: mix32(lo32(g) ^ (mix32(hi32(g) ^ hi32(seed)) + lo32(seed))) >> 8.  The magnitude is hi iff floor(f * 2^24) + t >= 2^24, otherwise lo; the
+ *     sign bit is x_i's.  A representable v never moves (f = 0).  P(hi) = floor(f * 2^24) / 2^24: exactly f for every float32 input whose discarded
+ *     mantissa is at most 24 bits wide, which is every element that lands in the format's normal range.  Infinite and NaN elements encode as in the
+ *     nearest call.
+ *   Two calls on the halves of a tensor cut at a multiple of 32 elements, each with its offset added to index_base, write the bytes of the one call.
+ * piquant_hip_quantize_mx_sr_batch, FP4 and FP8 (FP6 is refused, as by every batch): member i gets the bytes of the single call with
+ *   index_bases[i]; ONE launch per 16 members, the rules of piquant_hip_quantize_mx_batch.
+ * Both: the launch and alignment rules of the nearest calls (streaming kernels for 16-byte aligned buffers, guarded kernels with the same bytes
+ * otherwise); seed and bases travel by value, no host synchronisation, no allocation (hipGraph-capturable); numel == 0 is a no-op.  The codes are
+ * rounded in integer arithmetic and encoded by the nearest conversions; gfx950's own stochastic conversions take one random word per pair (FP4) or
+ * per 32 elements (FP6) and are not used (mx_kernels.hpp). */
+PIQUANT_EXPORT void piquant_hip_quantize_mx_sr(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales,
+                                               size_t numel, piquant_hip_mx_format_t fmt, uint64_t seed, uint64_t index_base);
+PIQUANT_EXPORT void piquant_hip_quantize_mx_sr_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes,
+                                                     uint8_t* const* scales, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt,
+                                                     uint64_t seed, const uint64_t* index_bases);
 
 /* The MX wire: the four calls that make a quantized collective over MX records a handful of launches.  Each is DEFINED as a composition of the two
  * calls above (nearest only, like them); `fmt` is one format for the terms and the result; term i is (codes[i], scales[i]) of `numel` elements.

@@ -1,5 +1,6 @@
 // The MX entry points of include/piquant_hip.h (mx_kernels.hpp, mx_reduce_kernels.hpp, mx_ef_kernels.hpp): fixed blocks of 32 FP4 E2M1 / FP8 E4M3
-// codes under one E8M0 scale byte -- no groups, no zero points, no round mode, so nothing is drawn.  The two single calls, the wire (the fused reduce,
+// codes under one E8M0 scale byte -- no groups, no zero points, and the rounding of the stochastic calls is a function of (seed, index) the caller
+// passes, so nothing is drawn.  The two single calls and the stochastic quantize (one body: quantize_mx_call, quantize_mx_batch_call), the wire (the fused reduce,
 // the dequantize-sum and the two batches) and the three error-feedback calls on a float32 residual.  All are stream-ordered, take device (or pinned) buffers only and read as capi_frame.hpp says; the terms of the
 // wire are resolved without allocating (at most kMxMaxInputs a launch, on the stack).
 #include "capi_frame.hpp"
@@ -61,24 +62,59 @@ bool resolve_mx_terms(const piquant_context_t* ctx, const char* entry, const voi
     return aligned;
 }
 
+// piquant_hip_quantize_mx and piquant_hip_quantize_mx_sr (stochastic: seed and index_base travel by value into the launch)
+void quantize_mx_call(const Where& w, piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
+                      piquant_hip_mx_format_t fmt, bool stochastic, uint64_t seed, uint64_t index_base) {
+    check_mx_call(w, ctx, "input", dtype_in, fmt, true);
+    if (numel == 0) return;
+    if (!in || !codes || !scales) bad(w, "NULL buffer");
+    const CallLock lock(ctx);
+    const MxQuantLaunch q {device_ptr(w, ctx->resolve_ptr(in)), device_ptr(w, ctx->resolve_ptr(codes)), mx_scales_ptr(w, scales), static_cast<int64_t>(numel),
+                           dtype_in, fmt, stochastic, seed, index_base};
+    check_element_aligned(w, "in", q.in, dtype_in);
+    run_call(ctx, false, [&] {
+        if (is_fp6(fmt)) launch_quantize_mx_fp6(q, ctx->stream, ctx->num_cu);
+        else launch_quantize_mx(q, ctx->stream, ctx->num_cu);
+    });
+}
+
+// The batches: run_batch's rule, with "streams" meaning every buffer of the member 16-byte aligned; a member that is not runs alone through the
+// single launch (the guarded kernel, the same bytes).  index_bases: NULL for the nearest batch, else the stochastic one's (member i: index_bases[i]).
+void quantize_mx_batch_call(const char* entry, piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes,
+                            uint8_t* const* scales, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt, uint64_t seed,
+                            const uint64_t* index_bases) {
+    check_mx_call(Where {entry}, ctx, "float type", dtype_in, fmt);
+    if (count == 0) return;
+    if (!inputs || !codes || !scales || !numels) panic("%s: NULL argument", entry);
+    const CallLock lock(ctx);
+    MxQuantBatchLaunch b {};
+    run_call(ctx, false, [&] {
+        run_batch(
+            b, numels, count,
+            [&](size_t i) {
+                const Where w {entry, static_cast<long>(i)};
+                if (!inputs[i] || !codes[i] || !scales[i]) bad(w, "NULL buffer");
+                return MxQuantLaunch {mx_float_ptr(ctx, w, inputs[i], dtype_in), device_ptr(w, ctx->resolve_ptr(codes[i])), mx_scales_ptr(w, scales[i]),
+                                      static_cast<int64_t>(numels[i]), dtype_in, fmt, index_bases != nullptr, seed, index_bases ? index_bases[i] : 0};
+            },
+            [](const MxQuantLaunch& q) { return aligned16(q.in) && aligned16(q.codes) && aligned16(q.scales); },
+            [&](const MxQuantLaunch& q) { launch_quantize_mx(q, ctx->stream, ctx->num_cu); },
+            [&] { launch_quantize_mx_batch(b, ctx->stream); });
+    });
+}
+
 }  // namespace
 
 extern "C" {
 
 void piquant_hip_quantize_mx(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
                              piquant_hip_mx_format_t fmt) {
-    const Where w {"piquant_hip_quantize_mx"};
-    check_mx_call(w, ctx, "input", dtype_in, fmt, true);
-    if (numel == 0) return;
-    if (!in || !codes || !scales) bad(w, "NULL buffer");
-    const CallLock lock(ctx);
-    const MxQuantLaunch q {device_ptr(w, ctx->resolve_ptr(in)), device_ptr(w, ctx->resolve_ptr(codes)), mx_scales_ptr(w, scales), static_cast<int64_t>(numel),
-                           dtype_in, fmt};
-    check_element_aligned(w, "in", q.in, dtype_in);
-    run_call(ctx, false, [&] {
-        if (is_fp6(fmt)) launch_quantize_mx_fp6(q, ctx->stream, ctx->num_cu);
-        else launch_quantize_mx(q, ctx->stream, ctx->num_cu);
-    });
+    quantize_mx_call(Where {"piquant_hip_quantize_mx"}, ctx, in, dtype_in, codes, scales, numel, fmt, false, 0, 0);
+}
+
+void piquant_hip_quantize_mx_sr(piquant_context_t* ctx, const void* in, piquant_dtype_t dtype_in, void* codes, uint8_t* scales, size_t numel,
+                                piquant_hip_mx_format_t fmt, uint64_t seed, uint64_t index_base) {
+    quantize_mx_call(Where {"piquant_hip_quantize_mx_sr"}, ctx, in, dtype_in, codes, scales, numel, fmt, true, seed, index_base);
 }
 
 void piquant_hip_dequantize_mx(piquant_context_t* ctx, const void* codes, const uint8_t* scales, void* out, piquant_dtype_t dtype_out, size_t numel,
@@ -152,31 +188,20 @@ void piquant_hip_dequantize_sum_mx(piquant_context_t* ctx, const void* const* co
     });
 }
 
-// The batches: run_batch's rule, with "streams" meaning every buffer of the member 16-byte aligned; a member that is not runs alone through the
-// single launch (the guarded kernel, the same bytes).
 void piquant_hip_quantize_mx_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes, uint8_t* const* scales,
                                    const size_t* numels, size_t count, piquant_hip_mx_format_t fmt) {
-    const char* entry = "piquant_hip_quantize_mx_batch";
-    check_mx_call(Where {entry}, ctx, "float type", dtype_in, fmt);
-    if (count == 0) return;
-    if (!inputs || !codes || !scales || !numels) panic("%s: NULL argument", entry);
-    const CallLock lock(ctx);
-    MxQuantBatchLaunch b {};
-    run_call(ctx, false, [&] {
-        run_batch(
-            b, numels, count,
-            [&](size_t i) {
-                const Where w {entry, static_cast<long>(i)};
-                if (!inputs[i] || !codes[i] || !scales[i]) bad(w, "NULL buffer");
-                return MxQuantLaunch {mx_float_ptr(ctx, w, inputs[i], dtype_in), device_ptr(w, ctx->resolve_ptr(codes[i])), mx_scales_ptr(w, scales[i]),
-                                      static_cast<int64_t>(numels[i]), dtype_in, fmt};
-            },
-            [](const MxQuantLaunch& q) { return aligned16(q.in) && aligned16(q.codes) && aligned16(q.scales); },
-            [&](const MxQuantLaunch& q) { launch_quantize_mx(q, ctx->stream, ctx->num_cu); },
-            [&] { launch_quantize_mx_batch(b, ctx->stream); });
-    });
+    quantize_mx_batch_call("piquant_hip_quantize_mx_batch", ctx, inputs, dtype_in, codes, scales, numels, count, fmt, 0, nullptr);
 }
 
+void piquant_hip_quantize_mx_sr_batch(piquant_context_t* ctx, const void* const* inputs, piquant_dtype_t dtype_in, void* const* codes,
+                                      uint8_t* const* scales, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt, uint64_t seed,
+                                      const uint64_t* index_bases) {
+    const char* entry = "piquant_hip_quantize_mx_sr_batch";
+    if (count != 0 && !index_bases) panic("%s: NULL argument", entry);
+    quantize_mx_batch_call(entry, ctx, inputs, dtype_in, codes, scales, numels, count, fmt, seed, index_bases);
+}
+
+// run_batch's rule again (quantize_mx_batch_call has it).
 void piquant_hip_dequantize_mx_batch(piquant_context_t* ctx, const void* const* codes, const uint8_t* const* scales, void* const* outputs,
                                      piquant_dtype_t dtype_out, const size_t* numels, size_t count, piquant_hip_mx_format_t fmt, piquant_reduce_op_t op) {
     const char* entry = "piquant_hip_dequantize_mx_batch";

@@ -23,8 +23,17 @@ void launch_quantize_mx(const MxQuantLaunch& q, hipStream_t stream, int num_cu) 
         constexpr int DT_IN = decltype(di)::value;
         with_mx_format(q.fmt, [&](auto fi) {
             constexpr int FMT = decltype(fi)::value;
-            if (streams) {
-                constexpr int64_t TE = MxQuantTile<DT_IN, FMT>::TILE_ELEMS;
+            constexpr int64_t TE = MxQuantTile<DT_IN, FMT>::TILE_ELEMS;
+            if (q.stochastic) {
+                if (streams) {
+                    const dim3 grid(grouped_blocks((q.numel + TE - 1) / TE, "quantize_mx_sr"));
+                    PQ_LAUNCH((quantize_mx_sr_kernel<DT_IN, FMT>), grid, dim3(kGroupedBlock), 0, stream, q.in, codes, q.scales, q.numel, nblocks, q.seed,
+                              q.index_base);
+                } else {
+                    PQ_LAUNCH((quantize_mx_sr_guarded_kernel<DT_IN, FMT>), dim3(mx_guarded_blocks(nblocks, num_cu)), dim3(kGroupedBlock), 0, stream, q.in, codes,
+                              q.scales, q.numel, nblocks, q.seed, q.index_base);
+                }
+            } else if (streams) {
                 const dim3 grid(grouped_blocks((q.numel + TE - 1) / TE, "quantize_mx"));
                 PQ_LAUNCH((quantize_mx_kernel<DT_IN, FMT>), grid, dim3(kGroupedBlock), 0, stream, q.in, codes, q.scales, q.numel, nblocks);
             } else {

@@ -31,6 +31,13 @@ void launch_quantize_mx_batch(const MxQuantBatchLaunch& b, hipStream_t stream) {
             a.count = b.count;
             const int64_t chunks = fill_chunk_table(a, MxQuantTile<DT, FMT>::TILE_ELEMS);
             if (chunks == 0) return;
+            if (b.t[0].stochastic) {
+                MxSrBatchArgs sr {};
+                sr.seed = b.t[0].seed;
+                for (int t = 0; t < b.count; ++t) sr.index_base[t] = b.t[t].index_base;
+                PQ_LAUNCH((quantize_mx_sr_batch_kernel<DT, FMT>), dim3(grouped_blocks(chunks, "quantize_mx_sr_batch")), dim3(kGroupedBlock), 0, stream, a, sr);
+                return;
+            }
             PQ_LAUNCH((quantize_mx_batch_kernel<DT, FMT>), dim3(grouped_blocks(chunks, "quantize_mx_batch")), dim3(kGroupedBlock), 0, stream, a);
         });
     });

@@ -34,7 +34,16 @@ void launch_quantize_mx_fp6(const MxQuantLaunch& q, hipStream_t stream, int num_
         constexpr int DT_IN = decltype(di)::value;
         with_mx_fp6_format(q.fmt, [&](auto fi) {
             constexpr int FMT = decltype(fi)::value;
-            if (streams) {
+            if (q.stochastic) {
+                if (streams) {
+                    const dim3 grid(grouped_blocks((q.numel + kMx6TileElems - 1) / kMx6TileElems, "quantize_mx_sr (FP6)"));
+                    PQ_LAUNCH((quantize_mx_fp6_sr_kernel<DT_IN, FMT>), grid, dim3(kGroupedBlock), 0, stream, q.in, codes, q.scales, q.numel, nblocks, q.seed,
+                              q.index_base);
+                } else {
+                    PQ_LAUNCH((quantize_mx_fp6_sr_guarded_kernel<DT_IN, FMT>), dim3(mx_guarded_blocks(nblocks, num_cu)), dim3(kGroupedBlock), 0, stream, q.in,
+                              codes, q.scales, q.numel, nblocks, q.seed, q.index_base);
+                }
+            } else if (streams) {
                 const dim3 grid(grouped_blocks((q.numel + kMx6TileElems - 1) / kMx6TileElems, "quantize_mx (FP6)"));
                 PQ_LAUNCH((quantize_mx_fp6_kernel<DT_IN, FMT>), grid, dim3(kGroupedBlock), 0, stream, q.in, codes, q.scales, q.numel, nblocks);
             } else {

@@ -268,6 +268,12 @@ struct MxQuantLaunch {
     int64_t numel;
     int dt_in;             // DT_F32 / DT_BF16
     int fmt;
+    // piquant_hip_quantize_mx_sr: stochastic rounding, element i at global index index_base + i.  The launchers of the nearest call and of its batch
+    // take it (all four formats / FP4 and FP8; a batch: t[0]'s `stochastic` and seed, every member's own base) and launch kernels of their own for
+    // it; every other user of the record leaves it nearest.
+    bool stochastic = false;
+    uint64_t seed = 0;
+    uint64_t index_base = 0;
 };
 struct MxDequantLaunch {
     const void* codes;

@@ -119,6 +119,34 @@ __device__ __forceinline__ void mx6_encode(uint32_t (&w)[kMx6Words<DT_IN>], uint
     }
 }
 
+// The same with stochastic rounding (keys: mx_sr_keys of the global index of the block's first element): the scale byte with headroom, every element
+// rounded in the scaled domain (mx_sr_round; bfloat16 widened first, which is exact) and the float32 conversion under the scale operand 1.0 for both
+// input types -- v_cvt_scalef32_sr_pk32_* draws ONE random word for its 32 elements and cannot follow the definition.
+template <int FMT, int DT_IN>
+__device__ __forceinline__ void mx6_encode_sr(const uint32_t (&w)[kMx6Words<DT_IN>], const MxSrKeys& keys, uint32_t& s, u32x6& c) {
+    auto elem = [&](int i) {                                        // the float32 bits of element i, a NaN replaced by +0
+        uint32_t x;
+        if constexpr (DT_IN == DT_F32) x = w[(i & 1) * 16 + (i >> 1)];
+        else x = i & 1 ? w[i >> 1] & 0xffff0000u : w[i >> 1] << 16;
+        return mx_is_nan(x) ? 0u : x;
+    };
+    uint32_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+        const uint32_t k = elem(i) & 0x7fffffffu;
+        m = k > m ? k : m;
+    }
+    s = mx_sr_scale_byte<FMT>(m);
+    f32x16 a, b;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        a[j] = __uint_as_float(mx_sr_round<FMT>(elem(2 * j), s, mx_sr_threshold(keys, 2 * j)));
+        b[j] = __uint_as_float(mx_sr_round<FMT>(elem(2 * j + 1), s, mx_sr_threshold(keys, 2 * j + 1)));
+    }
+    if constexpr (FMT == MX_FP6_E2M3) c = __builtin_amdgcn_cvt_scalef32_2xpk16_fp6_f32(a, b, mx_scale_operand(127u));
+    else c = __builtin_amdgcn_cvt_scalef32_2xpk16_bf6_f32(a, b, mx_scale_operand(127u));
+}
+
 // the block's 32 values in order, as float32
 template <int FMT>
 __device__ __forceinline__ f32x32 mx6_decode_f32(const u32x6& c, float scale) {
@@ -217,6 +245,101 @@ quantize_mx_fp6_guarded_kernel(const void* __restrict__ in, uint8_t* __restrict_
         uint32_t s;
         u32x6 c;
         mx6_encode<FMT, DT_IN>(w, s, c);
+        scales[b] = static_cast<uint8_t>(s);
+        const int nbytes = (n * 6 + 7) / 8;
+#pragma unroll
+        for (int k = 0; k < kMx6BlockBytes; ++k)
+            if (k < nbytes) codes[b * kMx6BlockBytes + k] = static_cast<uint8_t>(c[k >> 2] >> ((k & 3) * 8));
+    }
+}
+
+// The same tile with stochastic rounding: element i of the tensor at the global index index_base + i (seed and base by value: capturable).
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_fp6_sr_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks,
+                          uint64_t seed, uint64_t index_base) {
+    constexpr int EPV = InVec<DT_IN>::EPV, NV = kMx6TileElems / (64 * EPV), N = kMx6Words<DT_IN>;
+    using S = Mx6Slice<N * 4>;
+    constexpr int WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_stage[WAVES][S::BYTES];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    const int64_t e0 = tile * kMx6TileElems;
+    if (e0 >= numel) return;
+    const bool full = e0 + kMx6TileElems <= numel;                  // wave-uniform
+    uint8_t* stage = s_stage[wave];
+
+    u32x4 raw[NV];
+    grouped_load<DT_IN, NV>(in, numel, e0 / EPV, lane, full, raw);
+#pragma unroll
+    for (int r = 0; r < NV; ++r) {
+        const int v = r * 64 + lane;
+        if constexpr (DT_IN == DT_F32) {
+            uint8_t* dst = stage + (v >> 3) * S::STRIDE + (v & 7) * 8;
+            *reinterpret_cast<u32x2*>(dst) = u32x2 {raw[r][0], raw[r][2]};
+            *reinterpret_cast<u32x2*>(dst + 64) = u32x2 {raw[r][1], raw[r][3]};
+        } else {
+            *reinterpret_cast<u32x4*>(stage + (v >> 2) * S::STRIDE + (v & 3) * 16) = raw[r];
+        }
+    }
+    wave_lds_sync();
+
+    uint32_t w[N];
+#pragma unroll
+    for (int k = 0; k < N / 4; ++k) {
+        const u32x4 t = *reinterpret_cast<const u32x4*>(stage + lane * S::STRIDE + k * 16);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[4 * k + e] = t[e];
+    }
+    uint32_t s;
+    u32x6 c;
+    mx6_encode_sr<FMT, DT_IN>(w, mx_sr_keys(seed, index_base + static_cast<uint64_t>(e0 + lane * kMxBlock)), s, c);
+    wave_lds_sync();                                                // every lane has read its block: the slice is free for the codes
+
+#pragma unroll
+    for (int k = 0; k < 3; ++k) reinterpret_cast<u32x2*>(stage + lane * kMx6BlockBytes)[k] = u32x2 {c[2 * k], c[2 * k + 1]};
+    stage[S::SCALES_AT + lane] = static_cast<uint8_t>(s);
+    wave_lds_sync();
+
+    uint8_t* o = codes + tile * kMx6TileBytes;
+    uint8_t* osc = scales + tile * 64;
+    if (full) {
+        st<ST_WT>(reinterpret_cast<u32x4*>(o) + lane, reinterpret_cast<const u32x4*>(stage)[lane]);
+        if (lane < 32) st<ST_WT>(reinterpret_cast<u32x4*>(o) + 64 + lane, reinterpret_cast<const u32x4*>(stage)[64 + lane]);
+        if (lane < 4) st<ST_WT>(reinterpret_cast<u32x4*>(osc) + lane, reinterpret_cast<const u32x4*>(stage + S::SCALES_AT)[lane]);
+    } else {
+        const int64_t left = (numel * 6 + 7) / 8 - tile * kMx6TileBytes;   // code bytes of the tensor from the tile's first on (<= 1536)
+        for (int b = lane; b < left && b < kMx6TileBytes; b += 64) o[b] = stage[b];
+        if (tile * 64 + lane < nblocks) osc[lane] = stage[S::SCALES_AT + lane];
+    }
+}
+
+// Its guarded form: the same loop through mx6_encode_sr.
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_fp6_sr_guarded_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks,
+                                  uint64_t seed, uint64_t index_base) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kGroupedBlock;
+    for (int64_t b = static_cast<int64_t>(blockIdx.x) * kGroupedBlock + threadIdx.x; b < nblocks; b += stride) {
+        const int64_t i0 = b * kMxBlock;
+        const int n = numel - i0 < kMxBlock ? static_cast<int>(numel - i0) : kMxBlock;
+        uint32_t w[kMx6Words<DT_IN>];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {                              // elements at or past numel: quiet NaNs, as grouped_load has them
+            if constexpr (DT_IN == DT_F32) {
+                w[j] = 2 * j < n ? static_cast<const uint32_t*>(in)[i0 + 2 * j] : 0x7fc00000u;
+                w[16 + j] = 2 * j + 1 < n ? static_cast<const uint32_t*>(in)[i0 + 2 * j + 1] : 0x7fc00000u;
+            } else {
+                const uint32_t lo = 2 * j < n ? static_cast<const uint16_t*>(in)[i0 + 2 * j] : 0x7fc0u;
+                const uint32_t hi = 2 * j + 1 < n ? static_cast<const uint16_t*>(in)[i0 + 2 * j + 1] : 0x7fc0u;
+                w[j] = lo | (hi << 16);
+            }
+        }
+        uint32_t s;
+        u32x6 c;
+        mx6_encode_sr<FMT, DT_IN>(w, mx_sr_keys(seed, index_base + static_cast<uint64_t>(i0)), s, c);
         scales[b] = static_cast<uint8_t>(s);
         const int nbytes = (n * 6 + 7) / 8;
 #pragma unroll

@@ -78,6 +78,66 @@ __device__ __forceinline__ uint32_t mx_scale_byte(uint32_t amax_key) {
 
 __device__ __forceinline__ float mx_scale_operand(uint32_t s) { return __uint_as_float(s << 23); }
 
+// ---- stochastic rounding: what the RM = MX_SR instantiations add ---------------------------------------------------------------------------------
+enum : int { MX_RN = 0, MX_SR = 1 };
+
+// The four element formats as the rounding sees them: mantissa bits, the exponent of the smallest normal, emax and the mantissa field (float32) of
+// the largest magnitude (6, 448, 7.5, 28).
+template <int FMT>
+struct MxSrFormat {
+    static constexpr int MBITS = FMT == MX_FP4_E2M1 ? 1 : FMT == MX_FP6_E3M2 ? 2 : 3;
+    static constexpr int EMIN = FMT == MX_FP8_E4M3 ? -6 : FMT == MX_FP6_E3M2 ? -2 : 0;
+    static constexpr int EMAX = FMT == MX_FP8_E4M3 ? 8 : FMT == MX_FP6_E3M2 ? 4 : 2;
+    static constexpr uint32_t TOP_MANT = FMT == MX_FP4_E2M1 ? 0x400000u : FMT == MX_FP6_E2M3 ? 0x700000u : 0x600000u;
+};
+
+// The scale byte with headroom: one more than max(E - emax, 0) when the finite amax (key: mx_abs_key's, exponent field E >= emax) has a mantissa
+// above the top magnitude's, so that no finite element exceeds the top in the scaled domain.
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_sr_scale_byte(uint32_t amax_key) {
+    using F = MxSrFormat<FMT>;
+    const int s = static_cast<int>(amax_key >> 23) - F::EMAX;
+    const bool bump = s >= 0 && amax_key < 0x7f800000u && (amax_key & 0x7fffffu) > F::TOP_MANT;
+    return static_cast<uint32_t>(s > 0 ? s : 0) + (bump ? 1u : 0u);
+}
+
+// The keys of the counter hash (device_math.hpp: element_key) a tile can meet, from the global index g0 of its first element: the tile is far
+// shorter than 2^32 elements, so an element's upper half is g0's or the next one -- the next exactly when the lower half has wrapped.
+struct MxSrKeys {
+    uint32_t lo0, key0, key1;
+};
+
+__device__ __forceinline__ MxSrKeys mx_sr_keys(uint64_t seed, uint64_t g0) {
+    const uint32_t seed_lo = static_cast<uint32_t>(seed), seed_hi = static_cast<uint32_t>(seed >> 32), hi0 = static_cast<uint32_t>(g0 >> 32);
+    return {static_cast<uint32_t>(g0), mix32(hi0 ^ seed_hi) + seed_lo, mix32((hi0 + 1u) ^ seed_hi) + seed_lo};
+}
+
+// floor(element_threshold(seed, g0 + off) * 2^24)
+__device__ __forceinline__ uint32_t mx_sr_threshold(const MxSrKeys& k, uint32_t off) {
+    const uint32_t lo = k.lo0 + off;
+    return mix32(lo ^ (lo < k.lo0 ? k.key1 : k.key0)) >> 8;
+}
+
+// x (float32 bits) under scale byte s -> the float32 bits of its stochastically rounded value IN THE SCALED DOMAIN, x's sign kept: a magnitude the
+// format holds exactly (its denormals included), so that the nearest conversion under the scale operand 1.0 only encodes it.  t is the element's
+// 24-bit hash word.  With v = |x| * 2^(127 - s) in the binade of exponent field kf, the format's step there is 2^(e - 127 - MBITS), e = max(kf,
+// EMIN + 127); w = floor(v / step * 2^24) = (significand << (MBITS + 1)) >> (e - kf), and (w + t) >> 24 is the definition's choice between lo and
+// hi in units of the step.  A v below 2^-126 (kf = 0, also a rounded-off ldexp) is more than 2^24 steps below the first one and gives 0 like every
+// w < 2^24 - t.  Infinities and NaNs pass through for the conversion and its fix-ups.
+template <int FMT>
+__device__ __forceinline__ uint32_t mx_sr_round(uint32_t x, uint32_t s, uint32_t t) {
+    using F = MxSrFormat<FMT>;
+    constexpr int FMIN = F::EMIN + 127;
+    const uint32_t v = __float_as_uint(__builtin_amdgcn_ldexpf(__uint_as_float(x & 0x7fffffffu), 127 - static_cast<int>(s)));
+    const int kf = static_cast<int>(v >> 23);
+    const int e = kf > FMIN ? kf : FMIN;
+    const int d = e - kf < 31 ? e - kf : 31;
+    const uint32_t w = (((v & 0x7fffffu) | 0x800000u) << (F::MBITS + 1)) >> d;
+    const uint32_t m = (w + t) >> 24;                               // 0 .. 2^(MBITS + 1), in steps
+    const uint32_t r = m == 0 ? 0u : __float_as_uint(static_cast<float>(m)) + (static_cast<uint32_t>(e - 127 - F::MBITS) << 23);
+    return (kf == 255 ? v : r) | (x & 0x80000000u);
+}
+
 // Behind the FP8 conversion: w holds four codes; notnan has 0x01 in byte j when element j was no NaN.  A NaN byte (0x7f / 0xff) of such an
 // element stands for "above 464" or an infinity: one less is the largest finite code of its sign.  No borrow leaves a byte.
 __device__ __forceinline__ uint32_t mx_fp8_saturate(uint32_t w, uint32_t notnan) {
@@ -86,8 +146,16 @@ __device__ __forceinline__ uint32_t mx_fp8_saturate(uint32_t w, uint32_t notnan)
 }
 
 // The codes of the N = 4 or 8 elements whose float32 bits are in x, under scale byte s: N * BITS / 8 bytes, element 0 lowest, in w
-template <int FMT, int N>
-__device__ __forceinline__ void mx_encode(const uint32_t (&x)[N], uint32_t s, uint32_t (&w)[N * MxFormat<FMT>::BITS > 32 ? 2 : 1]) {
+// RM = MX_SR: t holds the elements' hash words; every element is rounded in the scaled domain first (mx_sr_round) and encoded under scale byte 127.
+template <int FMT, int N, int RM = MX_RN>
+__device__ __forceinline__ void mx_encode(const uint32_t (&x)[N], uint32_t s, uint32_t (&w)[N * MxFormat<FMT>::BITS > 32 ? 2 : 1], const uint32_t* t = nullptr) {
+    if constexpr (RM == MX_SR) {
+        uint32_t y[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) y[e] = mx_sr_round<FMT>(x[e], s, t[e]);
+        mx_encode<FMT, N>(y, 127u, w);
+        return;
+    }
     const float scale = mx_scale_operand(s);
     if constexpr (FMT == MX_FP4_E2M1) {
         uint32_t r = 0;
@@ -152,10 +220,12 @@ __device__ __forceinline__ void mx_unpack_bits(const u32x4& raw, uint32_t (&x)[I
 }
 
 // The tile's NV rows in `raw` (grouped_load: elements at or past numel are quiet NaNs) -> its codes and scale bytes, staged through the wave's LDS
-// slices and stored.  Shared by the single kernel, the batch (kernels_mx_batch.hip) and the fused reduce (mx_reduce_kernels.hpp).
-template <int DT_IN, int FMT>
+// slices and stored.  Shared by the single kernel, the batch (kernels_mx_batch.hip) and the fused reduce (mx_reduce_kernels.hpp).  RM = MX_SR: keys
+// are mx_sr_keys of the global index of the tile's first element.
+template <int DT_IN, int FMT, int RM = MX_RN>
 __device__ __forceinline__ void mx_quantize_rows(const u32x4 (&raw)[MxQuantTile<DT_IN, FMT>::NV], uint8_t* __restrict__ codes, uint8_t* __restrict__ scales,
-                                                 int64_t numel, int64_t nblocks, int64_t tile, bool full, int lane, uint8_t* stage, uint8_t* stage_scales) {
+                                                 int64_t numel, int64_t nblocks, int64_t tile, bool full, int lane, uint8_t* stage, uint8_t* stage_scales,
+                                                 [[maybe_unused]] const MxSrKeys& keys = {}) {
     using T = MxQuantTile<DT_IN, FMT>;
     constexpr int EPV = T::EPV, OB = T::OB, NV = T::NV, LPB = T::LPB, BPR = T::BPR, NB = T::NB;
 #pragma unroll
@@ -168,10 +238,17 @@ __device__ __forceinline__ void mx_quantize_rows(const u32x4 (&raw)[MxQuantTile<
             const uint32_t k = mx_abs_key(x[e]);
             key = k > key ? k : key;
         }
-        const uint32_t s = mx_scale_byte<FMT>(mx_block_max<LPB>(key));
+        const uint32_t s = RM == MX_SR ? mx_sr_scale_byte<FMT>(mx_block_max<LPB>(key)) : mx_scale_byte<FMT>(mx_block_max<LPB>(key));
         if (lane % LPB == 0) stage_scales[r * BPR + lane / LPB] = static_cast<uint8_t>(s);
         uint32_t w[OB > 4 ? 2 : 1];
-        mx_encode<FMT, EPV>(x, s, w);
+        if constexpr (RM == MX_SR) {
+            uint32_t t[EPV];
+#pragma unroll
+            for (int e = 0; e < EPV; ++e) t[e] = mx_sr_threshold(keys, static_cast<uint32_t>((r * 64 + lane) * EPV + e));
+            mx_encode<FMT, EPV, MX_SR>(x, s, w, t);
+        } else {
+            mx_encode<FMT, EPV>(x, s, w);
+        }
         uint8_t* dst = stage + (r * 64 + lane) * OB;
         if constexpr (OB == 2) *reinterpret_cast<uint16_t*>(dst) = static_cast<uint16_t>(w[0]);
         else if constexpr (OB == 4) *reinterpret_cast<uint32_t*>(dst) = w[0];
@@ -194,15 +271,19 @@ __device__ __forceinline__ void mx_quantize_rows(const u32x4 (&raw)[MxQuantTile<
 }
 
 // one wave's tile of one tensor (tile * TILE_ELEMS < numel): load, then mx_quantize_rows
-template <int DT_IN, int FMT>
+template <int DT_IN, int FMT, int RM = MX_RN>
 __device__ __forceinline__ void mx_quantize_tile(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel,
-                                                 int64_t nblocks, int64_t tile, int lane, uint8_t* stage, uint8_t* stage_scales) {
+                                                 int64_t nblocks, int64_t tile, int lane, uint8_t* stage, uint8_t* stage_scales, uint64_t seed = 0,
+                                                 uint64_t index_base = 0) {
     using T = MxQuantTile<DT_IN, FMT>;
     const int64_t e0 = tile * T::TILE_ELEMS;
     const bool full = e0 + T::TILE_ELEMS <= numel;                  // wave-uniform
     u32x4 raw[T::NV];
     grouped_load<DT_IN, T::NV>(in, numel, e0 / T::EPV, lane, full, raw);
-    mx_quantize_rows<DT_IN, FMT>(raw, codes, scales, numel, nblocks, tile, full, lane, stage, stage_scales);
+    if constexpr (RM == MX_SR)
+        mx_quantize_rows<DT_IN, FMT, MX_SR>(raw, codes, scales, numel, nblocks, tile, full, lane, stage, stage_scales,
+                                            mx_sr_keys(seed, index_base + static_cast<uint64_t>(e0)));
+    else mx_quantize_rows<DT_IN, FMT>(raw, codes, scales, numel, nblocks, tile, full, lane, stage, stage_scales);
 }
 
 template <int DT_IN, int FMT>
@@ -218,6 +299,23 @@ quantize_mx_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uin
     const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
     if (tile * T::TILE_ELEMS >= numel) return;
     mx_quantize_tile<DT_IN, FMT>(in, codes, scales, numel, nblocks, tile, lane, s_codes[wave], s_scales[wave]);
+}
+
+// The same launch with stochastic rounding: element i has global index index_base + i (seed and base by value: capturable).
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_sr_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks, uint64_t seed,
+                      uint64_t index_base) {
+    using T = MxQuantTile<DT_IN, FMT>;
+    constexpr int WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::OUT_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][T::NB];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t tile = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    if (tile * T::TILE_ELEMS >= numel) return;
+    mx_quantize_tile<DT_IN, FMT, MX_SR>(in, codes, scales, numel, nblocks, tile, lane, s_codes[wave], s_scales[wave], seed, index_base);
 }
 
 // element i of a float32 / bfloat16 tensor as float32 bits
@@ -247,6 +345,42 @@ quantize_mx_guarded_kernel(const void* __restrict__ in, uint8_t* __restrict__ co
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[e] = j + e < n ? mx_load_bits<DT_IN>(in, i0 + j + e) : 0u;
             mx_encode<FMT, 4>(x, s, w);
+            if constexpr (FMT == MX_FP4_E2M1) {
+                codes[(i0 + j) / 2] = static_cast<uint8_t>(w[0]);
+                if (j + 2 < n) codes[(i0 + j) / 2 + 1] = static_cast<uint8_t>(w[0] >> 8);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (j + e < n) codes[i0 + j + e] = static_cast<uint8_t>(w[0] >> (8 * e));
+            }
+        }
+    }
+}
+
+// The guarded form with stochastic rounding: the same loop, the headroom scale byte and the hash words from the block's own keys.
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_sr_guarded_kernel(const void* __restrict__ in, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales, int64_t numel, int64_t nblocks,
+                              uint64_t seed, uint64_t index_base) {
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kGroupedBlock;
+    for (int64_t b = static_cast<int64_t>(blockIdx.x) * kGroupedBlock + threadIdx.x; b < nblocks; b += stride) {
+        const int64_t i0 = b * kMxBlock;
+        const int n = numel - i0 < kMxBlock ? static_cast<int>(numel - i0) : kMxBlock;
+        uint32_t key = 0;
+        for (int j = 0; j < n; ++j) {
+            const uint32_t k = mx_abs_key(mx_load_bits<DT_IN>(in, i0 + j));
+            key = k > key ? k : key;
+        }
+        const uint32_t s = mx_sr_scale_byte<FMT>(key);
+        const MxSrKeys keys = mx_sr_keys(seed, index_base + static_cast<uint64_t>(i0));
+        scales[b] = static_cast<uint8_t>(s);
+        for (int j = 0; j < n; j += 4) {
+            uint32_t x[4], t[4], w[1];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = j + e < n ? mx_load_bits<DT_IN>(in, i0 + j + e) : 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) t[e] = mx_sr_threshold(keys, static_cast<uint32_t>(j + e));
+            mx_encode<FMT, 4, MX_SR>(x, s, w, t);
             if constexpr (FMT == MX_FP4_E2M1) {
                 codes[(i0 + j) / 2] = static_cast<uint8_t>(w[0]);
                 if (j + 2 < n) codes[(i0 + j) / 2 + 1] = static_cast<uint8_t>(w[0] >> 8);

@@ -367,6 +367,30 @@ quantize_mx_batch_kernel(MxQuantBatchArgs a) {
                                  s_scales[wave]);
 }
 
+// The batch with stochastic rounding: one seed, member t's elements at the global indices index_base[t] + i -- the bytes of quantize_mx_sr_kernel on it.
+struct MxSrBatchArgs {
+    uint64_t seed;
+    uint64_t index_base[kMxBatchMax];
+};
+
+template <int DT_IN, int FMT>
+__global__ void __launch_bounds__(kGroupedBlock)
+quantize_mx_sr_batch_kernel(MxQuantBatchArgs a, MxSrBatchArgs sr) {
+    using T = MxQuantTile<DT_IN, FMT>;
+    constexpr int WAVES = kGroupedBlock / 64;
+    __shared__ __attribute__((aligned(16))) uint8_t s_codes[WAVES][T::OUT_BYTES];
+    __shared__ __attribute__((aligned(16))) uint8_t s_scales[WAVES][T::NB];
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t c = static_cast<int64_t>(blockIdx.x) * WAVES + wave;
+    int t;
+    if (!grouped_batch_tensor(a, c, t)) return;
+    const int64_t numel = a.numel[t];
+    mx_quantize_tile<DT_IN, FMT, MX_SR>(a.in[t], a.codes[t], a.scales[t], numel, (numel + kMxBlock - 1) / kMxBlock, c - a.chunk_begin[t], lane, s_codes[wave],
+                                        s_scales[wave], sr.seed, sr.index_base[t]);
+}
+
 template <int FMT, int DT_OUT, int OP>
 __global__ void __launch_bounds__(kGroupedBlock)
 dequantize_mx_batch_kernel(MxDequantBatchArgs a) {

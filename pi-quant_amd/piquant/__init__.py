@@ -479,6 +479,25 @@ class Context:
         self.assume_device_pointers(_device_ptrs)
         C.piquant_hip_quantize_mx(self._ctx, ptr_in, dtype_in.value, codes_ptr, scales_ptr, numel, fmt)
 
+    def quantize_mx_sr_ptr(self, ptr_in: int, dtype_in: DataType, codes_ptr: int, scales_ptr: int, numel: int, fmt: int, seed: int, index_base: int = 0,
+                           _device_ptrs: bool = False) -> None:
+        """``quantize_mx_ptr`` with stochastic rounding (``piquant_hip_quantize_mx_sr``): unbiased, the scale byte with headroom; element i is rounded
+        by the counter hash of ``seed`` at the global index ``index_base + i`` (both 64-bit, passed by value)."""
+        assert dtype_in.is_dequantized and fmt in (0, 1, 2, 3) and 0 <= seed < 1 << 64 and 0 <= index_base < 1 << 64
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx_sr(self._ctx, ptr_in, dtype_in.value, codes_ptr, scales_ptr, numel, fmt, seed, index_base)
+
+    def quantize_mx_sr_batch_ptr(self, ptrs_in, dtype_in: DataType, codes_ptrs, scales_ptrs, numels, fmt: int, seed: int, index_bases,
+                                 _device_ptrs: bool = False) -> None:
+        """``quantize_mx_sr_ptr`` for several independent tensors, up to 16 per kernel launch (``piquant_hip_quantize_mx_sr_batch``): one seed,
+        member i at ``index_bases[i]``."""
+        n = len(ptrs_in)
+        assert dtype_in.is_dequantized and fmt in (0, 1) and n == len(codes_ptrs) == len(scales_ptrs) == len(numels) == len(index_bases)
+        assert 0 <= seed < 1 << 64 and all(0 <= b < 1 << 64 for b in index_bases)
+        self.assume_device_pointers(_device_ptrs)
+        C.piquant_hip_quantize_mx_sr_batch(self._ctx, (_C.c_void_p * n)(*ptrs_in), dtype_in.value, (_C.c_void_p * n)(*codes_ptrs),
+                                           (_C.c_void_p * n)(*scales_ptrs), (_C.c_size_t * n)(*numels), n, fmt, seed, (_C.c_uint64 * n)(*index_bases))
+
     def dequantize_mx_ptr(self, codes_ptr: int, scales_ptr: int, ptr_out: int, dtype_out: DataType, numel: int, fmt: int, reduce_op: ReduceOp,
                           _device_ptrs: bool = False) -> None:
         """MX block dequantize (``piquant_hip_dequantize_mx``), the buffers of ``quantize_mx_ptr``."""

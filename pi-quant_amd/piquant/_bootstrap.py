@@ -60,6 +60,9 @@ _DECLS = [
     ('piquant_hip_dequantize_grouped', None, [_vp, _vp, _int, _vp, _int, _sz, _sz, _vp, _vp, _int]),
     ('piquant_hip_quantize_mx', None, [_vp, _vp, _int, _vp, _vp, _sz, _int]),
     ('piquant_hip_dequantize_mx', None, [_vp, _vp, _vp, _vp, _int, _sz, _int, _int]),
+    ('piquant_hip_quantize_mx_sr', None, [_vp, _vp, _int, _vp, _vp, _sz, _int, C.c_uint64, C.c_uint64]),
+    ('piquant_hip_quantize_mx_sr_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz, _int,
+                                                C.c_uint64, C.POINTER(C.c_uint64)]),
     ('piquant_hip_dequantize_sum_mx', None, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _int, _sz, _int, _int]),
     ('piquant_hip_reduce_quantize_mx', None, [_vp, _vp, _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _sz, _vp, _vp, _sz, _int]),
     ('piquant_hip_quantize_mx_batch', None, [_vp, C.POINTER(C.c_void_p), _int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(_sz), _sz, _int]),

@@ -742,16 +742,38 @@ def _check_mx_bytes(t, nbytes: int, what: str) -> None:
              f'{what} must be a contiguous 1-D uint8 tensor of {nbytes} bytes')
 
 
+def _check_mx_rounding(round_mode, seed) -> Optional[int]:
+    """The rounding of an MX quantize call: None for 'nearest' (which takes no seed), the seed modulo 2^64 for 'stochastic' (which needs one)."""
+    _require(round_mode in ('nearest', 'stochastic'), f"round_mode must be 'nearest' or 'stochastic', got {round_mode!r}")
+    if round_mode == 'nearest':
+        _require(seed is None, "seed= belongs to round_mode='stochastic': nearest rounding draws nothing")
+        return None
+    _require(seed is not None, "round_mode='stochastic' needs seed=: the rounding is a function of (seed, global index)")
+    return _check_seed(seed)
+
+
+def _check_mx_index_base(base, what: str = 'index_base') -> int:
+    _require(isinstance(base, int) and not isinstance(base, bool) and 0 <= base < 1 << 64, f'{what} must be an int in [0, 2^64), got {base!r}')
+    return base
+
+
 def quantize_mx(tensor: torch.Tensor, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None, out: Optional[torch.Tensor] = None,
-                out_scales: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                out_scales: Optional[torch.Tensor] = None, round_mode: str = 'nearest', seed: Optional[int] = None,
+                index_base: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """OCP microscaling quantization (``include/piquant_hip.h``, piquant_hip_quantize_mx): the flattened tensor is cut into blocks of 32 elements
     (the last may be ragged), each stored as FP4 E2M1 (``'fp4_e2m1'``), FP6 E2M3 (``'fp6_e2m3'``), FP6 E3M2 (``'fp6_e3m2'``) or FP8 E4M3
     (``'fp8_e4m3'``) codes under one power-of-two scale byte.  Nearest rounding, ties to even, saturating.  Returns (codes, scales), flat uint8
     tensors on the tensor's device: ``ceil(numel / 2)`` (FP4, even index in the low nibble), ``ceil(6 * numel / 8)`` (FP6: element i in bits
     [6i, 6i + 6) of the little-endian bit string, 24 bytes a block) or ``numel`` (FP8) code bytes and ``ceil(numel / 32)`` scale bytes.  FP4 and
     FP8 ``.view()`` as ``torch.float4_e2m1fn_x2`` / ``torch.float8_e4m3fn``, the scales as ``torch.float8_e8m0fnu``.  One asynchronous launch on
-    the current stream."""
+    the current stream.
+    ``round_mode='stochastic'`` (piquant_hip_quantize_mx_sr) rounds every element up or down with the probability that makes the dequantized value
+    unbiased, under a scale byte with headroom so that nothing is clipped; the choice is a function of ``seed`` (an int, taken modulo 2^64) and the
+    element's global index ``index_base + i``: pieces of a tensor cut at multiples of 32 elements and quantized with their offsets as
+    ``index_base`` give the bytes of the one call.  ``seed`` with ``'nearest'`` is a ValueError."""
     _check_mx_format(format, fp6=True)
+    seed = _check_mx_rounding(round_mode, seed)
+    index_base = _check_mx_index_base(index_base)
     _require(isinstance(tensor, torch.Tensor) and tensor.dtype in _DEQUANT_TYPES, 'tensor must be a float32 or bfloat16 tensor')
     ncodes, nscales = mx_nbytes(tensor.numel(), format)
     if out is not None:
@@ -766,8 +788,12 @@ def quantize_mx(tensor: torch.Tensor, *, format: str = 'fp4_e2m1', ctx: Optional
     codes = torch.empty(ncodes, dtype=torch.uint8, device=tensor.device) if out is None else out
     scales = torch.empty(nscales, dtype=torch.uint8, device=tensor.device) if out_scales is None else out_scales
     ctx = _ctx_for(tensor, ctx)
-    ctx.quantize_mx_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), codes.data_ptr(), scales.data_ptr(), tensor.numel(), MX_FORMATS[format],
-                        _device_ptrs=True)
+    if seed is None:
+        ctx.quantize_mx_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), codes.data_ptr(), scales.data_ptr(), tensor.numel(), MX_FORMATS[format],
+                            _device_ptrs=True)
+    else:
+        ctx.quantize_mx_sr_ptr(tensor.data_ptr(), torch_to_piquant_dtype(tensor.dtype), codes.data_ptr(), scales.data_ptr(), tensor.numel(),
+                               MX_FORMATS[format], seed, index_base, _device_ptrs=True)
     return codes, scales
 
 
@@ -807,11 +833,19 @@ def _check_mx_terms(terms, numel: int, format: str, device) -> None:
         _require(term[0].device == device and term[1].device == device, f'terms[{i}] must live on {device}')
 
 
-def quantize_mx_batch(tensors, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None):
+def quantize_mx_batch(tensors, *, format: str = 'fp4_e2m1', ctx: Optional[Context] = None, round_mode: str = 'nearest', seed: Optional[int] = None,
+                      index_bases=None):
     """``quantize_mx`` of every tensor of a list (one float dtype, one device) with ONE launch per 16 tensors
-    (piquant_hip_quantize_mx_batch); returns the list of (codes, scales), each the bytes of the single call.  Empty tensors take no part."""
+    (piquant_hip_quantize_mx_batch); returns the list of (codes, scales), each the bytes of the single call.  Empty tensors take no part.
+    ``round_mode='stochastic'`` with ``seed`` (piquant_hip_quantize_mx_sr_batch): member i is ``quantize_mx(tensors[i], round_mode='stochastic',
+    seed=seed, index_base=index_bases[i])``; ``index_bases`` is one int per tensor, or None for all zeros."""
     _check_mx_format(format)
+    seed = _check_mx_rounding(round_mode, seed)
     _require(isinstance(tensors, (list, tuple)), 'tensors must be a list of tensors')
+    if index_bases is None:
+        index_bases = [0] * len(tensors)
+    _require(isinstance(index_bases, (list, tuple)) and len(index_bases) == len(tensors), 'index_bases must hold one int per tensor')
+    index_bases = [_check_mx_index_base(b, f'index_bases[{i}]') for i, b in enumerate(index_bases)]
     for t in tensors:
         _require(isinstance(t, torch.Tensor) and t.dtype in _DEQUANT_TYPES, 'every tensor must be a float32 or bfloat16 tensor')
         _require(t.dtype == tensors[0].dtype and t.device == tensors[0].device, 'the tensors of a batch share one dtype and one device')
@@ -820,8 +854,12 @@ def quantize_mx_batch(tensors, *, format: str = 'fp4_e2m1', ctx: Optional[Contex
         return []
     xs = [t if t.is_contiguous() else t.contiguous() for t in tensors]
     outs = [tuple(torch.empty(n, dtype=torch.uint8, device=x.device) for n in mx_nbytes(x.numel(), format)) for x in xs]
-    _ctx_for(xs[0], ctx).quantize_mx_batch_ptr([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [o[0].data_ptr() for o in outs],
-                                               [o[1].data_ptr() for o in outs], [x.numel() for x in xs], MX_FORMATS[format], _device_ptrs=True)
+    args = ([x.data_ptr() for x in xs], torch_to_piquant_dtype(xs[0].dtype), [o[0].data_ptr() for o in outs], [o[1].data_ptr() for o in outs],
+            [x.numel() for x in xs], MX_FORMATS[format])
+    if seed is None:
+        _ctx_for(xs[0], ctx).quantize_mx_batch_ptr(*args, _device_ptrs=True)
+    else:
+        _ctx_for(xs[0], ctx).quantize_mx_sr_batch_ptr(*args, seed, index_bases, _device_ptrs=True)
     return outs
 
 

@@ -32,6 +32,12 @@ FP8 call of the same shape in the same run (the four formats in turn, same proto
 whether its time is within 1.15 x the FP8 time x the ratio of their algorithmic bytes ("met" / "missed") and whether it is below the FP8 time.
 
     python tools/mx_bench.py --rows fp6 [--windows 7] [--rotate-gb 3.3] [--out FILE]
+
+--rows sr measures quantize_mx with stochastic rounding (piquant_hip_quantize_mx_sr) in the four formats for both float types, each next to the
+nearest call of the same pair in the same run (nearest window, stochastic window, in turn; same protocol) and writes profiles/mx_sr_bench.json: a
+row gives both times, their windows and the ratio stochastic / nearest.  No ratio is fixed in advance.
+
+    python tools/mx_bench.py --rows sr [--windows 7] [--rotate-gb 3.3] [--out FILE]
 """
 import argparse
 import json
@@ -359,15 +365,63 @@ def fp6_main(args):
     print(f"wrote {args.out}")
 
 
+def sr_main(args):
+    """quantize_mx with stochastic rounding next to the nearest call of the same pair (module docstring)."""
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    ctx = piquant.Context.get(0)
+    stream = torch.cuda.current_stream()
+    ctx.set_stream(stream.cuda_stream)
+    ctx.set_blocking(False)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    nblocks = pt.mx_nbytes(NUMEL, "fp8_e4m3")[1]
+    rows = []
+    for fname, (fdt, tdt, esize) in FLOAT.items():
+        nbuf = max(3, int(args.rotate_gb * 1e9 / (NUMEL * esize)) + 1)
+        per_window = max(2 * nbuf, 32)
+        xs = [torch.empty(NUMEL, device=dev).uniform_(-1, 1, generator=gen).to(tdt) for _ in range(nbuf)]
+        mxs = [torch.empty(nblocks, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+        for fmt, f in pt.MX_FORMATS.items():
+            ncodes = pt.mx_nbytes(NUMEL, fmt)[0]
+            codes = [torch.empty(ncodes, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+            calls = {
+                "nearest": lambda i: ctx.quantize_mx_ptr(xs[i].data_ptr(), fdt, codes[i].data_ptr(), mxs[i].data_ptr(), NUMEL, f, _device_ptrs=True),
+                "stochastic": lambda i: ctx.quantize_mx_sr_ptr(xs[i].data_ptr(), fdt, codes[i].data_ptr(), mxs[i].data_ptr(), NUMEL, f, 0x9E3779B97F4A7C15,
+                                                               1 << 40, _device_ptrs=True),
+            }
+            res = timed_alternating(calls, nbuf, args.windows, per_window, stream)
+            nbytes = NUMEL * esize + ncodes + nblocks
+            rows.append(row("quantize_mx", f"{fname} {fmt}", res["nearest"][0], nbytes, res["nearest"][1]))
+            r = row("quantize_mx_sr", f"{fname} {fmt}", res["stochastic"][0], nbytes, res["stochastic"][1])
+            r["nearest_us"], r["over_nearest"] = round(res["nearest"][0], 3), round(res["stochastic"][0] / res["nearest"][0], 3)
+            print(f"    stochastic / nearest = {r['over_nearest']:.3f}", flush=True)
+            rows.append(r)
+            del codes
+        del xs, mxs
+        torch.cuda.empty_cache()
+    out = {"numel": NUMEL, "device": torch.cuda.get_device_name(0), "windows": args.windows, "rotate_gb": args.rotate_gb,
+           "command": "python tools/mx_bench.py --rows sr",
+           "protocol": "alternating windows of back-to-back calls (nearest, stochastic in turn), HIP events, median over windows; rotated float and code "
+                       "buffers; no target ratio",
+           "spread": "run-to-run spread not measured (one run); every row carries its windows",
+           "not_measured": "other sizes, the guarded kernels, the batch", "rows": rows}
+    Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+    print(f"wrote {args.out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--rows", choices=("calls", "wire", "ef", "fp6"), default="calls")
+    ap.add_argument("--rows", choices=("calls", "wire", "ef", "fp6", "sr"), default="calls")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--rotate-gb", type=float, default=3.3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = str(ROOT / "profiles" / {"calls": "mx_bench.json", "wire": "mx_wire_bench.json", "ef": "mx_ef_bench.json", "fp6": "mx_fp6_bench.json"}[args.rows])
+        args.out = str(ROOT / "profiles" / {"calls": "mx_bench.json", "wire": "mx_wire_bench.json", "ef": "mx_ef_bench.json", "fp6": "mx_fp6_bench.json",
+                                                  "sr": "mx_sr_bench.json"}[args.rows])
+    if args.rows == "sr":
+        return sr_main(args)
     if args.rows == "fp6":
         return fp6_main(args)
     if args.rows == "wire":
